@@ -11,12 +11,16 @@ flight per replay, one stream each).
     python bench.py                              # 1 GPU
     python bench.py --gpus 8 --steps K --warmup W   # launches 8 ranks itself (torch.distributed.run, RCCL) — or run it
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
+    python bench.py --full                       # + everything below the headline (roofline, extra, cpu_baseline, ...)
 
 N>1: every rank runs its own K samples (weak scaling; sample indices interleaved by rank; `--scaling strong
 --total-samples S` shards S samples instead), then ONE RCCL all-reduce of the packed statistics inside the timed
 region.  A run whose process group does not have exactly --gpus ranks aborts: it cannot print a line.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with
+A plain run sets up, warms up, times ONE region of exactly K MC samples (`ms_per_step` = that region / K) and prints the
+line; `--dump-outputs DIR` then writes the predictive statistics of that region (mc.unpack: what a caller of the MC path
+receives) and the logits of its last MC sample as DIR/<name>.npy.  `--full` times the region back to back until it has
+settled (`--repeats`, `--settle-seconds`) and adds to the line (rank 0):
   roofline      dominant kernel = the stride-1 3x3 Flipout contraction (btx::contract_taps_kernel): algorithmic FLOPs
                 (2*2*M*N*K per launch) / the GPU time of the same launches, each launch of the step
                 re-issued `reps` times inside a hipGraph and timed with HIP events on the launch stream (no host gaps);
@@ -100,36 +104,23 @@ def _cpu_model_string():
 
 
 def cpu_baseline(typ, bs, budget_s=24.0):
-    """The reference's CPU path on the host cores: the reference itself when /root/reference is present (the build
-    container), else oracle/bt_ref.py — the same ATen calls on the same plain-layout tensors (bit-exact against the
-    reference, tests/test_oracle.py).  Timed twice: all host threads and capped at 32 (on the
-    256-thread GPU-box host the uncapped run is slower: serial RNG fills + small convs); `value` = the better one."""
+    """The reference's CPU path on the host cores: oracle/bt_ref.py — the reference's ATen calls on the same plain-layout
+    tensors (bit-exact against the reference, tests/test_oracle.py).  Timed twice: all host threads (at most
+    OMP_NUM_THREADS when that is set) and capped at 32 (on the 256-thread GPU-box host the uncapped run is slower: serial
+    RNG fills + small convs); `value` = the better one."""
     import bayesian_torch_amd as bt
     from bayesian_torch_amd.models.resnet import resnet18
-    kind = "port"
-    ref_root = "/root/reference"
+    from oracle import bt_ref
     torch.manual_seed(0)
-    if os.path.isdir(os.path.join(ref_root, "bayesian_torch")):
-        sys.path.insert(0, ref_root)
-        try:
-            from bayesian_torch.models.dnn_to_bnn import dnn_to_bnn as ref_dnn_to_bnn
-            from bayesian_torch.models.deterministic import resnet_large as ref_resnet
-            m = ref_resnet.resnet18()
-            ref_dnn_to_bnn(m, dict(PRIOR, type=typ, moped_enable=False))
-            m = m.eval()
-            kind = "reference"
-        except Exception:  # noqa
-            kind = "port"
-        finally:
-            sys.path.remove(ref_root)
-    if kind == "port":
-        from oracle import bt_ref
-        m = resnet18()
-        bt.dnn_to_bnn(m, dict(PRIOR, type=typ, moped_enable=False))
-        m = bt_ref.convert_for_baseline(m).eval()
+    m = resnet18()
+    bt.dnn_to_bnn(m, dict(PRIOR, type=typ, moped_enable=False))
+    m = bt_ref.convert_for_baseline(m).eval()
     torch.manual_seed(1234)
     x = torch.randn(bs, 3, 224, 224)
     ncpu = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:  # the host threads this process is given (a share of a larger host)
+        ncpu = min(ncpu, int(omp))
     runs = []
     for cores in sorted({ncpu, min(ncpu, 32)}, reverse=True):
         torch.set_num_threads(cores)
@@ -146,12 +137,10 @@ def cpu_baseline(typ, bs, budget_s=24.0):
                     break
         runs.append({"cores": cores, "value": n / el, "timed_forwards": n})
     best = max(runs, key=lambda r: r["value"])
-    return {"value": best["value"], "unit": "MC-samples/s", "cores": best["cores"], "kind": kind,
+    return {"value": best["value"], "unit": "MC-samples/s", "cores": best["cores"], "kind": "port",
             "cpu": _cpu_model_string(), "host_threads": ncpu, "runs": runs,
             "sample": "%d timed MC forwards (+1 warm-up) per thread count of ResNet18-%s bs%d 224^2 f32, %s" % (
-                best["timed_forwards"], typ, bs,
-                "the reference itself (/root/reference)" if kind == "reference" else
-                "oracle/bt_ref.py ATen op chain on plain-layout weights (/root/reference absent on this box)")}
+                best["timed_forwards"], typ, bs, "oracle/bt_ref.py ATen op chain on plain-layout weights")}
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -469,11 +458,12 @@ class Runner:
                 # ragged last groups (counts that are not a multiple of the lane count): one smaller graph per remainder.
                 # static_input: the batch is the same for every MC sample, so the stem's input is packed into its kernel
                 # layout once per batch (at capture) instead of once per replay
+                # keep_logits: each graph's static logits stay reachable (last_logits(); no work added to the replays)
                 rests = sorted({s % max(1, lanes) for s in sizes} - {0})
                 self.rest = {r: mc.GraphedMC(model, x, kl=kl, lanes=r, concurrent_hint=concurrent_hint, lane_mode=lane_mode,
-                                             static_input=static_input) for r in rests}
+                                             static_input=static_input, keep_logits=True) for r in rests}
                 self.graphed = mc.GraphedMC(model, x, kl=kl, lanes=max(1, lanes), concurrent_hint=concurrent_hint,
-                                            lane_mode=lane_mode, static_input=static_input)
+                                            lane_mode=lane_mode, static_input=static_input, keep_logits=True)
             except Exception as e:  # a runtime that cannot capture: measure the eager path rather than nothing
                 print("bench: hipGraph capture failed (%s: %s) - falling back to eager launches" % (type(e).__name__, e),
                       file=sys.stderr)
@@ -508,6 +498,12 @@ class Runner:
         if rest:
             gr = self.rest[len(rest)]
             gr.run(rest[0]) if gr.lanes == 1 else gr.run_many(rest)
+
+    def last_logits(self, n):
+        """the logits of the last MC sample of a run(indices) with len(indices) == n (None on the eager path)"""
+        if self.graphed is None:
+            return None
+        return self.rest.get(n % self.graphed.lanes, self.graphed).lane_logits[-1]
 
     def zero(self):
         self.packed.zero_()
@@ -623,12 +619,16 @@ def run_resnet_config(arch, typ, prec, bs, moped, steps, warmup, lanes, dev, wor
     runs = timed_mc(runner, mine, warm, world, dev, repeats=repeats, min_seconds=min_seconds)
     elapsed = settled(runs)  # median of the settled half of the back-to-back regions; the first five are listed, the rest summarised
     stats = runner.packed.clone()
+    last = runner.last_logits(len(mine)) if mine else None
+    last = None if last is None else last.float().cpu()
     lanes_used = runner.graphed.lanes if runner.graphed is not None else 0
     sustained = None
     if sustain and dev.type == "cuda" and world == 1 and runner.graphed is not None:
         sustained = sustained_run(runner, lanes_used, dev, seconds=sustain)
     runner.close()
     u = mc.unpack(stats, bs, 1000)
+    if last is not None:
+        u["last_logits"] = last
     assert abs(float(u["samples"]) - n_global) < 0.5, "work was skipped inside the timed region"
     assert torch.isfinite(u["mean_prob"]).all()
     res = {"elapsed": elapsed, "n_global": n_global, "per_rank": len(mine), "kl": kl, "lanes": lanes_used,
@@ -637,7 +637,8 @@ def run_resnet_config(arch, typ, prec, bs, moped, steps, warmup, lanes, dev, wor
            "ms_per_step_runs": [1e3 * r / max(len(mine), 1) for r in runs[:5]], "timed_regions": len(runs),
            "timed_seconds": sum(runs),
            "ms_per_step_all_regions": {"min": 1e3 * min(runs) / max(len(mine), 1), "max": 1e3 * max(runs) / max(len(mine), 1),
-                                       "mean": 1e3 * sum(runs) / len(runs) / max(len(mine), 1)}}
+                                       "mean": 1e3 * sum(runs) / len(runs) / max(len(mine), 1)},
+           "outputs": u}  # the statistics of the last timed region (not part of the JSON result)
     if sustained is not None:
         res["sustained"] = sustained
     known = KL_KNOWN.get((arch, moped))
@@ -858,6 +859,26 @@ def summarise_extra(name, r, prec, table=False):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outputs):
+    """mc.unpack statistics (+ last_logits) -> path/<name>.npy (float32).  Per-example arrays larger than DUMP_LIMIT_BYTES
+    in all keep a fixed, seeded sample of their rows (the same rows in every array, listed in path/rows.npy)."""
+    import numpy as np
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        bs = arrs["mean_prob"].shape[0]
+        keep = max(1, int(bs * DUMP_LIMIT_BYTES * 0.9 / total))
+        rows = np.sort(np.random.default_rng(0).choice(bs, keep, replace=False))
+        arrs = {k: (a[rows] if a.ndim and a.shape[0] == bs else a) for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def auto_lanes(steps, cap=32):
     """MC samples per hipGraph replay: the whole timed region when it fits, else its largest divisor <= cap (>= 8), else 16"""
     if steps <= cap:
@@ -1061,11 +1082,18 @@ def main():
     ap.add_argument("--lane-mode", default="launch", choices=["launch", "streams"], help="launch: the samples of a replay "
                     "are lanes of ONE launch per layer (btx_contract_fwd_lanes); streams: one launch per (layer, sample), "
                     "each sample on its own stream (the round-2 form)")
-    ap.add_argument("--repeats", type=int, default=5, help="the timed region (the same --steps MC samples) is run at least this "
-                    "many times, back to back")
-    ap.add_argument("--settle-seconds", type=float, default=1.0, help="...and on until the regions add up to this long: value / "
+    ap.add_argument("--full", action="store_true", help="measure what the headline does not need as well: settled "
+                    "back-to-back regions (the defaults of --repeats / --settle-seconds become 5 / 1.0), the per-launch "
+                    "roofline and its rocprofv3 traffic, the 2 s sustained replay, the logits parity, the other BASELINE "
+                    "configs (extra) and the CPU baseline; the --no-* options below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the predictive statistics of the timed "
+                    "region (mean_prob, var_prob, predictive_entropy, mutual_information, kl, samples) and the logits of its "
+                    "last MC sample (last_logits) as DIR/<name>.npy, float32")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (the same --steps MC samples) is run at least this "
+                    "many times, back to back (default 1; 5 with --full)")
+    ap.add_argument("--settle-seconds", type=float, default=None, help="...and on until the regions add up to this long: value / "
                     "ms_per_step are the median of the SECOND half of the regions (settled clock); ms_per_step_runs lists the "
-                    "first five, ms_per_step_all_regions min / max / mean of all")
+                    "first five, ms_per_step_all_regions min / max / mean of all (default 0; 1.0 with --full)")
     ap.add_argument("--no-presample", action="store_true")
     ap.add_argument("--latency-plan", action="store_true", help="A/B: plan every launch for its own latency (split-K to fill "
                     "idle CUs) although several MC samples are in flight")
@@ -1086,6 +1114,10 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, sys.argv[1:], args.dry_run))
 
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.settle_seconds is None:
+        args.settle_seconds = 1.0 if args.full else 0.0
     if args.lanes <= 0:
         per_rank = args.steps if args.scaling == "weak" else max(1, -(-args.total_samples // max(1, args.gpus)))
         args.lanes = auto_lanes(per_rank)
@@ -1123,11 +1155,13 @@ def main():
     head = run_resnet_config(args.arch, args.type, args.prec, args.batch, args.moped, args.steps, args.warmup, args.lanes,
                              dev, world, rank, graph=not args.no_graph, fuse=not args.no_fuse,
                              presample=not args.no_presample, scaling=args.scaling, total=args.total_samples,
-                             per_launch=not args.no_launch_timing and rank == 0,
+                             per_launch=args.full and not args.no_launch_timing and rank == 0,
                              concurrent_hint=False if args.latency_plan else None,
-                             parity=(rank == 0 and world == 1 and not args.no_extras), lane_mode=args.lane_mode,
-                             repeats=args.repeats, sustain=0.0 if args.no_sustain else 2.0,
+                             parity=(args.full and rank == 0 and world == 1 and not args.no_extras), lane_mode=args.lane_mode,
+                             repeats=args.repeats, sustain=2.0 if args.full and not args.no_sustain else 0.0,
                              min_seconds=args.settle_seconds)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["outputs"])
     if rank == 0:
         peak = MFMA_PEAK_TFLOPS[args.prec]
         roofline = None
@@ -1210,7 +1244,7 @@ def main():
             out["sustained"] = head["sustained"]
         if "logits_rel_l2_vs_unfused_f32" in head:
             out["logits_rel_l2_vs_unfused_f32"] = head["logits_rel_l2_vs_unfused_f32"]
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             extra = {}
             try:
                 r = run_resnet_config("resnet18", "Reparameterization", "bf16", 64, False, 16, 3, 16, dev, parity=True,
@@ -1257,7 +1291,7 @@ def main():
                                       e["dominant_kernel_tflops"], "peak": MFMA_PEAK_TFLOPS[tag], "value": e["value"],
                                       "frac_e2e": e.get("frac_e2e"), "logits_rel_l2": e.get("logits_rel_l2_vs_unfused_f32")}
                 roofline["modes_within_1e-4"] = modes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.type, args.batch)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
         else:

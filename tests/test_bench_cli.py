@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -179,3 +181,58 @@ def test_timed_regions_settle_and_every_region_is_exactly_the_steps():
     assert len(bench.timed_mc(r2, [1], [0], 1, torch.device("cpu"), repeats=4)) == 4   # no settling asked for: `repeats` regions
     assert bench.settled([9.0, 8.0, 7.0, 1.0, 2.0, 3.0, 2.5, 2.2]) == 2.5              # median of the second half [2.0, 3.0, 2.5, 2.2] -> sorted[2]
     assert bench.settled([3.0, 1.0, 2.0]) == 2.0                                      # fewer than 8 regions: the median of all
+
+
+def test_dump_outputs_writes_float_statistics_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: mc.unpack's statistics as DIR/<name>.npy in float32; past DUMP_LIMIT_BYTES every per-example array
+    keeps the same fixed, seeded rows (listed in rows.npy)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from bayesian_torch_amd import mc
+    packed = torch.zeros(mc.packed_numel(6, 10))
+    for s in range(3):
+        mc.accumulate(packed, torch.randn(6, 10, generator=torch.Generator().manual_seed(s)), kl=2.0)
+    u = mc.unpack(packed, 6, 10)
+    bench.dump_outputs(str(tmp_path / "all"), u)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert set(got) == {"mean_prob", "var_prob", "predictive_entropy", "mutual_information", "kl", "samples"}
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["mean_prob"], u["mean_prob"].numpy())
+    assert float(got["samples"]) == 3.0 and abs(float(got["kl"]) - 2.0) < 1e-6
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 300)  # the six arrays hold 536 bytes
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), u)
+    cut = {p.stem: np.load(p) for p in (tmp_path / "cut1").glob("*.npy")}
+    assert sum(a.nbytes for a in cut.values()) <= 300
+    rows = cut["rows"].astype(np.int64)
+    assert 0 < len(rows) < 6 and cut["mean_prob"].shape == (len(rows), 10)
+    np.testing.assert_array_equal(cut["mean_prob"], u["mean_prob"].numpy()[rows])
+    np.testing.assert_array_equal(cut["mutual_information"], u["mutual_information"].numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "cut2" / "rows.npy"), cut["rows"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_exactly_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps 8 --warmup 2` (no --full): ONE timed region of exactly 8 MC samples, nothing of the full run on the
+    line; --dump-outputs writes the statistics of those 8 samples and the logits of the last one, the same in two runs of the
+    same command"""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        r = _run(["--gpus", "1", "--steps", "8", "--warmup", "2", "--dump-outputs", str(tmp_path / str(k))])
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 8 and d["warmup"] == 2 and d["timed_regions"] == 1 and d["dtype"] == "bf16"
+        assert abs(d["value"] - 8 / (d["ms_per_step"] * 8e-3)) < 2e-4 * d["value"]  # the line carries 5 significant digits
+        assert d["roofline"] is None and d["cpu_baseline"] is None and "extra" not in d and "sustained" not in d
+        outs.append({p.stem: np.load(p) for p in (tmp_path / str(k)).glob("*.npy")})
+    a, b = outs
+    assert set(a) == {"mean_prob", "var_prob", "predictive_entropy", "mutual_information", "kl", "samples", "last_logits"}
+    assert a["last_logits"].shape == (64, 1000) and np.isfinite(a["last_logits"]).all()
+    assert float(a["samples"]) == 8.0 and a["mean_prob"].shape == (64, 1000)
+    assert np.allclose(a["mean_prob"].sum(axis=1), 1.0, atol=1e-3)
+    for name in a:
+        print("%s: max |run 1 - run 2| %.3g" % (name, float(np.abs(a[name] - b[name]).max())))
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-6)

@@ -92,7 +92,8 @@ def test_bench_one_rank_under_torchrun_uses_rccl():
     """`python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1` (how the driver launches N > 1, here N = 1):
     the run initialises RCCL, keeps the one all-reduce inside the timed region and reports rccl_ranks == 1; its rate equals
     the plain `python bench.py --gpus 1` invocation within noise."""
-    common = ["--gpus", "1", "--steps", "8", "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--no-traffic",
+    # --full: settled back-to-back regions on both sides (an 8-sample region is ~4 ms), nothing else of the full run
+    common = ["--gpus", "1", "--steps", "8", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline", "--no-traffic",
               "--no-launch-timing", "--no-sustain"]
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):

@@ -5,7 +5,7 @@
     python tools/refresh_profiles.py install                                        # here: gpurun_out/profiles/* -> profiles/
 
 steps (each writes the files named in its docstring, with the command that produced them in the header):
-  bench       profiles/<PREFIX>_bench_line.json (+ _summary.txt)            python bench.py (the driver's default invocation)
+  bench       profiles/<PREFIX>_bench_line.json (+ _summary.txt)            python bench.py --full
   trace       profiles/<PREFIX>_bench_kernel_trace_stats.txt, _lanes1.txt   rocprofv3 --kernel-trace of the bench command
   pmc         profiles/<PREFIX>_pmc_taps_lanes.txt                          SQ counters of contract_taps_kernel, many-tiles regime
   cfg3        profiles/<PREFIX>_cfg3_kernel_trace_stats.txt, _cfg3_pmc_taps.txt, _cfg3_bench_line.json   BASELINE cfg3 (Reparameterization):
@@ -53,7 +53,7 @@ def variant(name, flags):
 
 
 def step_bench():
-    out = sh("timeout -k 5 600 python bench.py --steps 20 --warmup 5", timeout=2400)  # the driver's invocation
+    out = sh("timeout -k 5 600 python bench.py --full --steps 20 --warmup 5", timeout=2400)  # the driver's full invocation
     line = [l for l in out.splitlines() if l.startswith("{")][-1]  # the compact line (<= 6 KB), LAST on stdout
     c = json.loads(line)
     os.makedirs(OUT, exist_ok=True)
@@ -75,7 +75,7 @@ def step_bench():
     for k, v in d.get("extra", {}).items():
         body += "%s: %s\n" % (k, json.dumps(v)[:600])
     body += "cpu_baseline: %s\n" % json.dumps(d.get("cpu_baseline"))[:400]
-    write(PREFIX + "_bench_summary.txt", "python bench.py --steps 20 --warmup 5   (the driver's invocation; 1 MI355X; the compact JSON line is profiles/" + PREFIX +
+    write(PREFIX + "_bench_summary.txt", "python bench.py --full --steps 20 --warmup 5   (the driver's full invocation; 1 MI355X; the compact JSON line is profiles/" + PREFIX +
           "_bench_line.json, the full result profiles/" + PREFIX + "_bench_detail.json)", body)
 
 
@@ -88,7 +88,7 @@ def step_trace():
     for tag, extra in tags:
         d = os.path.join(ROOT, "gpurun_out", "r6_kt_" + tag)
         shutil.rmtree(d, ignore_errors=True)
-        cmd = "python %s/bench.py --steps 20 --warmup 20 --no-extras --no-cpu-baseline --no-traffic --no-sustain%s" % (ROOT, extra)
+        cmd = "python %s/bench.py --full --steps 20 --warmup 20 --no-extras --no-cpu-baseline --no-traffic --no-sustain%s" % (ROOT, extra)
         sh("timeout -k 5 400 rocprofv3 --kernel-trace --stats -d %s -o kt -- %s" % (d, cmd), cwd="/tmp", timeout=1200)
         db = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
         body = sh("python tools/trace_report.py %s" % db[0]) if db else "(no trace written)\n"
@@ -163,7 +163,7 @@ def step_pmc():
 def step_cfg3():
     """BASELINE cfg3 — dnn_to_bnn(ResNet18) Reparameterization bs 64, 16 MC samples as lanes: the bench command's own line and
     per-launch table, its rocprofv3 kernel trace, and the SQ counters of contract_taps_kernel<bf16, Reparameterization, WIDE>"""
-    cmd = "python %s/bench.py --type Reparameterization --steps 16 --warmup 16 --no-extras --no-cpu-baseline --no-traffic" % ROOT
+    cmd = "python %s/bench.py --full --type Reparameterization --steps 16 --warmup 16 --no-extras --no-cpu-baseline --no-traffic" % ROOT
     out = sh("timeout -k 5 400 " + cmd, timeout=900)
     line = [l for l in out.splitlines() if l.startswith("{")][-1]
     json.dump(json.loads(line), open(os.path.join(OUT, PREFIX + "_cfg3_bench_line.json"), "w"), indent=1)
