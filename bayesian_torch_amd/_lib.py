@@ -14,8 +14,9 @@ FLAG_TRANSPOSED, FLAG_KL_ACCUM, FLAG_ROWFUSE, FLAG_OUT_F32, FLAG_OUT_BF16, FLAG_
 FLAG_REVERSE = 256
 E_UNSUPPORTED = -3
 STREAM_EPS_W, STREAM_EPS_B, STREAM_SIGN_IN, STREAM_SIGN_OUT = 0, 1, 2, 3
-ABI_VERSION = 8
+ABI_VERSION = 9
 FLAG_LANES_SHIFT = 16
+FLAG_LANES_MASK = 0xff << FLAG_LANES_SHIFT
 SAMPLE_SKIP_MU = 1
 
 
@@ -48,6 +49,14 @@ class Lanes(ctypes.Structure):
                 ("res_stride", ctypes.c_int64)]
 
 
+class PlanInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("family", "ksplits", "kper", "kgroups", "wide", "tall", "par_major", "pool_band",
+                                              "nwg", "lanes")] + [("ws_bytes", ctypes.c_uint64)]
+
+
+FAMILIES = ("gather", "regstage", "dma", "gemm8", "patch", "taps", "taps2", "stem", "stem_pool", "pw")  # BTX_FAMILY_* order
+
+
 class Noise(ctypes.Structure):
     _fields_ = [("eps_w", ctypes.c_void_p), ("eps_b", ctypes.c_void_p),
                 ("sign_in", ctypes.c_void_p), ("sign_out", ctypes.c_void_p), ("sampled_w", ctypes.c_void_p)]
@@ -67,7 +76,7 @@ class KlItem(ctypes.Structure):
 
 EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_gauss", "btx_kl_model_workspace_bytes",
            "btx_kl_gauss_model", "btx_kl_gauss_model_bwd", "btx_contract_wgrad",
-           "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
+           "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_contract_plan_info", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
            "btx_mc_packed_floats", "btx_mc_accumulate", "btx_mc_accumulate_lanes", "btx_sampled_w_bytes", "btx_sample_weights", "btx_sampled_w_bytes_lanes", "btx_sample_weights_lanes", "btx_rowfuse_pack", "btx_maxpool2d_cl", "btx_avgpool_global_cl",
            "btx_bn_workspace_bytes", "btx_bn_train_fwd", "btx_bn_train_bwd", "btx_dgrad_weights",
            "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd")
@@ -120,6 +129,8 @@ def lib():
     L.btx_contract_fwd_ex.argtypes = L.btx_contract_fwd.argtypes + [ctypes.POINTER(Epilogue)]
     L.btx_contract_fwd_lanes.restype = i32
     L.btx_contract_fwd_lanes.argtypes = L.btx_contract_fwd_ex.argtypes + [ctypes.POINTER(Lanes)]
+    L.btx_contract_plan_info.restype = i32
+    L.btx_contract_plan_info.argtypes = [i32, ctypes.POINTER(Geom), i32, i32, u32, ctypes.POINTER(Epilogue), ctypes.POINTER(PlanInfo)]
     L.btx_contract_pool_shape.restype = i32
     L.btx_contract_pool_shape.argtypes = [ctypes.POINTER(Geom), i32, i32, u32] + [ctypes.POINTER(ctypes.c_int32)] * 2
     L.btx_out_shape.restype = i32

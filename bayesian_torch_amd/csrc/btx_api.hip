@@ -897,6 +897,10 @@ static bool make_patch_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t 
   }
   const long long base1 = (long long)pl->mtiles * (pt->wide ? pl->ntiles / 2 : pl->ntiles) * g->groups;
   const long long base = base1 * plan_lanes(flags);
+  // Throughput plans decide the K split on the grid of the NARROW tile: there the wide tile changes the tile shape, never kper /
+  // ksplits.  (A launch with lanes goes wide where the one-lane plan of its samples stays narrow: both must sum in the same
+  // order.)  The latency plan of a lone launch promises no such thing and prices the grid it launches.
+  const long long base1n = throughput_plan(flags) ? (long long)pl->mtiles * pl->ntiles * g->groups : base1;
   // Few pixel tiles (at most one 4-wave block per CU): 8-wave blocks of two K-groups — split-K inside the workgroup
   // through LDS instead of through HBM, and two waves per SIMD.  BTX_NO_KG=1 disables (A/B).
   // BTX_FLAG_CONCURRENT: plain 4-wave blocks — an 8-wave block takes the whole LDS of its CU, so two such launches of
@@ -913,10 +917,10 @@ static bool make_patch_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t 
       const int per = (units + c - 1) / c;
       if (c > 1 && per * T < 4) break;
       if (pt->kg == 2 && units % c) continue;  // the 8-wave kernel wants every split full
-      const long long rounds = (base1 * c + slots - 1) / slots;
+      const long long rounds = (base1n * c + slots - 1) / slots;
       const long long cost = rounds * (per * T + 4) + (c > 1 ? 1 : 0);
       if (best < 0 || cost < best) { best = cost; ks = c; }
-      if (throughput_plan(flags) && base1 * c * pt->kg >= 64) { ks = c; break; }  // see make_plan
+      if (throughput_plan(flags) && base1n * c * pt->kg >= 64) { ks = c; break; }  // see make_plan
     }
   }
   const int per = (units + ks - 1) / ks;
@@ -964,7 +968,7 @@ static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t
     if (pt->lds < 4 * PT_EP_WAVE + 2048) { pt->lds = 4 * PT_EP_WAVE + 2048; pt->lds_g = (pt->lds + 15) & ~15; }
   }
   const long long base1 = (long long)pl->mtiles * (pt->wide ? pl->ntiles / 2 : pl->ntiles) * g->groups;
-  const long long base = base1 * plan_lanes(flags);
+  const long long base1n = throughput_plan(flags) ? (long long)pl->mtiles * pl->ntiles * g->groups : base1;  // as make_patch_plan
   pt->taps = 332;
   pt->kg = 1;
   int ks = 1;
@@ -973,10 +977,10 @@ static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t
     long long best = -1;
     for (int c = 1; c <= ncb && c <= 32; ++c) {
       const int per = (ncb + c - 1) / c;
-      const long long rounds = (base1 * c + slots - 1) / slots;
+      const long long rounds = (base1n * c + slots - 1) / slots;
       const long long cost = rounds * (per * 9 + 4) + (c > 1 ? 1 : 0);
       if (best < 0 || cost < best) { best = cost; ks = c; }
-      if (throughput_plan(flags) && base1 * c >= 64) { ks = c; break; }  // see make_plan
+      if (throughput_plan(flags) && base1n * c >= 64) { ks = c; break; }  // see make_plan
     }
   }
   const int per = (ncb + ks - 1) / ks;
@@ -1157,31 +1161,38 @@ int btx_contract_fwd_lanes(int kind, const BtxGeom* g, const void* x, const floa
                            (flags & ~BTX_FLAG_LANES_MASK) | BTX_FLAG_LANES(lanes->n), ws, ws_bytes, stream, ep, lanes);
 }
 
-static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w,
-                             const float* mu_b, const float* rho_b, void* out, const BtxRng* rng, const BtxNoise* noise,
-                             int act_dtype, int prec, uint32_t flags, void* ws, size_t ws_bytes, void* stream,
-                             const BtxEpilogue* ep, const BtxLanes* ln) {
-  if (!g || !x || !mu_w || !rho_w || !out || !rng) return BTX_E_NULL;
-  const int lanes = ln ? ln->n : 1;
-  if ((mu_b == nullptr) != (rho_b == nullptr)) return BTX_E_NULL;
+// What contract_fwd_impl launches for a request: the kernel family, its tile plan and the workspace it needs.  The ONE copy of
+// the routing rules — the launch and btx_contract_plan_info both call it.  `unaligned`: some pointer of the launch is not
+// 16-byte aligned (granule paths refused); `noise` / `ep` as passed to the launch (nullable).  Lanes: BTX_FLAG_LANES(n) in flags.
+struct FwdSel {
+  Plan pl;
+  bool gen, dma, rowfuse, par_major, stem, pool, patch, gemm8, pw;
+  int dma_nw, par_mqp, g8_pairs, pw_ntb, pw_chunks, out_bf16;
+  StemPlan stp;
+  StemPoolPlan spp;
+  PatchPlan pt;
+  size_t need, wt_off, wt_one, wt_all;
+};
+static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint32_t flags, bool unaligned, const BtxNoise* noise,
+                      const BtxEpilogue* ep, FwdSel* s) {
   if (kind != BTX_KIND_REPARAM && kind != BTX_KIND_FLIPOUT) return BTX_E_UNSUPPORTED;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
-  Plan pl;
+  memset(s, 0, sizeof(*s));
+  const int lanes = (int)plan_lanes(flags);
+  Plan& pl = s->pl;
   int rc = make_plan(g, prec, flags, BM, &pl);
   if (rc) return rc;
 
   // fast (granule) paths need whole 16-byte granules everywhere; otherwise the element-wise gather path
   const int G = (prec == BTX_PREC_BF16) ? 8 : 4;
-  const uintptr_t al = (uintptr_t)x | (uintptr_t)mu_w | (uintptr_t)rho_w | (uintptr_t)out |
-                       (uintptr_t)(noise && noise->eps_w ? noise->eps_w : nullptr);
   // Explicit noise (parity mode) runs on the same kernels as generated noise: eps_w enters the sampling pre-pass, the
   // sign words are packed from sign_in / sign_out.  BTX_FLAG_GATHER forces the element-wise gather kernel (tests).
   const bool explicit_kloop = (flags & BTX_FLAG_GATHER) != 0;
-  const bool gen = (pl.Cg % G != 0) || (al & 15) || explicit_kloop;
+  const bool gen = s->gen = (pl.Cg % G != 0) || unaligned || explicit_kloop;
   // LDS-DMA pipeline when the activations already have the contraction dtype (no conversion on the way to LDS);
   // BTX_NO_DMA=1 forces the register-staged kernel (A/B measurements).
   static const bool no_dma = tune_env("BTX_NO_DMA") != nullptr;
-  const bool rowfuse = (flags & BTX_FLAG_ROWFUSE) != 0;
+  const bool rowfuse = s->rowfuse = (flags & BTX_FLAG_ROWFUSE) != 0;
   bool dma = !gen && !no_dma && dma_shape_ok(g, act_dtype, prec, pl);
   // Sample where the weights are used when nothing shares the sampled tile.  A pointwise layer (Linear, 1x1x1 at stride 1) with
   // at most 256 rows per MC sample reads every weight once per sample: the register-staged kernel — (mu, rho) straight into the
@@ -1205,7 +1216,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     // one K-stage = one kernel row: the K walk sees KW*C "channels" per tap and a single tap per row
     const int esz = (act_dtype == BTX_ACT_BF16) ? 2 : 4;
     const int bk = NG * G;
-    const bool ok = !(al & 15) && !explicit_kloop && !(noise && noise->sign_in) && !no_dma && (prec == BTX_PREC_BF16) == (act_dtype == BTX_ACT_BF16) &&
+    const bool ok = !unaligned && !explicit_kloop && !(noise && noise->sign_in) && !no_dma && (prec == BTX_PREC_BF16) == (act_dtype == BTX_ACT_BF16) &&
                     g->groups == 1 && g->dw == 1 && g->pw == 0 && !(flags & BTX_FLAG_TRANSPOSED) &&
                     ((g->KW * g->C) % bk == 0) && ((g->sw * g->C * esz) % 16 == 0) && ((g->W * g->C * esz) % 16 == 0) &&
                     (g->C % G == 0 || G % g->C == 0);
@@ -1223,9 +1234,10 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
   // whose gather rule leaves 1, 2, 2 or 4 of a 3x3 filter's 9 taps per output-pixel parity class: with the pixels enumerated class by
   // class every 256-pixel tile walks only its class's taps (2.25 of 9 on average) and needs no K split.  Single-sample launches of
   // the generic LDS-DMA kernel with at least 8 pixel tiles and more than one tap.  BTX_NO_PAR_MAJOR=1 (tuning builds): raster order.
+  // Not under the throughput plan: a lane launch takes raster order, and a BTX_FLAG_CONCURRENT launch must sum as its lanes do.
   bool par_major = false;
   int par_mqp = 0;
-  if (dma && !rowfuse && (flags & BTX_FLAG_TRANSPOSED) && lanes == 1 && g->groups == 1 && g->D == 1 && g->KD == 1 && g->sd == 1 &&
+  if (dma && !rowfuse && (flags & BTX_FLAG_TRANSPOSED) && !throughput_plan(flags) && g->groups == 1 && g->D == 1 && g->KD == 1 && g->sd == 1 &&
       g->sh == 2 && g->sw == 2 && g->KH * g->KW <= 31 && g->KH * g->KW > 1 && (pl.Ho % 2) == 0 && (pl.Wo % 2) == 0 &&
       pl.mtiles >= 8 && !tune_env("BTX_NO_PAR_MAJOR")) {
     const int tp = 64 * dma_nw;
@@ -1332,7 +1344,9 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     wt_all = patch_wt_bytes(pl, g, kind, prec, &wt_one, lanes);
     if (sampled_w && wt_all < 0xfff00000ULL) wt_off = need;  // tiles live in the caller's buffer
     if (wt_off + wt_all >= 0xfff00000ULL) {  // 32-bit offsets inside the descriptor: register-staged kernel instead
-      if (rowfuse || (flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_OUT_BF16))) return BTX_E_UNSUPPORTED;
+      // The tiles of a launch grow with its lanes: the lane count alone would move a sample onto another kernel (another
+      // summation order).  A launch with lanes is refused; its caller runs one single-sample launch per lane.
+      if (rowfuse || (flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_OUT_BF16)) || lanes > 1) return BTX_E_UNSUPPORTED;
       dma = patch = false;
       rc = make_plan(g, prec, flags, BM, &pl);
       if (rc) return rc;
@@ -1341,6 +1355,65 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
       need = wt_off + wt_all;
     }
   }
+  if ((long long)pl.nwg * lanes > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+  s->dma = dma; s->par_major = par_major; s->stem = stem; s->pool = want_pool; s->patch = patch; s->gemm8 = gemm8; s->pw = pw;
+  s->dma_nw = dma_nw; s->par_mqp = par_mqp; s->g8_pairs = g8_pairs; s->pw_ntb = pw_ntb; s->pw_chunks = pw_chunks;
+  s->out_bf16 = out_bf16; s->stp = stp; s->spp = spp; s->pt = pt;
+  s->need = need; s->wt_off = wt_off; s->wt_one = wt_one; s->wt_all = wt_all;
+  return 0;
+}
+
+int btx_contract_plan_info(int kind, const BtxGeom* g, int act_dtype, int prec, uint32_t flags, const BtxEpilogue* ep,
+                           BtxPlanInfo* out) {
+  if (!g || !out) return BTX_E_NULL;
+  memset(out, 0, sizeof(*out));
+  FwdSel s;
+  const int rc = select_fwd(kind, g, act_dtype, prec, flags, false, nullptr, ep, &s);
+  if (rc) return rc;
+  if (s.pool) out->family = BTX_FAMILY_STEM_POOL;
+  else if (s.stem) out->family = BTX_FAMILY_STEM;
+  else if (s.patch) out->family = s.pt.taps == 33 ? BTX_FAMILY_TAPS : s.pt.taps == 332 ? BTX_FAMILY_TAPS2 : BTX_FAMILY_PATCH;
+  else if (s.dma && s.gemm8) out->family = BTX_FAMILY_GEMM8;
+#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
+  else if (s.dma && s.pw) out->family = BTX_FAMILY_PW;
+#endif
+  else if (s.dma) out->family = BTX_FAMILY_DMA;
+  else out->family = s.gen ? BTX_FAMILY_GATHER : BTX_FAMILY_REGSTAGE;
+  out->ksplits = s.pl.ksplits;
+  out->kper = s.pl.kper;
+  out->kgroups = s.patch ? s.pt.kg : 1;
+  out->wide = s.patch ? s.pt.wide : 0;
+  out->tall = s.patch ? s.pt.tall : 0;
+  out->par_major = (s.par_major && s.dma && !s.patch && !s.gemm8 && !s.stem) ? 1 : 0;
+  out->pool_band = s.pool ? s.spp.PB : 0;
+  out->nwg = s.pl.nwg;
+  out->lanes = (int32_t)plan_lanes(flags);
+  out->ws_bytes = (uint64_t)s.need;
+  return 0;
+}
+
+static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w,
+                             const float* mu_b, const float* rho_b, void* out, const BtxRng* rng, const BtxNoise* noise,
+                             int act_dtype, int prec, uint32_t flags, void* ws, size_t ws_bytes, void* stream,
+                             const BtxEpilogue* ep, const BtxLanes* ln) {
+  if (!g || !x || !mu_w || !rho_w || !out || !rng) return BTX_E_NULL;
+  const int lanes = ln ? ln->n : 1;
+  if ((mu_b == nullptr) != (rho_b == nullptr)) return BTX_E_NULL;
+  const uintptr_t al = (uintptr_t)x | (uintptr_t)mu_w | (uintptr_t)rho_w | (uintptr_t)out |
+                       (uintptr_t)(noise && noise->eps_w ? noise->eps_w : nullptr);
+  FwdSel sel;
+  int rc = select_fwd(kind, g, act_dtype, prec, flags, (al & 15) != 0, noise, ep, &sel);
+  if (rc) return rc;
+  const Plan& pl = sel.pl;
+  const bool gen = sel.gen, dma = sel.dma, rowfuse = sel.rowfuse, par_major = sel.par_major, stem = sel.stem, patch = sel.patch;
+  const bool want_pool = sel.pool, gemm8 = sel.gemm8, pw = sel.pw;
+  const int dma_nw = sel.dma_nw, par_mqp = sel.par_mqp, g8_pairs = sel.g8_pairs, pw_ntb = sel.pw_ntb, pw_chunks = sel.pw_chunks;
+  const int out_bf16 = sel.out_bf16;
+  const StemPlan& stp = sel.stp;
+  const StemPoolPlan& spp = sel.spp;
+  const PatchPlan& pt = sel.pt;
+  const size_t need = sel.need, wt_off = sel.wt_off, wt_one = sel.wt_one, wt_all = sel.wt_all;
+  const void* sampled_w = (noise && noise->sampled_w) ? noise->sampled_w : nullptr;
   if (need && (!ws || ws_bytes < need)) return BTX_E_WORKSPACE;
   if (need && (((uintptr_t)ws) & 15)) return BTX_E_ALIGN;
   // the persistent tap-unrolled kernel keeps its image-group queues (BTX_QUEUE_BYTES, zeroed per launch) behind everything
@@ -1356,7 +1429,6 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
   if (lanes > 1) {
     p.lane_x = ln->x_stride; p.lane_out = ln->out_stride; p.lane_res = ln->res_stride;
     p.lane_partial = (long long)(plan_ws(pl, g, 1));
-    if ((long long)pl.nwg * lanes > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
   }
   if (noise) {
     p.eps_w = noise->eps_w; p.eps_b = noise->eps_b;

@@ -274,6 +274,37 @@ def sample_weights(items, seed, sample_idx, prec, device, sample_dev=None, lanes
     return outs
 
 
+_REFUSED_CACHE = {}
+
+
+def _lanes_refused(kind, op, nb, spatial, dtype, out_dtype, prec_c, extra_flags, lanes):
+    """True when btx_contract_fwd_lanes would refuse this launch (BTX_E_UNSUPPORTED) for its lane count alone"""
+    flags = (_lib.FLAG_TRANSPOSED if op.transposed else 0) | extra_flags | (lanes << _lib.FLAG_LANES_SHIFT)
+    if out_dtype is not None and out_dtype != dtype:
+        flags |= _lib.FLAG_OUT_BF16 if out_dtype == torch.bfloat16 else _lib.FLAG_OUT_F32
+    act = _lib.ACT_BF16 if dtype == torch.bfloat16 else _lib.ACT_F32
+    key = (id(op), nb, spatial, kind, act, prec_c, flags)
+    hit = _REFUSED_CACHE.get(key)
+    if hit is None or hit[1] is not op:
+        L = _lib.lib()
+        g = _lib.Geom()
+        g.NB, (g.D, g.H, g.W), g.C, g.N = nb, spatial, op.in_channels, op.out_channels
+        g.KD, g.KH, g.KW = op.kernel
+        g.sd, g.sh, g.sw = op.stride
+        g.pd, g.ph, g.pw = op.padding
+        g.dd, g.dh, g.dw = op.dilation
+        g.od, g.oh, g.ow = op.output_padding
+        g.groups = op.groups
+        info = _lib.PlanInfo()
+        rc = L.btx_contract_plan_info(kind, ctypes.byref(g), act, prec_c, flags, None, ctypes.byref(info))
+        if len(_REFUSED_CACHE) > 4096:
+            _REFUSED_CACHE.clear()
+        hit = _REFUSED_CACHE[key] = (rc == _lib.E_UNSUPPORTED and
+                                     L.btx_contract_plan_info(kind, ctypes.byref(g), act, prec_c, flags & ~_lib.FLAG_LANES_MASK,
+                                                              None, ctypes.byref(info)) == 0, op)
+    return hit[0]
+
+
 def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_id, prec=None, noise=None,
                  extra_flags=0, out_dtype=None, epilogue=None, sampled_w=None, sample_dev=None, lanes=1, lane_batch=None,
                  self_sampling_weights=None):
@@ -320,7 +351,10 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
         out_lane = nb * out_sp[0] * out_sp[1] * out_sp[2] * op.out_channels * esz_o
         x_lane = 0 if x_shared else (xp.numel() // lanes) * xp.element_size()
         pooled = epilogue is not None and epilogue.get("pool")
-        if ((x_lane | out_lane) & 15) and not pooled:
+        # ... and so does a layer whose launch the library refuses for its lane count (btx_contract_plan_info: the pre-sampled
+        # tiles of all lanes would outgrow the 32-bit descriptor offsets and move the samples onto another kernel)
+        if not pooled and (((x_lane | out_lane) & 15) or _lanes_refused(kind, op, nb, spatial, x.dtype, out_dtype, prec_c,
+                                                                         extra_flags, lanes)):
             outs = []
             if sampled_w is not None and self_sampling_weights is not None:
                 mu_p, rho_p = self_sampling_weights()  # the single-lane launches sample in registers, from these

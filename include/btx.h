@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define BTX_ABI_VERSION 8
+#define BTX_ABI_VERSION 9
 
 /* argument-error codes (negative) */
 #define BTX_E_NULL        (-1)   /* required pointer is NULL */
@@ -251,6 +251,40 @@ int btx_contract_fwd_lanes(int kind, const BtxGeom* g,
                            int act_dtype, int prec, uint32_t flags,
                            void* ws, size_t ws_bytes, void* stream,
                            const BtxEpilogue* epilogue /* nullable */, const BtxLanes* lanes);
+
+/* Plan introspection (ABI 9, host only: no GPU, no launch).  What btx_contract_fwd_ex (flags without BTX_FLAG_LANES) or
+ * btx_contract_fwd_lanes (flags | BTX_FLAG_LANES(n)) would launch for this request — computed by the same routine the launch
+ * runs, so it cannot drift from it.  Assumes every pointer of the launch 16-byte aligned, no explicit noise and no pre-sampled
+ * tiles (BtxNoise NULL) and a workspace of at least ws_bytes; `ep` only matters through its pool / residual members (nullable).
+ * Returns what the launch would return for an argument error or an unsupported request (BTX_E_UNSUPPORTED: the caller runs the
+ * request another way — a launch with lanes, one single-sample launch per lane), else 0 and fills *out.
+ * The f32 summation order of an output element is fixed by (family, ksplits, kper, kgroups, par_major); wide, tall and
+ * pool_band change which workgroup computes an element, not how. */
+#define BTX_FAMILY_GATHER    0  /* element-wise gather kernel (unaligned / channel-padded shapes, BTX_FLAG_GATHER) */
+#define BTX_FAMILY_REGSTAGE  1  /* register-staged kernel (samples in registers) */
+#define BTX_FAMILY_DMA       2  /* generic LDS-DMA kernel (btx_contract_dma.h) */
+#define BTX_FAMILY_GEMM8     3  /* 8-wave pointwise GEMM (btx_contract_gemm8.h) */
+#define BTX_FAMILY_PATCH     4  /* run-time-tap patch kernel (btx_contract_patch.h) */
+#define BTX_FAMILY_TAPS      5  /* tap-unrolled 3x3 stride-1 kernel (btx_contract_taps.h) */
+#define BTX_FAMILY_TAPS2     6  /* tap-unrolled 3x3 stride-2 kernel (btx_contract_taps2.h) */
+#define BTX_FAMILY_STEM      7  /* row-fused stem (btx_contract_stem.h) */
+#define BTX_FAMILY_STEM_POOL 8  /* row-fused stem + max-pool (btx_contract_stempool.h) */
+#define BTX_FAMILY_PW        9  /* pointwise Flipout-GEMM (tuning builds only) */
+typedef struct BtxPlanInfo {
+  int32_t  family;     /* BTX_FAMILY_* */
+  int32_t  ksplits;    /* K splits (> 1: partial sums in the workspace + one reduce launch) */
+  int32_t  kper;       /* K elements per split */
+  int32_t  kgroups;    /* K-groups inside one workgroup (tap-unrolled 8-wave form: 2), else 1 */
+  int32_t  wide;       /* tap-unrolled Reparameterization: 64-pixel x 128-channel wave tiles */
+  int32_t  tall;       /* tap-unrolled: tall-strip tiles */
+  int32_t  par_major;  /* LDS-DMA transposed stride-2: parity-major pixel order */
+  int32_t  pool_band;  /* stem + max-pool: pooled rows per band (PB), else 0 */
+  int32_t  nwg;        /* workgroups per lane */
+  int32_t  lanes;      /* MC sample lanes of the launch */
+  uint64_t ws_bytes;   /* workspace the launch needs */
+} BtxPlanInfo;
+int btx_contract_plan_info(int kind, const BtxGeom* g, int act_dtype, int prec, uint32_t flags,
+                           const BtxEpilogue* ep /* nullable */, BtxPlanInfo* out);
 
 /* Weight gradient of one variational contraction (training; what autograd derives for the F.conv*d / F.linear calls of
  * conv_flipout.py:376-417, conv_variational.py:379-380, linear_flipout.py:168-174):
