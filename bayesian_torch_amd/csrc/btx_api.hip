@@ -1268,7 +1268,8 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
   const bool want_pool = ep && ep->pool;
   if (want_pool) {
     Plan sp;
-    if (ep->pool != 1 || !stem || ep->residual || (noise && (noise->sign_in || noise->sign_out)) ||
+    // (the pool kernel's store side knows ReLU only: ReLU6 is refused here, the caller clamps a ReLU launch's output)
+    if (ep->pool != 1 || !stem || ep->residual || ep->relu == 2 || (noise && (noise->sign_in || noise->sign_out)) ||
         (flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_SWAP_SIGNS)) || make_plan(g, prec, flags, DBM, &sp) ||
         !make_stem_pool_plan(g, act_dtype, prec, sp, &spp, tune_env("BTX_STEM_SHORT_BANDS") ? 1 : lanes))
       return BTX_E_UNSUPPORTED;
@@ -1574,7 +1575,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     // its 32-byte pieces drain more slowly than the staged side's whole 128-byte lines — 6.1k against 4.9k cycles on a
     // 56x56 tile, 6.5k against 8.3k on a tall strip — and the launch time does not move either way (+1.7 % .. -0.3 %).
     p.ep_direct = (tune_env("BTX_DIRECT") && pt.taps == 33 && pt.kg == 1 && pl.ksplits == 1 && prec == BTX_PREC_BF16 &&
-                   act_dtype == BTX_ACT_BF16 && out_bf16 && (pl.Ng % 64) == 0 && (g->N % 32) == 0 && !(noise && noise->sign_out) &&
+                   act_dtype == BTX_ACT_BF16 && out_bf16 && p.ep_relu != 2 && (pl.Ng % 64) == 0 && (g->N % 32) == 0 && !(noise && noise->sign_out) &&
                    (long long)pl.M * g->N * 2 < 0x7ff00000LL) ? 1 : 0;
     rc = (prec == BTX_PREC_BF16) ? launch_contract_patch_bf16(kind, p, pl.nwg * lanes, st)
          : (prec == BTX_PREC_BF16X3) ? launch_contract_patch_x3(kind, p, pl.nwg * lanes, st)
@@ -1585,7 +1586,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     // MEASUREMENT ONLY (tuning builds, BTX_G8_DIRECT=1): the store side from the fragment registers (direct_epilogue,
     // btx_epilogue.h) where its contract holds — outputs of the activation dtype, hashed s_out, 32-bit byte offsets with an
     // out-of-range value to spare (per lane).  Bit-identical and 5-25 % slower than the staged side.
-    p.ep_direct = (tune_env("BTX_G8_DIRECT") && (out_bf16 != 0) == (prec == BTX_PREC_BF16) && (g->N % 32) == 0 &&
+    p.ep_direct = (tune_env("BTX_G8_DIRECT") && (out_bf16 != 0) == (prec == BTX_PREC_BF16) && (g->N % 32) == 0 && p.ep_relu != 2 &&
                    !(noise && noise->sign_out) && (long long)pl.M * g->N * (out_bf16 ? 2 : 4) < 0x7ff00000LL) ? 1 : 0;
     rc = (prec == BTX_PREC_BF16) ? launch_contract_gemm8_bf16(kind, p, pl.nwg * lanes, st)
          : (prec == BTX_PREC_BF16X3) ? launch_contract_gemm8_x3(kind, p, pl.nwg * lanes, st)

@@ -373,6 +373,10 @@ __device__ __forceinline__ void apply_epilogue4(float* v, const ContractParams& 
   if (p.ep_relu) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : 0.f;
+    if (p.ep_relu == 2) {  // ReLU6
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = v[r] < 6.f ? v[r] : 6.f;
+    }
   }
 }
 
@@ -856,6 +860,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
       v = __builtin_fmaf(v, scale ? scale[col] : 1.f, shift ? shift[col] : 0.f);
       if (res) v += (float)res[i + r];
       if (relu) v = v > 0.f ? v : 0.f;
+      if (relu == 2) v = v < 6.f ? v : 6.f;  // ReLU6
       a[r] = v;
     }
     if (nv == 4) {

@@ -201,7 +201,8 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
   const uint32_t io_step = 8u * (uint32_t)p.N * 2u, io_bytes = (uint32_t)p.M * (uint32_t)p.N * 2u;
   if constexpr (RES_PRE) {
     const bool all_vec = ((p.N & 7) == 0) && (((group * p.Ng) & 7) == 0) && (ntile * BN + BN <= p.Ng);
-    if (all_vec && !to_partial && p.ep_res != nullptr && p.out_bf16) {  // exactly the case fast<1, RES> of stage 2 handles
+    if (all_vec && !to_partial && p.ep_res != nullptr && p.out_bf16 && p.ep_relu != 2) {  // exactly the case fast<1, RES> of stage 2 handles
+      // (ReLU6 stores through the element loop, which reads the residual itself)
       if constexpr (BUFIO) {
         const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.ep_res, 0, io_bytes, 0x00020000);
         const uint32_t io_voff = io_off(lane);
@@ -362,8 +363,14 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
     const int nv = min(8, p.Ng - col0);
     const uint32_t cbase = (uint32_t)(group * p.Ng + col0);
     // the whole 64-channel tile exists and 8-channel runs are 16-byte aligned (wave-uniform): no per-lane tails
-    const bool all_vec = ((p.N & 7) == 0) && (((group * p.Ng) & 7) == 0) && (ntile * BN + BN <= p.Ng);
+    const bool all_vec = ((p.N & 7) == 0) && (((group * p.Ng) & 7) == 0) && (ntile * BN + BN <= p.Ng) && p.ep_relu != 2;
     const bool res = !to_partial && p.ep_res != nullptr, relu = !to_partial && p.ep_relu;
+    // ReLU6 (BtxEpilogue.relu == 2, min(max(y, 0), 6)) takes the element loop below (all_vec is false for it), whose modes are
+    // run-time values.  Four more instantiations of `fast` for it were tried: they moved the register allocation of the kernels'
+    // existing streams (DMA kernel 170 -> 166 VGPRs, the 4x4 patch kernel 708 -> 1088 bytes of scratch), and so did a separate
+    // `relu6` test in front of `fast` (+2 VGPRs), and so did keeping split-K partial writes (to_partial, no activation) of
+    // ReLU6 launches on `fast` (the 4x4 bf16x3 patch kernel's scratch): the stores of relu 0 / 1 would have changed with them.
+    const bool relu6 = relu && p.ep_relu == 2;
     // Straight-line form, one per output mode (uniform): the 8 residual loads of the lane go out first (a pixel that does
     // not exist reads the tile's first pixel instead: no branch in front of a load), then the 16 LDS reads, then the
     // arithmetic and the 8 predicated stores.  (A loop that handles one pixel per iteration waits for each residual load
@@ -474,7 +481,7 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
         else { if (relu) fast(std::integral_constant<int, 2>{}, F{}, T{}); else fast(std::integral_constant<int, 2>{}, F{}, F{}); }
       }
     } else {
-      // ragged channel tiles / unaligned runs: one loop with run-time modes, element by element (rare shapes)
+      // ragged channel tiles / unaligned runs, and ReLU6: one loop with run-time modes, element by element (rare shapes)
       auto wk = pm.walk(pwave * 64 + (lane >> 3));
 #pragma unroll 1
       for (int r8 = 0; r8 < 8; ++r8) {
@@ -491,6 +498,7 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
             if (to_partial) { p.partial[(size_t)split * p.M * p.N + idx + j] = y; continue; }
             if (res) y += p.out_bf16 ? (float)((const __bf16*)p.ep_res)[idx + j] : ((const float*)p.ep_res)[idx + j];
             if (relu) y = fmaxf(y, 0.f);
+            if (relu6) y = fminf(y, 6.f);
             if (p.out_bf16) ((__bf16*)p.out)[idx + j] = (__bf16)y;
             else ((float*)p.out)[idx + j] = y;
           }
@@ -561,7 +569,9 @@ __device__ __forceinline__ void direct_epilogue(const ContractParams& p, const R
   }
   uint32_t SB = 0x80000000u;
   asm volatile("" : "+s"(SB));
-  const float lowb = p.ep_relu ? 0.f : -__builtin_inff();  // ReLU as a lower bound: one instruction stream for both
+  // ReLU as a lower bound: one instruction stream for both.  (ReLU6, BtxEpilogue.relu == 2, never gets here: the host sets
+  // ContractParams.ep_direct only for relu 0 / 1, and the staged store side applies the upper bound.)
+  const float lowb = p.ep_relu ? 0.f : -__builtin_inff();
   if constexpr (!FILLED) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the constants are in LDS
   // Phase A — (mean + bias) + s_out * (delta + bias delta) -> o (scalars, not the MFMA tuples: written back in place, the
   // partially updated 16-register tuples made the allocator copy and spill).  ONE instantiation: without a bias the

@@ -305,6 +305,30 @@ def _lanes_refused(kind, op, nb, spatial, dtype, out_dtype, prec_c, extra_flags,
     return hit[0]
 
 
+def act_code(act):
+    """BtxEpilogue.relu of an activation request: None / False -> 0, True / "relu" -> 1, "relu6" -> 2"""
+    if isinstance(act, str):
+        codes = {"none": 0, "relu": 1, "relu6": 2}
+        if act not in codes:
+            raise ValueError("epilogue activation must be one of %s, got %r" % (sorted(codes), act))
+        return codes[act]
+    if act is None or isinstance(act, bool):
+        return int(bool(act))
+    if act in (0, 1, 2):
+        return int(act)
+    raise ValueError("epilogue activation code must be 0, 1 or 2, got %r" % (act,))
+
+
+def apply_act_aten(out, act):
+    """the epilogue activation as ATen ops (CPU, autograd): act_code 1 -> relu, 2 -> clamp to [0, 6]"""
+    code = act_code(act)
+    if code == 1:
+        return torch.relu(out)
+    if code == 2:
+        return torch.clamp(out, 0.0, 6.0)
+    return out
+
+
 def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_id, prec=None, noise=None,
                  extra_flags=0, out_dtype=None, epilogue=None, sampled_w=None, sample_dev=None, lanes=1, lane_batch=None,
                  self_sampling_weights=None):
@@ -457,7 +481,7 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
                 raise ValueError("epilogue residual must match the output shape and dtype")
             keep.append(rp)
             ep.residual = rp.data_ptr()
-        ep.relu = 1 if epilogue.get("relu") else 0
+        ep.relu = act_code(epilogue.get("relu"))
         ep.pool = 1 if epilogue.get("pool") else 0
     args = (kind, ctypes.byref(g), xp.data_ptr(), mu_p.data_ptr(), rho_p.data_ptr(),
             mu_b.data_ptr() if mu_b is not None else None, rho_b.data_ptr() if rho_b is not None else None,
@@ -473,6 +497,13 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
         rc = L.btx_contract_fwd_lanes(*args, ctypes.byref(ln))
     else:
         rc = L.btx_contract_fwd_ex(*args)
+    if rc == _lib.E_UNSUPPORTED and ep is not None and ep.relu == 2:
+        # a store side without ReLU6 (the stem + max-pool kernel): the same launch with ReLU, then the upper bound.
+        # min(., 6) commutes with the rounding and with a max-pool, so the result is what ReLU6 in the store gives.
+        ep.relu = 1
+        rc = L.btx_contract_fwd_lanes(*args, ctypes.byref(ln)) if lanes > 1 else L.btx_contract_fwd_ex(*args)
+        _lib.check(rc)
+        out.clamp_(max=6.0)
     _lib.check(rc)
     if ev0 is not None:
         ev1 = torch.cuda.Event(enable_timing=True)

@@ -392,11 +392,14 @@ class _VariationalNd(BaseVariationalLayer_):
         return BF.contract_pool_ok(plan["op"], x.shape[0], (1, plan["Hp"], plan["Wp"]), torch.bfloat16, "bf16",
                                    _lib.FLAG_ROWFUSE)
 
-    def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False, pool=False):
+    def forward_fused(self, x, scale=None, shift=None, residual=None, relu=False, pool=False, act=None):
         """`relu?(forward(x) * scale[c] + shift[c] (+ residual))` with the affine / residual / ReLU
         folded into the store of the HIP contraction (eval-mode BatchNorm folds into scale/shift).  Returns `out` only.
+        The activation: relu=False / True (none / ReLU), or relu="relu6" / act="relu6" for ReLU6 (clamp to [0, 6]);
+        `act` ("none", "relu", "relu6"), when given, takes precedence over `relu`.
         With autograd (any of x / the parameters requires grad) the contraction runs through ContractFn and the affine,
         residual and ReLU as ATen ops, so gradients flow; CPU tensors evaluate the whole expression with ATen ops."""
+        relu = BF.act_code(act if act is not None else relu)
         if self._use_hip(x) and not self._needs_grad(x):
             return self._forward_hip(x, epilogue=dict(scale=scale, shift=shift, residual=residual, relu=relu, pool=pool))
         if pool:
@@ -411,7 +414,7 @@ class _VariationalNd(BaseVariationalLayer_):
             out = out + shift.view(shape).to(out.dtype)
         if residual is not None:
             out = out + residual
-        return torch.relu(out) if relu else out
+        return BF.apply_act_aten(out, relu)
 
     def _rowfuse_plan(self, x):
         if self._op.nd != 2 or self._op.in_channels > 4 or not x.is_cuda:

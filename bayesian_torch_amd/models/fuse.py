@@ -350,3 +350,375 @@ def hip_batchnorm(model, fuse_act=True):
             object.__setattr__(model, "_btx_fwd_eval", model.forward)
             model.forward = types.MethodType(_resnet_forward_train, model)
     return n
+
+
+# ---- fuse_model: the same store-side folding for any model, found on its traced dataflow ---------------------------------------
+# A "site" is a chain that starts at a variational layer V (anything with forward_fused) and whose every intermediate value has
+# exactly one user:  V -> BN [-> + other] [-> ReLU | ReLU6]  or  V -> ReLU | ReLU6.  The chain's ops are replaced by ONE call of
+# the site, which runs V.forward_fused (the BN as scale / shift, the add as residual, the activation in the store) in eval mode
+# and the original ops otherwise.  The module tree is not touched: the sites and the rewritten forward are plain objects.
+import operator as _operator  # noqa: E402
+
+import torch.nn.functional as _F  # noqa: E402
+
+_RELU_FUNCS = (torch.relu, torch.relu_, _F.relu, _F.relu_)
+_RELU6_FUNCS = (_F.relu6,)
+_ADD_FUNCS = (_operator.add, _operator.iadd, torch.add)
+
+
+class _SiteFold(_Folded):
+    """_Folded whose key also follows num_batches_tracked: a training-mode forward updates the running statistics in place
+    without bumping their version counters, the step counter it increments does"""
+
+    def _scale_shift(self):
+        bn = self.bn
+        ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked) if t is not None]
+        key = tuple((t.data_ptr(), t._version) for t in ts)
+        if key != self._key:
+            self._ss, self._key = fold_bn(bn), key
+        return self._ss
+
+
+class _Site:
+    """One fused chain.  `steps`: the chain's original ops behind V, replayed when the site cannot run fused — (kind, target,
+    args, kwargs) with _CUR standing for the chain's running value and _RES for the residual."""
+
+    def __init__(self, v, bn, steps, act, has_res):
+        self.v, self.bn, self.steps, self.act, self.has_res = v, bn, steps, act, has_res
+        self.folded = _SiteFold(v, bn) if bn is not None else None
+        # the modules the fused call would bypass: one with hooks runs the original ops, so its hooks fire
+        self.mods = [v] + [t for k, t, _, _ in steps if k == "call_module"]
+        self.__name__ = "btx_fused_site"  # (torch.fx code generation names the call after it)
+
+    def _fusable(self, x, residual):
+        v, bn = self.v, self.bn
+        if v.training or (bn is not None and bn.training):
+            return False  # training mode: batch statistics, running-stat updates, autograd — the original ops
+        if any(_hooked(m) for m in self.mods):
+            return False
+        op = getattr(v, "_op", None)
+        if op is None:
+            return False
+        if bn is not None:
+            if bn.num_features != op.out_channels or bn.running_mean is None:
+                return False
+            if op.nd == 0 and x.dim() != 2:
+                return False  # Linear -> BatchNorm1d normalises the channel axis only for [batch, features] outputs
+        if residual is not None:
+            if not torch.is_tensor(residual) or residual.dtype != x.dtype or residual.device != x.device:
+                return False
+            if op.nd == 0:
+                shape = tuple(x.shape[:-1]) + (op.out_channels,)
+            else:
+                if x.dim() != op.nd + 2:
+                    return False
+                sp = (1,) * (3 - op.nd) + tuple(x.shape[2:])
+                shape = (x.shape[0], op.out_channels) + op.out_spatial(sp)[3 - op.nd:]
+            if tuple(residual.shape) != shape:
+                return False
+        return True
+
+    def __call__(self, x, residual=None):
+        if self._fusable(x, residual):
+            scale, shift = self.folded._scale_shift() if self.folded is not None else (None, None)
+            return self.v.forward_fused(x, scale, shift, residual, act=self.act)
+        y = self.v(x)
+        for kind, target, args, kwargs in self.steps:
+            args = tuple(y if a is _CUR else residual if a is _RES else a for a in args)
+            if kind == "call_method":
+                y = getattr(args[0], target)(*args[1:], **kwargs)
+            else:
+                y = target(*args, **kwargs)
+        return y
+
+
+def _hooked(m):
+    return bool(m._forward_hooks or m._forward_pre_hooks)
+
+
+class _Marker:
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return self.name
+
+
+_CUR, _RES = _Marker("_CUR"), _Marker("_RES")
+
+
+def _act_of(node, modules):
+    """'relu' / 'relu6' when the fx node applies ReLU / ReLU6 to its first argument (and nothing else), else None"""
+    if node.op == "call_module":
+        m = modules.get(node.target)
+        if len(node.args) != 1 or node.kwargs:
+            return None
+        if type(m) is nn.ReLU:
+            return "relu"
+        if type(m) is nn.ReLU6 or (type(m) is nn.Hardtanh and m.min_val == 0.0 and m.max_val == 6.0):
+            return "relu6"
+        return None
+    if node.op == "call_function":
+        extra = set(node.kwargs) - {"inplace"}
+        if extra or len(node.args) > (2 if node.target in (_F.relu, _F.relu6) else 1):
+            return None
+        if node.target in _RELU_FUNCS:
+            return "relu"
+        if node.target in _RELU6_FUNCS:
+            return "relu6"
+        return None
+    if node.op == "call_method" and node.target in ("relu", "relu_") and len(node.args) == 1 and not node.kwargs:
+        return "relu"
+    return None
+
+
+def _is_add(node):
+    if node.op == "call_function" and node.target in _ADD_FUNCS:
+        return len(node.args) == 2 and not node.kwargs
+    return node.op == "call_method" and node.target in ("add", "add_") and len(node.args) == 2 and not node.kwargs
+
+
+def _only_user(node):
+    users = list(node.users)
+    return users[0] if len(users) == 1 else None
+
+
+def _bn_ok(m):
+    return type(m) in _BN_TYPES and m.track_running_stats
+
+
+def _match_site(node, modules):
+    """(site, chain nodes, residual node) for the chain that starts at the call of V `node`, or None"""
+    v = modules[node.target]
+    if len(node.args) != 1 or node.kwargs:
+        return None
+    chain, steps, bn, act, res = [node], [], None, None, None
+    cur = node
+    u = _only_user(cur)
+    if u is not None and u.op == "call_module" and _bn_ok(modules.get(u.target)) and u.args == (cur,) and not u.kwargs:
+        bn = modules[u.target]
+        chain.append(u); steps.append(("call_module", bn, (_CUR,), {}))
+        cur = u
+        u = _only_user(cur)
+        if u is None:
+            return None  # the normalised value has several users (or none): the chain is left alone
+        if u is not None and _is_add(u) and isinstance(u.args[0], torch.fx.Node) and isinstance(u.args[1], torch.fx.Node):
+            a0, a1 = u.args
+            inplace = u.target in (_operator.iadd, "add_")
+            other = a1 if a0 is cur else a0 if (a1 is cur and not inplace) else None  # in place: only the chain's value changes
+            if other is not None and other is not cur:
+                res = other
+                chain.append(u)
+                steps.append((u.op, u.target, tuple(_CUR if a is cur else _RES for a in u.args), {}))
+                cur = u
+                u = _only_user(cur)
+    if u is not None and u.args and u.args[0] is cur:
+        act = _act_of(u, modules)
+        if act is not None:
+            chain.append(u)
+            target = modules[u.target] if u.op == "call_module" else u.target
+            steps.append((u.op, target, (_CUR,) + tuple(u.args[1:]), dict(u.kwargs)))
+    if bn is None and act is None:
+        return None
+    return _Site(v, bn, steps, act or "none", res is not None), chain, res
+
+
+class _Tracer(torch.fx.Tracer):
+    """variational layers and torch.nn modules (not containers) are leaves: their calls stay single nodes"""
+
+    def is_leaf_module(self, m, qualname):
+        return _is_var(m) or super().is_leaf_module(m, qualname)
+
+
+def _inlined(module):
+    """the modules whose forward code the trace inlines: `module` and every non-leaf module reached without passing a leaf"""
+    tr, out, todo = _Tracer(), [], [module]
+    while todo:
+        m = todo.pop()
+        out.append(m)
+        todo.extend(c for c in m.children() if not tr.is_leaf_module(c, ""))
+    return out
+
+
+def _trace(module):
+    """the fx graph of `module`'s forward in EVAL mode: a traced forward reads `self.training` as a constant, so the flags of the
+    whole tree are False while tracing (and restored after); _FusedForward runs the class's forward whenever an inlined module
+    is in training mode"""
+    mods = list(module.modules())
+    flags = [m.training for m in mods]
+    try:
+        for m in mods:
+            m.training = False
+        return _Tracer().trace(module)
+    finally:
+        for m, t in zip(mods, flags):
+            m.training = t
+
+
+def _rewrite(module, graph):
+    """replace every site of the traced `graph` by one call; returns (compiled forward, sites)"""
+    modules = dict(module.named_modules())
+    sites, covered = [], set()
+    for node in list(graph.nodes):
+        if node.op != "call_module" or not _is_var(modules.get(node.target)) or node.graph is not graph:
+            continue
+        if node.target in covered or not node.users:
+            continue
+        m = _match_site(node, modules)
+        if m is None:
+            continue
+        site, chain, res = m
+        # the site runs where V ran, or right behind the residual when that is computed later: the ops between keep their
+        # order relative to V as far as the dataflow allows
+        anchor = node
+        if res is not None:
+            order = {n: i for i, n in enumerate(graph.nodes)}  # (earlier sites added nodes)
+            if order[res] > order[node]:
+                anchor = res
+        with graph.inserting_after(anchor):
+            new = graph.call_function(site, (node.args[0], res) if res is not None else (node.args[0],))
+        chain[-1].replace_all_uses_with(new)
+        for n in reversed(chain):
+            graph.erase_node(n)
+        sites.append(site)
+        covered.add(node.target)
+    graph.lint()
+    code = graph.python_code(root_module="self")
+    glb = dict(code.globals)
+    exec(compile(code.src, "<fuse_model %s>" % type(module).__name__, "exec"), glb)  # noqa: S102 — fx-generated source
+    return glb["forward"], sites
+
+
+def _seq_sites(seq):
+    """peephole over the consecutive children of one nn.Sequential: [(start index, length, site)]"""
+    kids = list(seq)
+    out, i = [], 0
+    while i < len(kids):
+        if not _is_var(kids[i]):
+            i += 1
+            continue
+        j, bn, act, steps = i + 1, None, None, []
+        if j < len(kids) and _bn_ok(kids[j]):
+            bn = kids[j]; steps.append(("call_module", bn, (_CUR,), {})); j += 1
+        if j < len(kids):
+            k = kids[j]
+            if type(k) is nn.ReLU:
+                act = "relu"
+            elif type(k) is nn.ReLU6 or (type(k) is nn.Hardtanh and k.min_val == 0.0 and k.max_val == 6.0):
+                act = "relu6"
+            if act is not None:
+                steps.append(("call_module", k, (_CUR,), {})); j += 1
+        if bn is None and act is None:
+            i += 1
+            continue
+        out.append((i, j - i, _Site(kids[i], bn, steps, act or "none", False)))
+        i = j
+    return out
+
+
+class _FusedForward:
+    """the rewritten forward, installed as the module's instance-level `forward`.  It pickles (and deep-copies) as the module
+    alone: the copy rebuilds its sites from its own modules on its first call — the same deterministic rewrite — so it is
+    fused, and no site of the copy points at the original's layers."""
+
+    def __init__(self, module, mode, fn=None, sites=None):
+        self.module, self.mode, self.fn, self.sites = module, mode, fn, sites
+        self.inlined = _inlined(module) if mode == "fx" else None
+
+    def _build(self):
+        if self.mode == "fx":
+            self.fn, self.sites = _rewrite(self.module, _trace(self.module))
+            self.inlined = _inlined(self.module)
+        else:
+            self.sites = _seq_sites(self.module)
+            self.fn = None
+
+    def __call__(self, *args, **kwargs):
+        if self.mode == "fx":
+            # the rewrite was traced in eval mode and inlines the forward code (and skips the hooks) of these modules: in
+            # training mode, or with hooks on one of them, the class's own forward runs — the model as it was before fusing
+            inl = self.inlined if self.inlined is not None else _inlined(self.module)
+            if any(m.training for m in inl) or any(_hooked(m) for m in inl[1:]):
+                return type(self.module).forward(self.module, *args, **kwargs)
+            if self.sites is None:
+                self._build()
+            return self.fn(self.module, *args, **kwargs)
+        if self.sites is None:
+            self._build()
+        (x,) = args
+        kids = list(self.module)
+        starts = {i: (n, s) for i, n, s in self.sites}
+        i = 0
+        while i < len(kids):
+            if i in starts:
+                n, s = starts[i]
+                x = s(x)
+                i += n
+            else:
+                x = kids[i](x)
+                i += 1
+        return x
+
+    def __getstate__(self):
+        return (self.module, self.mode)
+
+    def __setstate__(self, st):
+        self.module, self.mode = st
+        self.fn, self.sites, self.inlined = None, None, None
+
+
+def fuse_model(model):
+    """Fold eval-mode BatchNorm, residual adds and ReLU / ReLU6 into the store of the variational layers of ANY model converted
+    by dnn_to_bnn (its variational layers return a tensor), in place.  The model's forward is traced with torch.fx (variational
+    layers and torch.nn modules as leaves) and every chain
+
+        V -> BatchNorm{1,2,3}d [-> + other] [-> ReLU | ReLU6]      V -> ReLU | ReLU6
+
+    whose intermediate values have exactly one user becomes one V.forward_fused call (BtxEpilogue: scale / shift, residual, relu
+    1 / 2).  ReLU: nn.ReLU, F.relu, torch.relu, Tensor.relu (and the in-place forms); ReLU6: nn.ReLU6, F.relu6,
+    nn.Hardtanh(0, 6); the add: `+`, torch.add, operator.add / iadd without alpha.  A BatchNorm qualifies with
+    track_running_stats=True.  The forward is traced in eval mode; whenever a module whose code the trace inlined (the model, its
+    containers and blocks) is in training mode or has forward hooks, the model's class forward runs instead — so a fused model
+    trains exactly like the unfused one and can be evaluated afterwards without re-fusing.  At call time a site itself runs the
+    ORIGINAL ops whenever its BatchNorm or layer is in training mode, one of its modules has hooks, a Linear -> BatchNorm1d
+    output is not 2-D, or the residual does not have the output's shape and dtype.  A fused site runs V where V ran, or right
+    behind its residual when that is computed later (a ResNet `downsample`): on the CPU, whose noise comes from torch's
+    generator, such a model then draws its noise in another order than the unfused one (the GPU's noise is keyed per layer).  The folded (scale, shift) follow the BatchNorm tensors (load_state_dict, .to(),
+    in-place edits).  The module tree, state_dict keys and parameters are unchanged; nothing is copied, moved or sampled.
+    A model whose forward cannot be traced (control flow on tensor values), or whose inlined modules have forward hooks at
+    fusing time, gets the folding inside its nn.Sequential containers only (consecutive children V, BN, activation), with one
+    warning.  Returns the number of fused sites; a
+    second call returns 0."""
+    if model.__dict__.get("_btx_fuse_model"):
+        return 0
+    object.__setattr__(model, "_btx_fuse_model", True)
+    inl = set(map(id, _inlined(model)))
+    hooked = [k for k, m in model.named_modules() if k and id(m) in inl and _hooked(m)]
+    if hooked:  # (tracing would run the hooks on fx proxies, and the rewritten forward would skip them)
+        return _fuse_sequentials(model, "forward hooks on %s" % ", ".join(hooked))
+    try:
+        graph = _trace(model)
+    except Exception as e:  # noqa — torch.fx.proxy.TraceError and whatever a forward raises on Proxy inputs
+        return _fuse_sequentials(model, "it could not be traced (%s: %s)"
+                                 % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""))
+    fn, sites = _rewrite(model, graph)
+    if not sites:
+        return 0
+    model.forward = _FusedForward(model, "fx", fn, sites)
+    return len(sites)
+
+
+def _fuse_sequentials(model, why):
+    import warnings
+    n, covered = 0, set()
+    seqs = [m for m in model.modules() if type(m) is nn.Sequential and not isinstance(m.__dict__.get("forward"), _FusedForward)]
+    for seq in seqs:
+        sites = _seq_sites(seq)
+        if sites:
+            seq.forward = _FusedForward(seq, "seq", None, sites)
+            n += len(sites)
+            covered.update(id(s.v) for _, _, s in sites)
+    left = [k for k, m in model.named_modules() if _is_var(m) and id(m) not in covered]
+    warnings.warn("bayesian_torch_amd.models.fuse.fuse_model: %s: %s; only chains inside nn.Sequential containers were fused "
+                  "(%d); left unfused: %s" % (type(model).__name__, why, n, ", ".join(left) if left else "none"))
+    return n

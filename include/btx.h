@@ -203,7 +203,10 @@ int btx_contract_fwd(int kind, const BtxGeom* g,
 
 /* §8(f)-3, the step either side of the path: eval-mode BatchNorm (+ residual add, + ReLU) folded into the store of the
  * contraction (reference models/deterministic/resnet_large.py:49-60: out = relu(bn(conv(x)) [+ identity])).
- *   y = conv_out * scale[n] + shift[n]  (+ residual[same index as out])  ;  y = max(y, 0) if relu
+ *   y = conv_out * scale[n] + shift[n]  (+ residual[same index as out])  ;  then the activation `relu`:
+ *   relu = 0: none;  1: y = max(y, 0) (ReLU);  2: y = min(max(y, 0), 6) (ReLU6, MobileNetV2's ConvBNReLU).
+ * The activation acts on the f32 value, in front of the one rounding to the output dtype; both bounds of ReLU6 are exact in
+ * bf16, so relu = 2 gives exactly clamp(output of relu = 0, 0, 6).  relu = 2 with pool = 1 returns BTX_E_UNSUPPORTED.
  * scale/shift: f32 [N] (NULL => 1 / 0); residual: same layout and dtype as `out` (NULL => none).
  * pool = 1: the ResNet stem's nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet_large.py:118,145) is applied to y
  * inside the same launch and `out` is the POOLED tensor [NB][Hq][Wq][N] (btx_contract_pool_shape); the conv output never
@@ -213,7 +216,7 @@ typedef struct BtxEpilogue {
   const float* scale;
   const float* shift;
   const void*  residual;
-  int32_t      relu;
+  int32_t      relu;      /* 0 none, 1 ReLU, 2 ReLU6 */
   int32_t      pool;
 } BtxEpilogue;
 /* 1 (and the pooled extent) when btx_contract_fwd_ex would take epilogue.pool = 1 for this geometry, else 0 */
