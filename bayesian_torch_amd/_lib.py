@@ -68,6 +68,11 @@ class SampleItem(ctypes.Structure):
                 ("src_KW", ctypes.c_int32), ("src_C", ctypes.c_int32)]
 
 
+class LstmLayer(ctypes.Structure):
+    _fields_ = [("mu_w", ctypes.c_void_p), ("rho_w", ctypes.c_void_p), ("mu_b", ctypes.c_void_p), ("rho_b", ctypes.c_void_p),
+                ("layer_id", ctypes.c_uint32), ("sample_idx", ctypes.c_uint32), ("sample_idx_dev", ctypes.c_void_p)]
+
+
 class KlItem(ctypes.Structure):
     _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("prior_mu_t", ctypes.c_void_p),
                 ("prior_sigma_t", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("drho", ctypes.c_void_p),
@@ -79,7 +84,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_contract_plan_info", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
            "btx_mc_packed_floats", "btx_mc_accumulate", "btx_mc_accumulate_lanes", "btx_sampled_w_bytes", "btx_sample_weights", "btx_sampled_w_bytes_lanes", "btx_sample_weights_lanes", "btx_rowfuse_pack", "btx_maxpool2d_cl", "btx_avgpool_global_cl",
            "btx_bn_workspace_bytes", "btx_bn_train_fwd", "btx_bn_train_bwd", "btx_dgrad_weights",
-           "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd")
+           "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd",
+           "btx_lstm_workspace_bytes", "btx_lstm_fwd")
 
 
 def lib_path():
@@ -175,6 +181,11 @@ def lib():
     L.btx_bn_train_bwd.argtypes = [vp, vp, vp, i32, i64, i32, vp, i32, vp, vp, vp, vp, ctypes.POINTER(BnFuse), vp, sz, vp]
     L.btx_dgrad_weights.restype = i32
     L.btx_dgrad_weights.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(Rng), vp]
+    L.btx_lstm_workspace_bytes.restype = sz
+    L.btx_lstm_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.btx_lstm_fwd.restype = i32
+    L.btx_lstm_fwd.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, i32, vp, vp, vp, vp,
+                               vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

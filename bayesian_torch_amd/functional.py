@@ -749,6 +749,83 @@ def pad_channels(x, op, extra):
     return xp.permute((0, nd + 1) + tuple(range(1, nd + 1)))
 
 
+LSTM_PRECISIONS = ("f32", "bf16")  # btx_lstm_fwd's forms; bf16x3 LSTMs run the eager per-step loop
+
+
+def lstm_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, c0=None, kl_terms=None):
+    """The whole sequence of a Bayesian LSTM in one call (btx_lstm_fwd: 1 + T launches enqueued on the current stream).
+    x [rows, T, I] (f32 / bf16); ih / hh = (mu_w [4H, K], rho_w, mu_b [4H] or None, rho_b, layer_id, sample_idx, sample_dev):
+    step t of a layer draws the noise of sample index sample_idx + lane + t, or sample_dev[lane] + t when sample_dev (an
+    int32 tensor with one word per lane) is given.  lanes > 1: rows == batch (one input, shared by the lanes) or lanes * batch
+    (lane l's rows at l * B); h0 / c0 hold lanes * B rows.  kl_terms = (kl_ih, kl_hh): f32 scalars whose per-step sum
+    over the T steps is returned as the third value (else None).  Returns (hidden_seq, c_seq, kl), [lanes * B, T, H]."""
+    L = _lib.lib()
+    if not x.is_cuda:
+        raise _lib.BtxError("lstm_hip needs a CUDA (ROCm) tensor")
+    if x.dtype == torch.float32:
+        act = _lib.ACT_F32
+    elif x.dtype == torch.bfloat16:
+        act = _lib.ACT_BF16
+    else:
+        raise _lib.BtxError("activations must be float32 or bfloat16, got %s" % x.dtype)
+    prec = prec or _PRECISION
+    if prec not in LSTM_PRECISIONS:
+        raise _lib.BtxError("the fused LSTM sequence has no %s form" % prec)
+    lanes = int(lanes)
+    rows, T, I = x.shape
+    H = ih[0].shape[0] // 4
+    B, x_shared = rows, 0
+    if lanes > 1:
+        if batch is None:
+            raise _lib.BtxError("lanes > 1 needs batch (rows per lane)")
+        B = int(batch)
+        if rows == B:
+            x_shared = 1
+        elif rows != lanes * B:
+            raise _lib.BtxError("lanes=%d x batch=%d does not match the input rows %d" % (lanes, B, rows))
+    x = x.contiguous()
+    keep = [x]
+
+    def layer(p):
+        mu_w, rho_w, mu_b, rho_b, lid, s, sdev = p
+        for t in (mu_w, rho_w, mu_b, rho_b):
+            if t is not None:
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise _lib.BtxError("LSTM parameters must be contiguous float32")
+        if sdev is not None and (sdev.dtype != torch.int32 or sdev.numel() != lanes):
+            raise _lib.BtxError("sample_dev must be an int32 tensor with one word per lane")
+        return _lib.LstmLayer(mu_w.data_ptr(), rho_w.data_ptr(), mu_b.data_ptr() if mu_b is not None else None,
+                              rho_b.data_ptr() if rho_b is not None else None, int(lid) & 0xFFFFFFFF,
+                              int(s) & 0xFFFFFFFF, sdev.data_ptr() if sdev is not None else None)
+
+    li, lh = layer(ih), layer(hh)
+    if hh[0].shape[1] != H or ih[0].shape[1] != I:
+        raise _lib.BtxError("LSTM parameter shapes do not match the input (I=%d, H=%d)" % (I, H))
+    if h0 is not None:
+        if h0.shape != (lanes * B, H) or c0 is None or c0.shape != (lanes * B, H):
+            raise _lib.BtxError("h0 / c0 must be [lanes * B, H] = [%d, %d]" % (lanes * B, H))
+        h0, c0 = h0.to(x.dtype).contiguous(), c0.to(x.dtype).contiguous()
+        keep += [h0, c0]
+    hs = torch.empty(lanes * B, T, H, dtype=x.dtype, device=x.device)
+    cs = torch.empty_like(hs)
+    need = L.btx_lstm_workspace_bytes(lanes, B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    kl = None
+    ki = kh = None
+    if kl_terms is not None:
+        ki, kh = (k.detach().to(torch.float32).reshape(1).contiguous() for k in kl_terms)
+        keep += [ki, kh]
+        kl = torch.empty((), dtype=torch.float32, device=x.device)
+    _lib.check(L.btx_lstm_fwd(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                              ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(), x_shared,
+                              h0.data_ptr() if h0 is not None else None, c0.data_ptr() if c0 is not None else None,
+                              hs.data_ptr(), cs.data_ptr(), ki.data_ptr() if ki is not None else None,
+                              kh.data_ptr() if kh is not None else None, kl.data_ptr() if kl is not None else None,
+                              lanes, B, I, H, T, act, _lib.PREC_CODE[prec], ws.data_ptr(), need,
+                              torch.cuda.current_stream(x.device).cuda_stream))
+    return hs, cs, kl
+
+
 def fill_eps_hip(n, device, seed, sample_idx, layer_id, rng_stream, sample_dev=None):
     """BTX-RNG v1 eps for a flat index space of n elements, as a flat f32 CUDA tensor.  sample_dev: the sample index lives in
     that device word (captured steps) and sample_idx is ignored."""

@@ -241,8 +241,8 @@ class _VariationalNd(BaseVariationalLayer_):
         until the layer has seen an input: the stem layouts depend on the input shape).  Padded layouts (row-fused
         stems, channel padding) are sampled straight from the unpadded parameters (BtxSampleItem.src_KW / src_C)."""
         shape = getattr(self, "_btx_last_xshape", None)
-        if shape is None:
-            return None
+        if shape is None or self.__dict__.get("_btx_fused_seq"):
+            return None  # (the inner layers of a fused LSTM sample inside btx_lstm_fwd: a tile here would never be read)
         mu, rho = self._w()
         op0 = self._op
         mu_p, rho_p = BF.gemm_major_view(mu, op0), BF.gemm_major_view(rho, op0)
@@ -581,9 +581,77 @@ class _VariationalLSTM(BaseVariationalLayer_):
     def kl_loss(self):
         return self.ih.kl_loss() + self.hh.kl_loss()
 
+    # fused_sequence (opt-in; models.fuse_model sets it): inference forwards on the GPU run the whole sequence as one
+    # btx_lstm_fwd call — 1 + T launches, lanes and graph capture included — with the noise and recurrence of the eager loop
+    @property
+    def fused_sequence(self):
+        return bool(self.__dict__.get("_btx_fused_sequence", False))
+
+    @fused_sequence.setter
+    def fused_sequence(self, on):
+        on = bool(on)
+        self.__dict__["_btx_fused_sequence"] = on
+        for lin in (self.ih, self.hh):
+            lin.__dict__["_btx_fused_seq"] = on  # rng.presample(): no tiles for the inner layers
+
+    def _fused_ok(self, X, hidden_states):
+        """the conditions of the fused sequence path; otherwise the eager loop runs (and raises where it raises)"""
+        ih, hh = self.ih, self.hh
+        if not self.fused_sequence or not X.is_cuda or not ih._use_hip(X) or X.dim() != 3:
+            return False
+        if X.dtype not in (torch.float32, torch.bfloat16) or ih._needs_grad(X) or hh._needs_grad(None):
+            return False
+        if hidden_states is not None:
+            h0, c0 = hidden_states
+            if h0.dtype != X.dtype or c0.dtype != X.dtype or h0.dim() != 2 or c0.shape != h0.shape:
+                return False
+            if torch.is_grad_enabled() and (h0.requires_grad or c0.requires_grad):
+                return False
+        if ih._forward_hooks or ih._forward_pre_hooks or hh._forward_hooks or hh._forward_pre_hooks:
+            return False
+        prec = ih.precision or BF.get_precision()
+        if prec not in BF.LSTM_PRECISIONS or (hh.precision or BF.get_precision()) != prec:
+            return False
+        if ih._lanes() != hh._lanes():
+            return False
+        return True
+
+    def _forward_fused(self, X, hidden_states, return_kl):
+        ih, hh = self.ih, self.hh
+        nb, steps, _ = X.shape
+        lanes, lane_batch = ih._lanes()
+        B = nb
+        if lanes > 1:
+            B = lane_batch if nb == lane_batch else nb // lanes
+        h0 = c0 = None
+        if hidden_states is not None:
+            h0, c0 = hidden_states
+            if lanes > 1 and h0.shape[0] == B:  # one initial state, shared by the lanes
+                h0, c0 = h0.repeat(lanes, 1), c0.repeat(lanes, 1)
+
+        def params(lin):
+            mu, rho = lin._w()
+            s = lin._btx_sample
+            lin.__dict__["_btx_sample"] = s + steps * lanes  # the counter of `steps` eager forwards
+            return (mu.detach(), rho.detach(), lin.mu_bias.detach() if lin.mu_bias is not None else None,
+                    lin.rho_bias.detach() if lin.rho_bias is not None else None, lin._btx_layer_id, s,
+                    getattr(lin, "_btx_sample_dev", None))
+
+        kl_terms = (ih.kl_loss(), hh.kl_loss())
+        kind = _lib.KIND_FLIPOUT if self._family == "flipout" else _lib.KIND_REPARAM
+        hidden_seq, c_ts, kl = BF.lstm_hip(kind, X, params(ih), params(hh), _rng.seed(), prec=ih.precision or BF.get_precision(),
+                                           lanes=lanes, batch=B, h0=h0, c0=c0, kl_terms=kl_terms)
+        if self._family == "flipout":
+            self.kl = kl  # reference rnn_flipout.py:150
+        if return_kl:
+            return hidden_seq, (hidden_seq, c_ts), kl
+        return hidden_seq, (hidden_seq, c_ts)
+
     def forward(self, X, hidden_states=None, return_kl=True):
         if self.dnn_to_bnn_flag:
             return_kl = False
+        if self.fused_sequence and self._fused_ok(X, hidden_states):
+            return self._forward_fused(X, hidden_states, return_kl)
         nb, steps, _ = X.size()
         hs = self.out_features
         for lin in (self.ih, self.hh):

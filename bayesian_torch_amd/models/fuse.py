@@ -29,6 +29,12 @@ def _is_var(m):
     return hasattr(m, "forward_fused")
 
 
+def _is_lstm(m):
+    """a Bayesian LSTM: a leaf of the trace (its forward loops over the time steps), never an epilogue site; fuse_model switches
+    it to its fused sequence path (fused_sequence)"""
+    return hasattr(m, "fused_sequence") and hasattr(m, "ih") and hasattr(m, "hh")
+
+
 # ---- "is this module's forward the dataflow the fused forms assume?" — decided by RUNNING it, not by its class name -------------
 # Attribute names prove nothing about a forward (a pre-activation block has conv1 / bn1 / conv2 / bn2 / downsample too), and a
 # class-name list stops at the classes it knows.  A deep copy of the module on the CPU, in eval mode, is run twice on a small random
@@ -527,7 +533,7 @@ class _Tracer(torch.fx.Tracer):
     """variational layers and torch.nn modules (not containers) are leaves: their calls stay single nodes"""
 
     def is_leaf_module(self, m, qualname):
-        return _is_var(m) or super().is_leaf_module(m, qualname)
+        return _is_var(m) or _is_lstm(m) or super().is_leaf_module(m, qualname)
 
 
 def _inlined(module):
@@ -687,25 +693,29 @@ def fuse_model(model):
     in-place edits).  The module tree, state_dict keys and parameters are unchanged; nothing is copied, moved or sampled.
     A model whose forward cannot be traced (control flow on tensor values), or whose inlined modules have forward hooks at
     fusing time, gets the folding inside its nn.Sequential containers only (consecutive children V, BN, activation), with one
-    warning.  Returns the number of fused sites; a
-    second call returns 0."""
+    warning.  Every Bayesian LSTM (LSTMReparameterization / LSTMFlipout) is a leaf of the trace and gets fused_sequence = True:
+    its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd call.  Returns the number of fused sites plus
+    the number of LSTMs switched; a second call returns 0."""
     if model.__dict__.get("_btx_fuse_model"):
         return 0
     object.__setattr__(model, "_btx_fuse_model", True)
+    lstms = [m for m in model.modules() if _is_lstm(m) and not m.fused_sequence]
+    for m in lstms:
+        m.fused_sequence = True
     inl = set(map(id, _inlined(model)))
     hooked = [k for k, m in model.named_modules() if k and id(m) in inl and _hooked(m)]
     if hooked:  # (tracing would run the hooks on fx proxies, and the rewritten forward would skip them)
-        return _fuse_sequentials(model, "forward hooks on %s" % ", ".join(hooked))
+        return len(lstms) + _fuse_sequentials(model, "forward hooks on %s" % ", ".join(hooked))
     try:
         graph = _trace(model)
     except Exception as e:  # noqa — torch.fx.proxy.TraceError and whatever a forward raises on Proxy inputs
-        return _fuse_sequentials(model, "it could not be traced (%s: %s)"
-                                 % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""))
+        return len(lstms) + _fuse_sequentials(model, "it could not be traced (%s: %s)"
+                                              % (type(e).__name__, str(e).splitlines()[0] if str(e) else ""))
     fn, sites = _rewrite(model, graph)
     if not sites:
-        return 0
+        return len(lstms)
     model.forward = _FusedForward(model, "fx", fn, sites)
-    return len(sites)
+    return len(lstms) + len(sites)
 
 
 def _fuse_sequentials(model, why):

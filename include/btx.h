@@ -454,6 +454,36 @@ int btx_mc_accumulate(const void* logits, int bs, int C, int act_dtype, float kl
 int btx_mc_accumulate_lanes(const void* logits, int lanes, int bs, int C, int act_dtype, float kl,
                             float* packed, void* stream);
 
+/* Fused Bayesian LSTM inference (reference layers/variational_layers/rnn_variational.py:104-153, layers/flipout_layers/
+ * rnn_flipout.py:104-153): the whole sequence of an LSTMReparameterization / LSTMFlipout as 1 + T launches on `stream` —
+ * the input projection of every (lane, step) pair at once into the workspace, then one recurrent step launch per time step
+ * that samples its rows of W_hh in registers, contracts h_{t-1}, applies the gates and the cell and writes h_t / c_t into
+ * hidden_seq[:, t] / c_seq[:, t].  Step t of a layer draws the noise of a Linear forward of that layer with sample index
+ * s + t (s = sample_idx + lane, or the lane's word sample_idx_dev[lane]; the device word is read by the kernels, so a captured
+ * sequence replays any sample).  Layer parameters: mu_w / rho_w [4H][K] f32 (K = I for ih, H for hh), mu_b / rho_b [4H] or
+ * both NULL.
+ *   x          [rows][T][I] in act_dtype; rows = B (x_shared: every lane reads it) or lanes*B (lane l's rows at l*B)
+ *   h0, c0     [lanes*B][H] in act_dtype, or both NULL (zeros)
+ *   hidden_seq, c_seq [lanes*B][T][H] in act_dtype (c is carried in f32 between the steps)
+ *   kl_ih, kl_hh, kl_out: optional f32 scalars; kl_out = the per-step KL terms summed over T steps in the eager order
+ *   prec       BTX_PREC_F32 or BTX_PREC_BF16 (BTX_PREC_BF16X3: BTX_E_UNSUPPORTED)
+ * lanes in [1, 255].  Argument errors return before anything is launched. */
+typedef struct BtxLstmLayer {
+  const float* mu_w;
+  const float* rho_w;
+  const float* mu_b;
+  const float* rho_b;
+  uint32_t layer_id;
+  uint32_t sample_idx;           /* index of step 0 of lane 0 (host form) */
+  const void* sample_idx_dev;    /* uint32 per lane, or NULL */
+} BtxLstmLayer;
+
+size_t btx_lstm_workspace_bytes(int lanes, int B, int H, int T);
+int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
+                 const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
+                 float* kl_out, int lanes, int B, int I, int H, int T, int act_dtype, int prec, void* workspace,
+                 size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
