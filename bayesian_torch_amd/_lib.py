@@ -73,6 +73,10 @@ class LstmLayer(ctypes.Structure):
                 ("layer_id", ctypes.c_uint32), ("sample_idx", ctypes.c_uint32), ("sample_idx_dev", ctypes.c_void_p)]
 
 
+class LstmGrads(ctypes.Structure):
+    _fields_ = [("dmu_w", ctypes.c_void_p), ("drho_w", ctypes.c_void_p), ("dmu_b", ctypes.c_void_p), ("drho_b", ctypes.c_void_p)]
+
+
 class KlItem(ctypes.Structure):
     _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("prior_mu_t", ctypes.c_void_p),
                 ("prior_sigma_t", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("drho", ctypes.c_void_p),
@@ -85,7 +89,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_mc_packed_floats", "btx_mc_accumulate", "btx_mc_accumulate_lanes", "btx_sampled_w_bytes", "btx_sample_weights", "btx_sampled_w_bytes_lanes", "btx_sample_weights_lanes", "btx_rowfuse_pack", "btx_maxpool2d_cl", "btx_avgpool_global_cl",
            "btx_bn_workspace_bytes", "btx_bn_train_fwd", "btx_bn_train_bwd", "btx_dgrad_weights",
            "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd",
-           "btx_lstm_workspace_bytes", "btx_lstm_fwd")
+           "btx_lstm_workspace_bytes", "btx_lstm_fwd", "btx_lstm_train_saved_bytes", "btx_lstm_train_workspace_bytes",
+           "btx_lstm_fwd_train", "btx_lstm_bwd")
 
 
 def lib_path():
@@ -186,6 +191,17 @@ def lib():
     L.btx_lstm_fwd.restype = i32
     L.btx_lstm_fwd.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, i32, vp, vp, vp, vp,
                                vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
+    L.btx_lstm_train_saved_bytes.restype = sz
+    L.btx_lstm_train_saved_bytes.argtypes = [i32, i32, i32]
+    L.btx_lstm_train_workspace_bytes.restype = sz
+    L.btx_lstm_train_workspace_bytes.argtypes = [i32, i32, i32]
+    L.btx_lstm_fwd_train.restype = i32
+    L.btx_lstm_fwd_train.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, vp, vp, vp,
+                                     vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, vp, sz, vp]
+    L.btx_lstm_bwd.restype = i32
+    L.btx_lstm_bwd.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, vp, vp, vp, vp, vp,
+                               vp, vp, vp, vp, ctypes.POINTER(LstmGrads), ctypes.POINTER(LstmGrads), i32, i32, i32, i32, i32,
+                               i32, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

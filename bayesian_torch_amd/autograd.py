@@ -237,6 +237,48 @@ class KlFn(torch.autograd.Function):
         return (None,) + tuple(res)
 
 
+class LstmTrainFn(torch.autograd.Function):
+    """(hidden_seq, c_seq, kl) of a Bayesian LSTM on the HIP backend — btx_lstm_fwd_train, then btx_lstm_bwd for the backward
+    through time — with gradients w.r.t. x, h0, c0, the (mu, rho) tensors of ih and hh and the two per-step KL terms.
+    meta = (kind, seed, prec, (layer_id, sample_idx, sample_dev) of ih, the same of hh).  kl is the per-step sum of kl_ih + kl_hh
+    over the T steps (the eager loop's order), so its backward hands T * g to both terms (KlFn outputs)."""
+
+    @staticmethod
+    def forward(ctx, meta, x, h0, c0, mu_i, rho_i, mub_i, rhob_i, mu_h, rho_h, mub_h, rhob_h, kl_i, kl_h):
+        kind, seed, prec, mi, mh = meta
+        d = lambda t: t.detach() if t is not None else None  # noqa: E731
+        ih = (d(mu_i), d(rho_i), d(mub_i), d(rhob_i)) + tuple(mi)
+        hh = (d(mu_h), d(rho_h), d(mub_h), d(rhob_h)) + tuple(mh)
+        hs, cs, kl, saved = BF.lstm_train_fwd_hip(kind, x.detach(), ih, hh, seed, prec=prec, h0=d(h0), c0=d(c0),
+                                                  kl_terms=(kl_i, kl_h))
+        ctx.meta, ctx.saved_buf, ctx.steps = meta, saved, x.shape[1]
+        ctx.set_materialize_grads(False)
+        # save_for_backward: an in-place optimizer update of a parameter between forward and backward is caught by autograd
+        ctx.save_for_backward(x, h0, c0, mu_i, rho_i, mub_i, rhob_i, mu_h, rho_h, mub_h, rhob_h, hs)
+        return hs, cs, kl
+
+    @staticmethod
+    def backward(ctx, d_hs, d_cs, d_kl):
+        kind, seed, prec, mi, mh = ctx.meta
+        x, h0, c0, mu_i, rho_i, mub_i, rhob_i, mu_h, rho_h, mub_h, rhob_h, hs = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d = lambda t: t.detach() if t is not None else None  # noqa: E731
+        with torch.no_grad():
+            ih = (d(mu_i), d(rho_i), d(mub_i), d(rhob_i)) + tuple(mi)
+            hh = (d(mu_h), d(rho_h), d(mub_h), d(rhob_h)) + tuple(mh)
+            want_ih, want_hh = any(need[4:8]), any(need[8:12])
+            dx, dh0, dc0, gi, gh = BF.lstm_bwd_hip(kind, x.detach(), ih, hh, seed, hs.detach(), ctx.saved_buf, d_hs, d_cs,
+                                                   prec=prec, h0=d(h0), c0=d(c0), want_dx=need[1],
+                                                   want_dh0=need[2] and h0 is not None, want_dc0=need[3] and c0 is not None,
+                                                   want_ih=want_ih, want_hh=want_hh)
+            gi = gi if gi is not None else (None,) * 4
+            gh = gh if gh is not None else (None,) * 4
+            gk = d_kl * ctx.steps if d_kl is not None else None
+        mask = lambda i, g: g if need[i] else None  # noqa: E731
+        return ((None, dx, dh0, dc0) + tuple(mask(4 + i, g) for i, g in enumerate(gi)) +
+                tuple(mask(8 + i, g) for i, g in enumerate(gh)) + (mask(12, gk), mask(13, gk)))
+
+
 def _entries(meta, params):
     out = []
     for i, (pm, ps, pmt, pst, op) in enumerate(meta):

@@ -56,6 +56,8 @@ struct LstmKArgs {
   const float* kl_i;             // projection launch, block 0: kl_out = sum over T of (kl_i + kl_h), eager order
   const float* kl_h;
   float* kl_out;
+  float* sv_g;                   // training forward (STEP = 2): gate pre-activations [T][B][4H] f32
+  float* sv_c;                   //   and the f32 cell state [T][B][H]
 };
 
 template <typename T> __device__ __forceinline__ float ld_f(const T* p) { return (float)*p; }
@@ -68,7 +70,8 @@ __device__ __forceinline__ bool sign_neg(uint32_t idx, uint32_t ka, uint32_t kb)
 
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-// STEP = 0: input projection (grid.x = hblocks * lanes * T, grid.y = batch blocks); 1: recurrent step t (grid.z = lanes)
+// STEP = 0: input projection (grid.x = hblocks * lanes * T, grid.y = batch blocks); 1: recurrent step t (grid.z = lanes);
+// 2: the step of a training forward (one lane) — step 1 plus stores of the gate pre-activations and c_t for btx_lstm_bwd
 template <int FLIP, int BFP, typename XT, int STEP>
 __global__ __launch_bounds__(256) void lstm_kernel(LstmKArgs a) {
   __shared__ __attribute__((aligned(16))) float xs[LB * LXS];
@@ -243,6 +246,12 @@ __global__ __launch_bounds__(256) void lstm_kernel(LstmKArgs a) {
   const float i_t = sigm(g[0]), f_t = sigm(g[1]), g_t = tanhf(g[2]), o_t = sigm(g[3]);
   const float c = f_t * c_prev + i_t * g_t;
   const float h = o_t * tanhf(c);
+  if (STEP == 2) {
+    float* sg = a.sv_g + ((long long)t * B + gb) * N4 + j;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sg[q * H] = g[q];
+    a.sv_c[((long long)t * B + gb) * H + j] = c;
+  }
   a.cst[hrow * H + j] = c;
   st_f((XT*)a.hs + (hrow * a.T + t) * H + j, h);
   st_f((XT*)a.cs + (hrow * a.T + t) * H + j, c);
@@ -250,32 +259,23 @@ __global__ __launch_bounds__(256) void lstm_kernel(LstmKArgs a) {
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-template <int FLIP, int BFP, typename XT>
+template <int FLIP, int BFP, typename XT, int STEP = 1>
 hipError_t launch_all(LstmKArgs pa, LstmKArgs sa, int lanes, int bblocks, int T, hipStream_t st) {
   hipLaunchKernelGGL((lstm_kernel<FLIP, BFP, XT, 0>), dim3(pa.hblocks * lanes * T, bblocks, 1), dim3(256), 0, st, pa);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   for (int t = 0; t < T; ++t) {
     sa.t = t;
-    hipLaunchKernelGGL((lstm_kernel<FLIP, BFP, XT, 1>), dim3(sa.hblocks, bblocks, lanes), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL((lstm_kernel<FLIP, BFP, XT, STEP>), dim3(sa.hblocks, bblocks, lanes), dim3(256), 0, st, sa);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t btx_lstm_workspace_bytes(int lanes, int B, int H, int T) {
-  if (lanes <= 0 || B <= 0 || H <= 0 || T <= 0) return 0;
-  return align256((size_t)lanes * T * B * 4 * H * sizeof(float)) + align256((size_t)lanes * B * H * sizeof(float));
-}
-
-int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
-                 const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
-                 float* kl_out, int lanes, int B, int I, int H, int T, int act_dtype, int prec, void* workspace,
-                 size_t ws_bytes, void* stream) {
+int lstm_fwd_impl(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
+                  const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
+                  float* kl_out, int lanes, int B, int I, int H, int T, int act_dtype, int prec, void* workspace,
+                  size_t ws_bytes, void* saved, size_t saved_bytes, void* stream) {
   if (!ih || !hh || !x || !hidden_seq || !c_seq || !workspace) return BTX_E_NULL;
   if (!ih->mu_w || !ih->rho_w || !hh->mu_w || !hh->rho_w) return BTX_E_NULL;
   if ((ih->mu_b == nullptr) != (ih->rho_b == nullptr) || (hh->mu_b == nullptr) != (hh->rho_b == nullptr)) return BTX_E_NULL;
@@ -294,6 +294,7 @@ int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
   const uint64_t hblocks = ((uint64_t)H + LJ - 1) / LJ, bblocks = ((uint64_t)B + LB - 1) / LB;
   if (hblocks * lanes * T > 0x7fffffffull || bblocks > 65535) return BTX_E_UNSUPPORTED;
   if (ws_bytes < btx_lstm_workspace_bytes(lanes, B, H, T)) return BTX_E_WORKSPACE;
+  if (saved && saved_bytes < btx_lstm_train_saved_bytes(B, H, T)) return BTX_E_WORKSPACE;
 
   LstmKArgs pa = {};
   pa.x = x;
@@ -311,11 +312,25 @@ int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
   sa.K = H; sa.Kr = Hr;
   sa.h0 = h0; sa.c0 = c0; sa.hs = hidden_seq; sa.cs = c_seq;
   sa.cst = (float*)((char*)workspace + align256((size_t)lanes * T * B * 4 * H * sizeof(float)));
+  if (saved) {
+    sa.sv_g = (float*)saved;
+    sa.sv_c = (float*)((char*)saved + align256((size_t)T * B * 4 * H * sizeof(float)));
+  }
 
   hipStream_t st = (hipStream_t)stream;
   const int bb = (int)bblocks;
   hipError_t e;
   const bool bf = prec == BTX_PREC_BF16, xb = act_dtype == BTX_ACT_BF16;
+  if (saved) {  // training forward: one lane, the step form that keeps what btx_lstm_bwd needs
+    if (kind == BTX_KIND_FLIPOUT) {
+      if (bf) e = xb ? launch_all<1, 1, __bf16, 2>(pa, sa, 1, bb, T, st) : launch_all<1, 1, float, 2>(pa, sa, 1, bb, T, st);
+      else    e = xb ? launch_all<1, 0, __bf16, 2>(pa, sa, 1, bb, T, st) : launch_all<1, 0, float, 2>(pa, sa, 1, bb, T, st);
+    } else {
+      if (bf) e = xb ? launch_all<0, 1, __bf16, 2>(pa, sa, 1, bb, T, st) : launch_all<0, 1, float, 2>(pa, sa, 1, bb, T, st);
+      else    e = xb ? launch_all<0, 0, __bf16, 2>(pa, sa, 1, bb, T, st) : launch_all<0, 0, float, 2>(pa, sa, 1, bb, T, st);
+    }
+    return (int)e;
+  }
   if (kind == BTX_KIND_FLIPOUT) {
     if (bf) e = xb ? launch_all<1, 1, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<1, 1, float>(pa, sa, lanes, bb, T, st);
     else    e = xb ? launch_all<1, 0, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<1, 0, float>(pa, sa, lanes, bb, T, st);
@@ -324,6 +339,42 @@ int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
     else    e = xb ? launch_all<0, 0, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<0, 0, float>(pa, sa, lanes, bb, T, st);
   }
   return (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t btx_lstm_workspace_bytes(int lanes, int B, int H, int T) {
+  if (lanes <= 0 || B <= 0 || H <= 0 || T <= 0) return 0;
+  return align256((size_t)lanes * T * B * 4 * H * sizeof(float)) + align256((size_t)lanes * B * H * sizeof(float));
+}
+
+size_t btx_lstm_train_saved_bytes(int B, int H, int T) {
+  if (B <= 0 || H <= 0 || T <= 0) return 0;
+  return align256((size_t)T * B * 4 * H * sizeof(float)) + align256((size_t)T * B * H * sizeof(float));
+}
+
+size_t btx_lstm_train_workspace_bytes(int B, int H, int T) {
+  // the forward's projection G + f32 cell row; the backward's dgates [T][B][4H] + f32 dc carry: the same sizes
+  return btx_lstm_workspace_bytes(1, B, H, T);
+}
+
+int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
+                 const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
+                 float* kl_out, int lanes, int B, int I, int H, int T, int act_dtype, int prec, void* workspace,
+                 size_t ws_bytes, void* stream) {
+  return lstm_fwd_impl(kind, ih, hh, seed, x, x_shared, h0, c0, hidden_seq, c_seq, kl_ih, kl_hh, kl_out, lanes, B, I, H, T,
+                       act_dtype, prec, workspace, ws_bytes, nullptr, 0, stream);
+}
+
+int btx_lstm_fwd_train(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x,
+                       const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
+                       float* kl_out, int B, int I, int H, int T, int act_dtype, int prec, void* workspace, size_t ws_bytes,
+                       void* saved, size_t saved_bytes, void* stream) {
+  if (!saved) return BTX_E_NULL;
+  return lstm_fwd_impl(kind, ih, hh, seed, x, 0, h0, c0, hidden_seq, c_seq, kl_ih, kl_hh, kl_out, 1, B, I, H, T, act_dtype,
+                       prec, workspace, ws_bytes, saved, saved_bytes, stream);
 }
 
 }  // extern "C"

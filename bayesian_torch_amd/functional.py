@@ -752,6 +752,115 @@ def pad_channels(x, op, extra):
 LSTM_PRECISIONS = ("f32", "bf16")  # btx_lstm_fwd's forms; bf16x3 LSTMs run the eager per-step loop
 
 
+def _lstm_layer(p, lanes=1):
+    """BtxLstmLayer of (mu_w, rho_w, mu_b, rho_b, layer_id, sample_idx, sample_dev)"""
+    mu_w, rho_w, mu_b, rho_b, lid, s, sdev = p
+    for t in (mu_w, rho_w, mu_b, rho_b):
+        if t is not None:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise _lib.BtxError("LSTM parameters must be contiguous float32")
+    if sdev is not None and (sdev.dtype != torch.int32 or sdev.numel() != lanes):
+        raise _lib.BtxError("sample_dev must be an int32 tensor with one word per lane")
+    return _lib.LstmLayer(mu_w.data_ptr(), rho_w.data_ptr(), mu_b.data_ptr() if mu_b is not None else None,
+                          rho_b.data_ptr() if rho_b is not None else None, int(lid) & 0xFFFFFFFF,
+                          int(s) & 0xFFFFFFFF, sdev.data_ptr() if sdev is not None else None)
+
+
+def _lstm_act(x):
+    if x.dtype == torch.float32:
+        return _lib.ACT_F32
+    if x.dtype == torch.bfloat16:
+        return _lib.ACT_BF16
+    raise _lib.BtxError("activations must be float32 or bfloat16, got %s" % x.dtype)
+
+
+def _lstm_train_prec(prec):
+    prec = prec or _PRECISION
+    if prec not in LSTM_PRECISIONS:
+        raise _lib.BtxError("the fused LSTM sequence has no %s form" % prec)
+    return prec
+
+
+def lstm_train_fwd_hip(kind, x, ih, hh, seed, prec=None, h0=None, c0=None, kl_terms=None):
+    """The forward of a fused LSTM training step (btx_lstm_fwd_train, one lane): lstm_hip's (hidden_seq, c_seq, kl), bit for
+    bit, plus `saved` — the f32 gate pre-activations and cell states lstm_bwd_hip needs.  ih / hh as in lstm_hip (sample_dev:
+    one word); h0 / c0 [B, H] or None."""
+    L = _lib.lib()
+    if not x.is_cuda:
+        raise _lib.BtxError("lstm_train_fwd_hip needs a CUDA (ROCm) tensor")
+    act, prec = _lstm_act(x), _lstm_train_prec(prec)
+    B, T, I = x.shape
+    H = ih[0].shape[0] // 4
+    x = x.contiguous()
+    li, lh = _lstm_layer(ih), _lstm_layer(hh)
+    if hh[0].shape[1] != H or ih[0].shape[1] != I:
+        raise _lib.BtxError("LSTM parameter shapes do not match the input (I=%d, H=%d)" % (I, H))
+    if h0 is not None:
+        if h0.shape != (B, H) or c0 is None or c0.shape != (B, H):
+            raise _lib.BtxError("h0 / c0 must be [B, H] = [%d, %d]" % (B, H))
+        h0, c0 = h0.to(x.dtype).contiguous(), c0.to(x.dtype).contiguous()
+    hs = torch.empty(B, T, H, dtype=x.dtype, device=x.device)
+    cs = torch.empty_like(hs)
+    need = L.btx_lstm_train_workspace_bytes(B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    nsv = L.btx_lstm_train_saved_bytes(B, H, T)
+    saved = torch.empty(nsv, dtype=torch.uint8, device=x.device)
+    kl = ki = kh = None
+    if kl_terms is not None:
+        ki, kh = (k.detach().to(torch.float32).reshape(1).contiguous() for k in kl_terms)
+        kl = torch.empty((), dtype=torch.float32, device=x.device)
+    _lib.check(L.btx_lstm_fwd_train(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                                    ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(),
+                                    h0.data_ptr() if h0 is not None else None, c0.data_ptr() if c0 is not None else None,
+                                    hs.data_ptr(), cs.data_ptr(), ki.data_ptr() if ki is not None else None,
+                                    kh.data_ptr() if kh is not None else None, kl.data_ptr() if kl is not None else None,
+                                    B, I, H, T, act, _lib.PREC_CODE[prec], ws.data_ptr(), need, saved.data_ptr(), nsv,
+                                    torch.cuda.current_stream(x.device).cuda_stream))
+    return hs, cs, kl, saved
+
+
+def lstm_bwd_hip(kind, x, ih, hh, seed, hidden_seq, saved, d_hidden_seq=None, d_c_seq=None, prec=None, h0=None, c0=None,
+                 want_dx=True, want_dh0=False, want_dc0=False, want_ih=True, want_hh=True):
+    """The backward through time of one lstm_train_fwd_hip call with the same arguments (btx_lstm_bwd).  d_hidden_seq / d_c_seq
+    [B, T, H] or None.  Returns (dx, dh0, dc0, grads_ih, grads_hh); grads_* = (dmu_w, drho_w, dmu_b, drho_b) f32 (bias entries
+    None without bias), None where not wanted."""
+    L = _lib.lib()
+    act, prec = _lstm_act(x), _lstm_train_prec(prec)
+    B, T, I = x.shape
+    H = ih[0].shape[0] // 4
+    x = x.contiguous()
+    li, lh = _lstm_layer(ih), _lstm_layer(hh)
+    if h0 is not None:
+        h0, c0 = h0.to(x.dtype).contiguous(), c0.to(x.dtype).contiguous()
+    dev = x.device
+    d_hs = d_hidden_seq.to(x.dtype).contiguous() if d_hidden_seq is not None else None
+    d_cs = d_c_seq.to(x.dtype).contiguous() if d_c_seq is not None else None
+    dx = torch.empty(B, T, I, dtype=x.dtype, device=dev) if want_dx else None
+    dh0 = torch.empty(B, H, dtype=x.dtype, device=dev) if want_dh0 else None
+    dc0 = torch.empty(B, H, dtype=x.dtype, device=dev) if want_dc0 else None
+
+    def grads(p, want):
+        if not want:
+            return None, None
+        mu_w, mu_b = p[0], p[2]
+        g = (torch.empty_like(mu_w), torch.empty_like(mu_w), torch.empty_like(mu_b) if mu_b is not None else None,
+             torch.empty_like(mu_b) if mu_b is not None else None)
+        return g, _lib.LstmGrads(*(t.data_ptr() if t is not None else None for t in g))
+
+    gi, si = grads(ih, want_ih)
+    gh, sh = grads(hh, want_hh)
+    need = L.btx_lstm_train_workspace_bytes(B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(L.btx_lstm_bwd(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                              ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(), ptr(h0), ptr(c0),
+                              hidden_seq.data_ptr(), saved.data_ptr(), ptr(d_hs), ptr(d_cs), ptr(dx), ptr(dh0), ptr(dc0),
+                              ctypes.byref(si) if si is not None else None, ctypes.byref(sh) if sh is not None else None,
+                              B, I, H, T, act, _lib.PREC_CODE[prec], ws.data_ptr(), need,
+                              torch.cuda.current_stream(dev).cuda_stream))
+    return dx, dh0, dc0, gi, gh
+
+
 def lstm_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, c0=None, kl_terms=None):
     """The whole sequence of a Bayesian LSTM in one call (btx_lstm_fwd: 1 + T launches enqueued on the current stream).
     x [rows, T, I] (f32 / bf16); ih / hh = (mu_w [4H, K], rho_w, mu_b [4H] or None, rho_b, layer_id, sample_idx, sample_dev):
@@ -785,20 +894,7 @@ def lstm_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, c0=
             raise _lib.BtxError("lanes=%d x batch=%d does not match the input rows %d" % (lanes, B, rows))
     x = x.contiguous()
     keep = [x]
-
-    def layer(p):
-        mu_w, rho_w, mu_b, rho_b, lid, s, sdev = p
-        for t in (mu_w, rho_w, mu_b, rho_b):
-            if t is not None:
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise _lib.BtxError("LSTM parameters must be contiguous float32")
-        if sdev is not None and (sdev.dtype != torch.int32 or sdev.numel() != lanes):
-            raise _lib.BtxError("sample_dev must be an int32 tensor with one word per lane")
-        return _lib.LstmLayer(mu_w.data_ptr(), rho_w.data_ptr(), mu_b.data_ptr() if mu_b is not None else None,
-                              rho_b.data_ptr() if rho_b is not None else None, int(lid) & 0xFFFFFFFF,
-                              int(s) & 0xFFFFFFFF, sdev.data_ptr() if sdev is not None else None)
-
-    li, lh = layer(ih), layer(hh)
+    li, lh = _lstm_layer(ih, lanes), _lstm_layer(hh, lanes)
     if hh[0].shape[1] != H or ih[0].shape[1] != I:
         raise _lib.BtxError("LSTM parameter shapes do not match the input (I=%d, H=%d)" % (I, H))
     if h0 is not None:

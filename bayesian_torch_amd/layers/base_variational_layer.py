@@ -594,6 +594,69 @@ class _VariationalLSTM(BaseVariationalLayer_):
         for lin in (self.ih, self.hh):
             lin.__dict__["_btx_fused_seq"] = on  # rng.presample(): no tiles for the inner layers
 
+    # fused_training (opt-in; models.fuse_model(model, lstm_training=True) sets it, and it implies fused_sequence): forwards that
+    # need gradients run btx_lstm_fwd_train and their backward btx_lstm_bwd (autograd.LstmTrainFn) — eagerly and inside
+    # autograd.GraphedTrainStep.  Without it, training forwards take the eager loop.
+    @property
+    def fused_training(self):
+        return bool(self.__dict__.get("_btx_fused_training", False))
+
+    @fused_training.setter
+    def fused_training(self, on):
+        on = bool(on)
+        self.__dict__["_btx_fused_training"] = on
+        if on:
+            self.fused_sequence = True
+
+    def _fused_train_ok(self, X, hidden_states):
+        """the conditions of the fused training path: fused_training, a forward that needs gradients, and _fused_ok's other
+        conditions; otherwise the eager loop runs"""
+        ih, hh = self.ih, self.hh
+        if not self.fused_training or not X.is_cuda or not ih._use_hip(X) or X.dim() != 3:
+            return False
+        if X.dtype not in (torch.float32, torch.bfloat16):
+            return False
+        grad = ih._needs_grad(X) or hh._needs_grad(None)
+        if hidden_states is not None:
+            h0, c0 = hidden_states
+            if h0.dtype != X.dtype or c0.dtype != X.dtype or h0.dim() != 2 or c0.shape != h0.shape:
+                return False
+            grad = grad or (torch.is_grad_enabled() and (h0.requires_grad or c0.requires_grad))
+        if not grad:
+            return False
+        if ih._forward_hooks or ih._forward_pre_hooks or hh._forward_hooks or hh._forward_pre_hooks:
+            return False
+        prec = ih.precision or BF.get_precision()
+        if prec not in BF.LSTM_PRECISIONS or (hh.precision or BF.get_precision()) != prec:
+            return False
+        return True
+
+    def _forward_fused_train(self, X, hidden_states, return_kl):
+        ih, hh = self.ih, self.hh
+        if ih._lanes()[0] > 1 or hh._lanes()[0] > 1:
+            raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
+        steps = X.shape[1]
+        h0, c0 = hidden_states if hidden_states is not None else (None, None)
+
+        def meta(lin):
+            s = lin._btx_sample
+            lin.__dict__["_btx_sample"] = s + steps  # the counter of `steps` eager forwards
+            return lin._btx_layer_id, s, getattr(lin, "_btx_sample_dev", None)
+
+        kl_i, kl_h = ih.kl_loss(), hh.kl_loss()
+        kind = _lib.KIND_FLIPOUT if self._family == "flipout" else _lib.KIND_REPARAM
+        from .. import autograd as _ag
+        mu_i, rho_i = ih._w()
+        mu_h, rho_h = hh._w()
+        m = (kind, _rng.seed(), ih.precision or BF.get_precision(), meta(ih), meta(hh))
+        hidden_seq, c_ts, kl = _ag.LstmTrainFn.apply(m, X, h0, c0, mu_i, rho_i, ih.mu_bias, ih.rho_bias,
+                                                     mu_h, rho_h, hh.mu_bias, hh.rho_bias, kl_i, kl_h)
+        if self._family == "flipout":
+            self.kl = kl  # reference rnn_flipout.py:150
+        if return_kl:
+            return hidden_seq, (hidden_seq, c_ts), kl
+        return hidden_seq, (hidden_seq, c_ts)
+
     def _fused_ok(self, X, hidden_states):
         """the conditions of the fused sequence path; otherwise the eager loop runs (and raises where it raises)"""
         ih, hh = self.ih, self.hh
@@ -652,6 +715,8 @@ class _VariationalLSTM(BaseVariationalLayer_):
             return_kl = False
         if self.fused_sequence and self._fused_ok(X, hidden_states):
             return self._forward_fused(X, hidden_states, return_kl)
+        if self.fused_training and self._fused_train_ok(X, hidden_states):
+            return self._forward_fused_train(X, hidden_states, return_kl)
         nb, steps, _ = X.size()
         hs = self.out_features
         for lin in (self.ih, self.hh):

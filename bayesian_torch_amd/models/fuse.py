@@ -673,7 +673,14 @@ class _FusedForward:
         self.fn, self.sites, self.inlined = None, None, None
 
 
-def fuse_model(model):
+def _lstm_training(model, on):
+    if on:
+        for m in model.modules():
+            if _is_lstm(m):
+                m.fused_training = True
+
+
+def fuse_model(model, lstm_training=False):
     """Fold eval-mode BatchNorm, residual adds and ReLU / ReLU6 into the store of the variational layers of ANY model converted
     by dnn_to_bnn (its variational layers return a tensor), in place.  The model's forward is traced with torch.fx (variational
     layers and torch.nn modules as leaves) and every chain
@@ -695,13 +702,17 @@ def fuse_model(model):
     fusing time, gets the folding inside its nn.Sequential containers only (consecutive children V, BN, activation), with one
     warning.  Every Bayesian LSTM (LSTMReparameterization / LSTMFlipout) is a leaf of the trace and gets fused_sequence = True:
     its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd call.  Returns the number of fused sites plus
-    the number of LSTMs switched; a second call returns 0."""
+    the number of LSTMs switched; a second call returns 0.  lstm_training=True also sets fused_training on every Bayesian LSTM:
+    its training forwards on the GPU then run btx_lstm_fwd_train and their backward btx_lstm_bwd (also inside
+    autograd.GraphedTrainStep); it changes neither the count nor what the default call does."""
     if model.__dict__.get("_btx_fuse_model"):
+        _lstm_training(model, lstm_training)
         return 0
     object.__setattr__(model, "_btx_fuse_model", True)
     lstms = [m for m in model.modules() if _is_lstm(m) and not m.fused_sequence]
     for m in lstms:
         m.fused_sequence = True
+    _lstm_training(model, lstm_training)
     inl = set(map(id, _inlined(model)))
     hooked = [k for k, m in model.named_modules() if k and id(m) in inl and _hooked(m)]
     if hooked:  # (tracing would run the hooks on fx proxies, and the rewritten forward would skip them)

@@ -484,6 +484,45 @@ int btx_lstm_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
                  float* kl_out, int lanes, int B, int I, int H, int T, int act_dtype, int prec, void* workspace,
                  size_t ws_bytes, void* stream);
 
+/* Fused Bayesian LSTM training (one lane, lanes are an inference feature): the forward of btx_lstm_fwd that also keeps, in the
+ * caller's `saved` buffer, what the backward needs, and the backward through time.
+ *   saved      [T][B][4H] f32 gate pre-activations, then (256-byte aligned) [T][B][H] f32 cell states c_t;
+ *              btx_lstm_train_saved_bytes(B, H, T) bytes.  hidden_seq / c_seq / kl_out are bit for bit those of btx_lstm_fwd.
+ *   workspace  btx_lstm_train_workspace_bytes(B, H, T) bytes for the forward, and again for the backward (dgates [T][B][4H] f32
+ *              + the f32 dc carry [B][H]); the two need not be the same buffer.
+ * btx_lstm_bwd is the backward of one btx_lstm_fwd_train call with the SAME arguments (layers, seed, sample indices, x, h0 / c0,
+ * hidden_seq, saved).  Noise contract: that of btx_lstm_fwd — step t of a layer uses sample index s + t (s = sample_idx, or the
+ * word sample_idx_dev[0], read on the device), eps_w element n*Kr + k (Kr = K rounded up to 8 when K % 8 != 0), eps_b element
+ * n, s_in element b*Kr + k, s_out element b*4H + n; the backward regenerates every one of them in its kernels.  Launches:
+ * T step launches (t = T-1 .. 0: dgates_t = gate / cell backward of d hidden_seq[:, t] (+ d c_seq[:, t]) + dgates_{t+1} . W_hh(s+t+1),
+ * W_hh columns sampled in registers), one launch for dh0 / dc0 when either is wanted, one input-gradient launch for all steps
+ * (dx_t = dgates_t . W_ih(s+t)), and one weight-gradient launch per layer whose grads are given.  Every sum runs in a fixed order
+ * (no atomics): two calls give the same bits.
+ *   d_hidden_seq, d_c_seq  [B][T][H] in act_dtype, either nullable (zeros)
+ *   dx [B][T][I], dh0 / dc0 [B][H] in act_dtype, each nullable (not computed); dh0 / dc0 of a call without h0 / c0: the
+ *              gradients at the zero initial state
+ *   BtxLstmGrads (per layer, nullable): dmu_w / drho_w [4H][K] f32, dmu_b / drho_b [4H] f32 (NULL when the layer has no bias)
+ *              drho = (sum_t dW_t * eps_t) * sigmoid(rho) (Flipout: dDelta_t = (dg_t o s_out)^T (in_t o s_in) in that sum)
+ * bf16 precision: the operands the forward rounds (x, h, the sampled W / mu / Delta) are rounded to bf16, f32 accumulation.
+ * prec BTX_PREC_BF16X3: BTX_E_UNSUPPORTED.  Argument errors return before anything is launched. */
+typedef struct BtxLstmGrads {
+  float* dmu_w;
+  float* drho_w;
+  float* dmu_b;
+  float* drho_b;
+} BtxLstmGrads;
+
+size_t btx_lstm_train_saved_bytes(int B, int H, int T);
+size_t btx_lstm_train_workspace_bytes(int B, int H, int T);
+int btx_lstm_fwd_train(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x,
+                       const void* h0, const void* c0, void* hidden_seq, void* c_seq, const float* kl_ih, const float* kl_hh,
+                       float* kl_out, int B, int I, int H, int T, int act_dtype, int prec, void* workspace, size_t ws_bytes,
+                       void* saved, size_t saved_bytes, void* stream);
+int btx_lstm_bwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, const void* h0,
+                 const void* c0, const void* hidden_seq, const void* saved, const void* d_hidden_seq, const void* d_c_seq,
+                 void* dx, void* dh0, void* dc0, const BtxLstmGrads* g_ih, const BtxLstmGrads* g_hh, int B, int I, int H, int T,
+                 int act_dtype, int prec, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
