@@ -54,7 +54,7 @@ class PlanInfo(ctypes.Structure):
                                               "nwg", "lanes")] + [("ws_bytes", ctypes.c_uint64)]
 
 
-FAMILIES = ("gather", "regstage", "dma", "gemm8", "patch", "taps", "taps2", "stem", "stem_pool", "pw")  # BTX_FAMILY_* order
+FAMILIES = ("gather", "regstage", "dma", "gemm8", "patch", "taps", "taps2", "stem", "stem_pool")  # BTX_FAMILY_* order
 
 
 class Noise(ctypes.Structure):

@@ -10,17 +10,6 @@
 #include "btx_presample.h"
 namespace btx { constexpr int DBM = 512; }  // pixels per tile of the LDS-DMA variant (btx_contract_dma.h)
 
-// A/B knobs of the measurement builds (tools/build_variants.sh ... "-DBTX_TUNING", tools/kbench.py): the shipped library
-// reads no environment variable — every dispatch decision is a function of the call's arguments.
-static inline const char* tune_env(const char* name) {
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 using namespace btx;
 
 // ========================================================================================================
@@ -664,16 +653,11 @@ int btx_out_shape(const BtxGeom* g, uint32_t flags, int32_t* Do, int32_t* Ho, in
   return 0;
 }
 
-// Workgroup slots the split-K cost model fills with 4-wave blocks.  512 (two per CU) minimises the latency of a single
-// launch on an otherwise idle GPU (ResNet18 layer3: 63.5 vs 69.8 us); 256 splits K half as often, which wins as soon as
-// several MC samples are in flight (mc.GraphedMC lanes, the bench default: 1.16 -> 1.22 k MC-samples/s) because the
-// partial sums cost HBM traffic and a reduce launch while the other samples fill the idle CUs anyway.  BTX_SLOTS4
-// overrides.
-static long long slots4() {
-  static const char* e = tune_env("BTX_SLOTS4");
-  static const long long v = e ? atoll(e) : 256;
-  return v > 0 ? v : 256;
-}
+// Workgroup slots the split-K cost models fill, whatever the block size.  For 4-wave blocks, 512 (two per CU) minimises the
+// latency of a single launch on an otherwise idle GPU (ResNet18 layer3: 63.5 vs 69.8 us); 256 splits K half as often, which
+// wins as soon as several MC samples are in flight (mc.GraphedMC lanes, the bench default: 1.16 -> 1.22 k MC-samples/s)
+// because the partial sums cost HBM traffic and a reduce launch while the other samples fill the idle CUs anyway.
+constexpr long long SLOTS = 256;
 
 // tiling plan shared by btx_contract_workspace_bytes and btx_contract_fwd
 struct Plan {
@@ -710,7 +694,7 @@ static int make_plan(const BtxGeom* g, int prec, uint32_t flags, int bm, Plan* p
   // each split keeps >= 4 stages so the DMA ring fills.
   int ks = 1;
   {
-    const long long ncu = (bm == 256) ? slots4() : 256;  // 256-pixel tiles run two blocks per CU
+    const long long ncu = SLOTS;
     long long best = -1;
     const int max_ks = stages / 4 > 1 ? (stages / 4 < 32 ? stages / 4 : 32) : 1;
     for (int c = 1; c <= max_ks; ++c) {
@@ -724,9 +708,7 @@ static int make_plan(const BtxGeom* g, int prec, uint32_t flags, int bm, Plan* p
       // on how many samples share its launch, nor on how the samples were grouped over launches and ranks.
       // 16 workgroups of at most 16 stages are enough as well: ResNet18's fc (16 n-tiles of 16 stages per lane) in ONE piece —
       // 4 splits of 4 stages + the reduce launch measured 77 us per 20 lanes against 39 (profiles/r06_experiments.txt E18)
-      long long tp_min = 64, tp_short = 16;
-      if (const char* e = tune_env("BTX_TP_MINWG")) { tp_min = atoll(e); tp_short = 1 << 30; }  // A/B (E18)
-      if (throughput_plan(flags) && (base1 * c >= tp_min || (base1 * c >= tp_short && (stages + c - 1) / c <= 16))) { ks = c; break; }
+      if (throughput_plan(flags) && (base1 * c >= 64 || (base1 * c >= 16 && (stages + c - 1) / c <= 16))) { ks = c; break; }
     }
   }
   int per_stages = (stages + ks - 1) / ks;
@@ -754,7 +736,7 @@ static bool dma_shape_ok(const BtxGeom* g, int act_dtype, int prec, const Plan& 
 // Tile plan of the patch variant (btx_contract_patch.h): stride-1 2-D convolutions with more than one tap whose
 // activations already have the contraction dtype.  Returns false when the shape is not eligible.
 struct PatchPlan {
-  int G, R, Rp, Wp, PP, NI, rtiles, nw, mi, astage, lds;
+  int G, R, Rp, Wp, PP, NI, rtiles, nw, astage, lds;
   int taps, kg, lds_g;  // tap-unrolled kernel (btx_contract_taps.h): 10*KH+KW or 0; K-groups per workgroup; LDS per group
   int wide;             // tap-unrolled kernel, Reparameterization: 64-pixel x 128-channel wave tiles, ntiles / 2 grid n-tiles
   int tall, P, Wt, ncs;  // tall-strip tiles (ContractParams.pt_tall): virtual rows per image, strip width, strips per row tile
@@ -789,15 +771,9 @@ static double tall_tile(const BtxGeom* g, const Plan& pl, int tp, int ppcap, Pat
   }
   return best;
 }
-#ifndef BTX_GEMM8_MINK_DEFAULT
-#define BTX_GEMM8_MINK_DEFAULT 128
-#endif
-#ifndef BTX_WG_MB_DEFAULT
-#define BTX_WG_MB_DEFAULT 3.0
-#endif
-#ifndef BTX_TALL_MIN_DEFAULT
-#define BTX_TALL_MIN_DEFAULT 1.15
-#endif
+constexpr double TALL_MIN_GAIN = 1.15;  // the gain in pixel-slot efficiency from which tall strips are taken (make_patch_plan)
+constexpr int GEMM8_MIN_K = 128;        // the shortest K that goes to the 8-wave pointwise GEMM
+constexpr double WG_MAJOR_MIB = 3.0;    // the weight-tile size (MiB) from which the workgroup order turns weight-major
 // tile of `tp` output pixels whose patch holds at most `ppcap` pixels
 static bool patch_tile(const BtxGeom* g, const Plan& pl, int tp, int ppcap, PatchPlan* pt) {
   const int Ho = pl.Ho, Wo = pl.Wo;
@@ -844,52 +820,42 @@ static bool make_patch_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t 
   const int T = g->KH * g->KW;
   if (T < 2 || T > 64) return false;
   // 4-wave blocks, two per CU: 2 patch slots + 2 sign slots + 4 weight tiles within 80 KiB -> 22 pieces = 352 pixels;
-  // 8-wave blocks, one per CU: 60 pieces = 960 pixels.  BTX_PATCH_NW=8 forces the latter (A/B measurements).
-  static const char* nw_env = tune_env("BTX_PATCH_NW");
-  const bool force8 = nw_env && atoi(nw_env) == 8;
-  // BTX_PATCH_MI=4: 4 waves x 128 pixels, one block per CU, 256 accumulators per wave (A/B measurements)
-  static const char* mi_env = tune_env("BTX_PATCH_MI");
-  const bool want_mi4 = mi_env && atoi(mi_env) == 4;
-  pt->mi = 2;
+  // 8-wave blocks, one per CU: 60 pieces = 960 pixels
   pt->tall = 0; pt->P = 1; pt->Wt = 1; pt->ncs = 1;
-  if (want_mi4 && patch_tile(g, *pl, 512, 960, pt)) { pt->nw = 4; pt->mi = 4; }
-  else if (!force8 && patch_tile(g, *pl, 256, 352, pt)) pt->nw = 4;
+  if (patch_tile(g, *pl, 256, 352, pt)) pt->nw = 4;
   else if (patch_tile(g, *pl, 512, 960, pt)) pt->nw = 8;
   else return false;
   // 3x3 on 4-wave blocks (the tap-unrolled kernel): tall-strip tiles when they fill the pixel slots better
-  if (pt->nw == 4 && pt->mi == 2 && g->KH == 3 && g->KW == 3 && !tune_env("BTX_NO_TALL") && !tune_env("BTX_NO_TAPS")) {
+  if (pt->nw == 4 && g->KH == 3 && g->KW == 3) {
     const long long mt_old = (long long)((g->NB + pt->G - 1) / pt->G) * pt->rtiles;
     const double eff_old = (double)pl->M / ((double)mt_old * 256.0);
     PatchPlan tp = *pt;
     const double eff_tall = tall_tile(g, *pl, 256, 352, &tp);
-    // measured (tools/kbench.py --throughput-plan, batch 256 / 512 = the tiles of 4 / 8 MC sample lanes): the heavier
+    // measured (profiles/r03_tall_tiles_ab.txt, batch 256 / 512 = the tiles of 4 / 8 MC sample lanes): the heavier
     // tile (4 full waves, a store side 50 % longer) pays off only where it removes >= ~15 % of the workgroups (28x28:
     // 19 %, +3 / +8 %; 14x14: 16 %, -5 / +2 %); on 56x56 (9 % fewer workgroups) and 7x7 (6 %) it loses 4-7 %
-    const char* te = tune_env("BTX_TALL_MIN");  // A/B: the gain in pixel-slot efficiency from which tall strips are taken
-    const double tall_min = te ? atof(te) : BTX_TALL_MIN_DEFAULT;
-    if (eff_tall > eff_old * tall_min) *pt = tp;
+    if (eff_tall > eff_old * TALL_MIN_GAIN) *pt = tp;
   }
   const int pieces = (pt->PP + 15) / 16;
   pt->NI = (pieces + pt->nw - 1) / pt->nw;
-  if (pt->NI > (pt->mi == 4 ? 16 : PT_MAXNI)) return false;
+  if (pt->NI > PT_MAXNI) return false;
   pt->astage = pieces * 1024;
   int lds = 2 * pt->astage + 2 * (pt->astage / 16) + PT_WD * 8192 + 1024;  // + the scratch piece of btx_contract_taps.h
   const int ep = pt->nw * PT_EP_WAVE + 1024;
   if (lds < ep) lds = ep;
-  if (lds > ((pt->nw == 4 && pt->mi == 2) ? 81920 : 163840)) return false;
+  if (lds > (pt->nw == 4 ? 81920 : 163840)) return false;
   pt->lds = lds;
   pt->lds_g = (lds + 15) & ~15;
   // grid: m-tiles are (image group, row tile); split-K over the channel blocks
   const int bk = NG * (prec == BTX_PREC_BF16 ? 8 : 4);
   const int ncb = pl->Cg / bk;
   pl->mtiles = pt->tall ? pt->rtiles * pt->ncs : ((g->NB + pt->G - 1) / pt->G) * pt->rtiles;
-  const bool no_taps = tune_env("BTX_NO_TAPS") != nullptr;  // A/B: the run-time-tap patch kernel instead (read per call)
-  pt->taps = (!no_taps && pt->nw == 4 && pt->mi == 2 && pt->NI <= 6 && g->KH == 3 && g->KW == 3) ? 33 : 0;
+  pt->taps = (pt->nw == 4 && pt->NI <= 6 && g->KH == 3 && g->KW == 3) ? 33 : 0;
   // Reparameterization on the tap-unrolled kernel: one accumulator set per output, so the wave can hold a 64-pixel x 128-channel
   // tile (contract_taps_kernel<..., WIDE>) — taken when whole pairs of n-tiles exist and the halved grid still fills the
-  // workgroup slots (few-tile launches keep the narrow tile and its K-groups).  BTX_NO_WIDE=1 disables (A/B).
+  // workgroup slots (few-tile launches keep the narrow tile and its K-groups).
   if (kind == BTX_KIND_REPARAM && pt->taps == 33 && prec == BTX_PREC_BF16 && act_dtype == BTX_ACT_BF16 && (pl->Ng % 128) == 0 &&
-      (long long)pl->mtiles * (pl->ntiles / 2) * g->groups * plan_lanes(flags) >= slots4() && !tune_env("BTX_NO_WIDE"))
+      (long long)pl->mtiles * (pl->ntiles / 2) * g->groups * plan_lanes(flags) >= SLOTS)
     pt->wide = 1;
   if (pt->wide && pt->lds < pt->nw * PT_EP_WAVE + 2048) {  // its store side keeps the constants of two channel tiles
     pt->lds = pt->nw * PT_EP_WAVE + 2048;
@@ -902,16 +868,15 @@ static bool make_patch_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t 
   // order.)  The latency plan of a lone launch promises no such thing and prices the grid it launches.
   const long long base1n = throughput_plan(flags) ? (long long)pl->mtiles * pl->ntiles * g->groups : base1;
   // Few pixel tiles (at most one 4-wave block per CU): 8-wave blocks of two K-groups — split-K inside the workgroup
-  // through LDS instead of through HBM, and two waves per SIMD.  BTX_NO_KG=1 disables (A/B).
+  // through LDS instead of through HBM, and two waves per SIMD.
   // BTX_FLAG_CONCURRENT: plain 4-wave blocks — an 8-wave block takes the whole LDS of its CU, so two such launches of
   // different MC samples cannot share a CU; 4-wave blocks of two launches pair up and free-run against each other
   // (measured, ResNet18 bs 64, 3 / 4 / 6 samples in flight: 1340 / 1369 / 1346 -> 1382 / 1402 / 1378 MC-samples/s).
-  const bool no_kg = tune_env("BTX_NO_KG") != nullptr || throughput_plan(flags);
-  pt->kg = (pt->taps && !no_kg && base <= 256 && ncb >= 2 && (ncb % 2) == 0 && 2 * pt->lds_g <= 163840) ? 2 : 1;
+  pt->kg = (pt->taps && !throughput_plan(flags) && base <= 256 && ncb >= 2 && (ncb % 2) == 0 && 2 * pt->lds_g <= 163840) ? 2 : 1;
   const int units = ncb / pt->kg;  // channel blocks per K-group over the whole K
   int ks = 1;
   {
-    const long long slots = (pt->kg == 2) ? 256 : ((pt->nw == 4 && pt->mi == 2) ? slots4() : 256);
+    const long long slots = SLOTS;
     long long best = -1;
     for (int c = 1; c <= units && c <= 32; ++c) {
       const int per = (units + c - 1) / c;
@@ -938,7 +903,6 @@ static bool make_patch_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t 
 static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t flags, Plan* pl, PatchPlan* pt, int kind = -1) {
   if (flags & (BTX_FLAG_TRANSPOSED | BTX_FLAG_ROWFUSE)) return false;
   pt->wide = 0;
-  if (tune_env("BTX_NO_TAPS2")) return false;  // A/B: the per-tap LDS-DMA kernel instead
   if (make_plan(g, prec, flags, DBM, pl)) return false;
   if (!dma_shape_ok(g, act_dtype, prec, *pl)) return false;
   if (g->D != 1 || g->KD != 1 || pl->Do != 1) return false;
@@ -946,7 +910,7 @@ static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t
   BtxGeom gp = *g;  // the plane of a tile is the halo'd patch of a 2x2 stride-1 window: R+1 rows, Wo+1 columns
   gp.KH = 2; gp.KW = 2;
   if (!patch_tile(&gp, *pl, 256, 272, pt)) return false;
-  pt->nw = 4; pt->mi = 2;
+  pt->nw = 4;
   pt->tall = 0; pt->P = 1; pt->Wt = 1; pt->ncs = 1;
   const int pieces = (pt->PP + 15) / 16;
   pt->NI = (pieces + 3) / 4;
@@ -963,7 +927,7 @@ static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t
   pl->mtiles = ((g->NB + pt->G - 1) / pt->G) * pt->rtiles;
   // Reparameterization: 64-pixel x 128-channel wave tiles (contract_taps2_kernel<..., WIDE>) under the conditions of the stride-1 plan
   if (kind == BTX_KIND_REPARAM && prec == BTX_PREC_BF16 && act_dtype == BTX_ACT_BF16 && (pl->Ng % 128) == 0 &&
-      (long long)pl->mtiles * (pl->ntiles / 2) * g->groups * plan_lanes(flags) >= slots4() && !tune_env("BTX_NO_WIDE")) {
+      (long long)pl->mtiles * (pl->ntiles / 2) * g->groups * plan_lanes(flags) >= SLOTS) {
     pt->wide = 1;
     if (pt->lds < 4 * PT_EP_WAVE + 2048) { pt->lds = 4 * PT_EP_WAVE + 2048; pt->lds_g = (pt->lds + 15) & ~15; }
   }
@@ -973,7 +937,7 @@ static bool make_patch2_plan(const BtxGeom* g, int act_dtype, int prec, uint32_t
   pt->kg = 1;
   int ks = 1;
   {
-    const long long slots = slots4();
+    const long long slots = SLOTS;
     long long best = -1;
     for (int c = 1; c <= ncb && c <= 32; ++c) {
       const int per = (ncb + c - 1) / c;
@@ -1003,8 +967,7 @@ static bool make_stem_plan(const BtxGeom* g, int act_dtype, int prec, const Plan
   const int bk = NG * (prec == BTX_PREC_BF16 ? 8 : 4);
   if ((g->KW * g->C) % bk || pl.K % bk) return false;
   const long long rowB = (long long)g->W * g->C * esz;
-  static const char* snw_env = tune_env("BTX_STEM_NW");  // 8: skip the 4-wave plan (A/B measurements)
-  for (int nw = (snw_env && atoi(snw_env) == 8) ? 8 : 4; nw <= 8; nw += 4) {
+  for (int nw = 4; nw <= 8; nw += 4) {
     const int tp = 64 * nw;
     if (pl.Wo > tp) continue;
     int R = tp / pl.Wo;
@@ -1079,7 +1042,6 @@ static size_t patch_wt_bytes(const Plan& pl, const BtxGeom* g, int kind, int pre
   return arr * (size_t)(kind == BTX_KIND_FLIPOUT ? 1 + lanes : lanes);
 }
 static size_t pad256(size_t v) { return (v + 255) & ~(size_t)255; }
-constexpr size_t BTX_QUEUE_BYTES = 4096;  // image-group queues of the persistent kernel: one counter per tile position (<= 1024)
 
 static size_t plan_ws(const Plan& pl, const BtxGeom* g, int lanes = 1) {  // split-K partials [lane][split][M][N]
   return pl.ksplits > 1 ? (size_t)lanes * (size_t)pl.ksplits * (size_t)pl.M * (size_t)g->N * sizeof(float) : 0;
@@ -1124,7 +1086,6 @@ size_t btx_contract_workspace_bytes(const BtxGeom* g, int kind, int act_dtype, i
       if (ww > wc) wc = ww;
     }
     if (wc > wa) wa = wc;
-    if (pt.taps == 33) wa = pad256(wa) + BTX_QUEUE_BYTES;
   }
   return wa;
 }
@@ -1166,8 +1127,8 @@ int btx_contract_fwd_lanes(int kind, const BtxGeom* g, const void* x, const floa
 // 16-byte aligned (granule paths refused); `noise` / `ep` as passed to the launch (nullable).  Lanes: BTX_FLAG_LANES(n) in flags.
 struct FwdSel {
   Plan pl;
-  bool gen, dma, rowfuse, par_major, stem, pool, patch, gemm8, pw;
-  int dma_nw, par_mqp, g8_pairs, pw_ntb, pw_chunks, out_bf16;
+  bool gen, dma, rowfuse, par_major, stem, pool, patch, gemm8;
+  int par_mqp, g8_pairs, out_bf16;
   StemPlan stp;
   StemPoolPlan spp;
   PatchPlan pt;
@@ -1189,11 +1150,9 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
   // sign words are packed from sign_in / sign_out.  BTX_FLAG_GATHER forces the element-wise gather kernel (tests).
   const bool explicit_kloop = (flags & BTX_FLAG_GATHER) != 0;
   const bool gen = s->gen = (pl.Cg % G != 0) || unaligned || explicit_kloop;
-  // LDS-DMA pipeline when the activations already have the contraction dtype (no conversion on the way to LDS);
-  // BTX_NO_DMA=1 forces the register-staged kernel (A/B measurements).
-  static const bool no_dma = tune_env("BTX_NO_DMA") != nullptr;
+  // LDS-DMA pipeline when the activations already have the contraction dtype (no conversion on the way to LDS)
   const bool rowfuse = s->rowfuse = (flags & BTX_FLAG_ROWFUSE) != 0;
-  bool dma = !gen && !no_dma && dma_shape_ok(g, act_dtype, prec, pl);
+  bool dma = !gen && dma_shape_ok(g, act_dtype, prec, pl);
   // Sample where the weights are used when nothing shares the sampled tile.  A pointwise layer (Linear, 1x1x1 at stride 1) with
   // at most 256 rows per MC sample reads every weight once per sample: the register-staged kernel — (mu, rho) straight into the
   // wave's registers, softplus + Philox + Box-Muller there, the sampled tile never exists in HBM (north_star's kernel design) —
@@ -1209,38 +1168,36 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
     // BTX_FLAG_CONCURRENT single-sample launches are planned like lanes (a lane is bit-identical to them): same kernel as the lanes.
     if (dma && !rowfuse && pointwise_geom && lanes == 1 && !(flags & BTX_FLAG_CONCURRENT) && pl.M <= 256 && prec != BTX_PREC_BF16X3 &&
         !(noise && (noise->sampled_w || noise->eps_w || noise->sign_in || noise->sign_out)) &&
-        !(flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_OUT_BF16)) && !tune_env("BTX_NO_FUSED_LINEAR"))
+        !(flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_OUT_BF16)))
       dma = false;
   }
   if (rowfuse) {
     // one K-stage = one kernel row: the K walk sees KW*C "channels" per tap and a single tap per row
     const int esz = (act_dtype == BTX_ACT_BF16) ? 2 : 4;
     const int bk = NG * G;
-    const bool ok = !unaligned && !explicit_kloop && !(noise && noise->sign_in) && !no_dma && (prec == BTX_PREC_BF16) == (act_dtype == BTX_ACT_BF16) &&
+    const bool ok = !unaligned && !explicit_kloop && !(noise && noise->sign_in) && (prec == BTX_PREC_BF16) == (act_dtype == BTX_ACT_BF16) &&
                     g->groups == 1 && g->dw == 1 && g->pw == 0 && !(flags & BTX_FLAG_TRANSPOSED) &&
                     ((g->KW * g->C) % bk == 0) && ((g->sw * g->C * esz) % 16 == 0) && ((g->W * g->C * esz) % 16 == 0) &&
                     (g->C % G == 0 || G % g->C == 0);
     if (!ok) return BTX_E_UNSUPPORTED;
     dma = true;
   }
-  // LDS-DMA variant: 4-wave blocks on 256-pixel tiles (two per CU) unless BTX_DMA_NW=8 (A/B measurements)
-  static const char* dnw_env = tune_env("BTX_DMA_NW");
-  const int dma_nw = (dnw_env && atoi(dnw_env) == 8) ? 8 : 4;
+  // LDS-DMA variant: 4-wave blocks on 256-pixel tiles (two per CU)
   if (dma) {
-    rc = make_plan(g, prec, flags, 64 * dma_nw, &pl);
+    rc = make_plan(g, prec, flags, 256, &pl);
     if (rc) return rc;
   }
   // Parity-major pixel order (ContractParams.par_major) for the data gradient of a stride-2 2-D convolution — a transposed launch
   // whose gather rule leaves 1, 2, 2 or 4 of a 3x3 filter's 9 taps per output-pixel parity class: with the pixels enumerated class by
   // class every 256-pixel tile walks only its class's taps (2.25 of 9 on average) and needs no K split.  Single-sample launches of
-  // the generic LDS-DMA kernel with at least 8 pixel tiles and more than one tap.  BTX_NO_PAR_MAJOR=1 (tuning builds): raster order.
+  // the generic LDS-DMA kernel with at least 8 pixel tiles and more than one tap.
   // Not under the throughput plan: a lane launch takes raster order, and a BTX_FLAG_CONCURRENT launch must sum as its lanes do.
   bool par_major = false;
   int par_mqp = 0;
   if (dma && !rowfuse && (flags & BTX_FLAG_TRANSPOSED) && !throughput_plan(flags) && g->groups == 1 && g->D == 1 && g->KD == 1 && g->sd == 1 &&
       g->sh == 2 && g->sw == 2 && g->KH * g->KW <= 31 && g->KH * g->KW > 1 && (pl.Ho % 2) == 0 && (pl.Wo % 2) == 0 &&
-      pl.mtiles >= 8 && !tune_env("BTX_NO_PAR_MAJOR")) {
-    const int tp = 64 * dma_nw;
+      pl.mtiles >= 8) {
+    const int tp = 256;
     const long long mq = (long long)g->NB * (pl.Ho / 2) * (pl.Wo / 2);
     const long long tiles_per_class = (mq + tp - 1) / tp;  // the last tile of a class is padded: no tile holds two classes
     if (4 * tiles_per_class * pl.ntiles <= 0x7fffffffLL) {
@@ -1251,11 +1208,10 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
       pl.nwg = pl.mtiles * pl.ntiles * g->groups;
     }
   }
-  // stem variant: row-fused small-C convolutions with the input rows of the tile resident in LDS (BTX_NO_STEM=1 disables)
-  static const bool no_stem = tune_env("BTX_NO_STEM") != nullptr;
+  // stem variant: row-fused small-C convolutions with the input rows of the tile resident in LDS
   StemPlan stp;
   bool stem = false;
-  if (dma && rowfuse && !no_stem) {
+  if (dma && rowfuse) {
     Plan sp;
     if (!make_plan(g, prec, flags, DBM, &sp) && make_stem_plan(g, act_dtype, prec, sp, &stp)) {
       sp.ksplits = 1; sp.kper = sp.K; sp.nwg = stp.nwg;
@@ -1271,15 +1227,14 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
     // (the pool kernel's store side knows ReLU only: ReLU6 is refused here, the caller clamps a ReLU launch's output)
     if (ep->pool != 1 || !stem || ep->residual || ep->relu == 2 || (noise && (noise->sign_in || noise->sign_out)) ||
         (flags & (BTX_FLAG_OUT_F32 | BTX_FLAG_SWAP_SIGNS)) || make_plan(g, prec, flags, DBM, &sp) ||
-        !make_stem_pool_plan(g, act_dtype, prec, sp, &spp, tune_env("BTX_STEM_SHORT_BANDS") ? 1 : lanes))
+        !make_stem_pool_plan(g, act_dtype, prec, sp, &spp, lanes))
       return BTX_E_UNSUPPORTED;
     pl.nwg = spp.nwg;
   }
-  // patch variant: stride-1 2-D convolutions keep the halo'd input patch of the tile in LDS (BTX_NO_PATCH=1 disables)
-  static const bool no_patch = tune_env("BTX_NO_PATCH") != nullptr;
+  // patch variant: stride-1 2-D convolutions keep the halo'd input patch of the tile in LDS
   PatchPlan pt;
   bool patch = false;
-  if (dma && !rowfuse && !no_patch) {
+  if (dma && !rowfuse) {
     Plan pp;
     if (make_patch_plan(g, act_dtype, prec, flags, &pp, &pt, kind)) { pl = pp; patch = true; }
     else if (make_patch2_plan(g, act_dtype, prec, flags, &pp, &pt, kind)) { pl = pp; patch = true; }
@@ -1294,13 +1249,10 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
   bool gemm8 = false;
   int g8_pairs = 1;
   {
-    const char* mk = tune_env("BTX_GEMM8_MINK");
-    const int min_k = mk ? atoi(mk) : BTX_GEMM8_MINK_DEFAULT;
     const int bk8 = NG * (prec == BTX_PREC_BF16 ? 8 : 4);  // (dma: the activation dtype is the contraction's)
     if (dma && !rowfuse && !patch && kind == BTX_KIND_FLIPOUT &&
         !(flags & BTX_FLAG_TRANSPOSED) && g->KD == 1 && g->KH == 1 && g->KW == 1 &&
-        g->pd == 0 && g->ph == 0 && g->pw == 0 && (pl.K % bk8) == 0 && pl.K >= 4 * bk8 && pl.K >= min_k && (pl.Ng % 128) == 0 &&
-        !tune_env("BTX_NO_GEMM8")) {
+        g->pd == 0 && g->ph == 0 && g->pw == 0 && (pl.K % bk8) == 0 && pl.K >= 4 * bk8 && pl.K >= GEMM8_MIN_K && (pl.Ng % 128) == 0) {
       const long long mt = (pl.M + 255) / 256;
       g8_pairs = pl.Ng / 128;
       const long long nwg = mt * g->groups * g8_pairs;
@@ -1308,30 +1260,6 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
         gemm8 = true;
         pl.mtiles = (int)mt; pl.ksplits = 1; pl.kper = pl.K; pl.nwg = (int)nwg;
       }
-    }
-  }
-  // MEASUREMENT ONLY (tuning builds, BTX_PW=1): pointwise contractions (Linear, 1x1x1 / stride 1 / no padding) on the
-  // Flipout-GEMM of btx_contract_pw.h — one workgroup per pixel tile walks `pw_ntb` n-tiles, store side from the fragment
-  // registers.  Bit-identical to the LDS-DMA kernel; measured (profiles/r04_pointwise_ab.txt): +4..7 % where the activation
-  // stages stay resident (K = 64), 7..16 % SLOWER where they stream — one workgroup per (pixel tile, n-tile) with the staged
-  // store already overlaps prologue and store side across the two workgroups of a CU, and whole-line stores drain faster.
-  bool pw = false;
-  int pw_ntb = 1, pw_chunks = 1;
-  if (tune_env("BTX_PW") && !gemm8 && dma && !rowfuse && !patch && dma_nw == 4 && !(flags & BTX_FLAG_TRANSPOSED) && g->KD == 1 && g->KH == 1 && g->KW == 1 &&
-      g->sd == 1 && g->sh == 1 && g->sw == 1 && g->pd == 0 && g->ph == 0 && g->pw == 0 &&
-      out_bf16 == (act_dtype == BTX_ACT_BF16 ? 1 : 0) && (pl.Ng % 64) == 0 && (g->N % 32) == 0 && !(noise && noise->sign_out) &&
-      (long long)pl.M * g->N * (out_bf16 ? 2 : 4) < 0x7ff00000LL) {
-    const long long mt = (pl.M + 255) / 256;
-    const long long base = mt * g->groups * lanes;
-    long long chunks = (1024 + base - 1) / base;  // at least two rounds of workgroups on the 512 slots when the n-tiles allow
-    if (chunks > pl.ntiles) chunks = pl.ntiles;
-    if (chunks < 1) chunks = 1;
-    pw_ntb = (int)((pl.ntiles + chunks - 1) / chunks);
-    pw_chunks = (pl.ntiles + pw_ntb - 1) / pw_ntb;
-    const long long nwg = mt * g->groups * pw_chunks;
-    if (nwg * lanes <= 0x7fffffffLL) {
-      pw = true;
-      pl.mtiles = (int)mt; pl.ksplits = 1; pl.kper = pl.K; pl.nwg = (int)nwg;
     }
   }
   size_t need = plan_ws(pl, g, lanes);
@@ -1357,8 +1285,8 @@ static int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint3
     }
   }
   if ((long long)pl.nwg * lanes > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
-  s->dma = dma; s->par_major = par_major; s->stem = stem; s->pool = want_pool; s->patch = patch; s->gemm8 = gemm8; s->pw = pw;
-  s->dma_nw = dma_nw; s->par_mqp = par_mqp; s->g8_pairs = g8_pairs; s->pw_ntb = pw_ntb; s->pw_chunks = pw_chunks;
+  s->dma = dma; s->par_major = par_major; s->stem = stem; s->pool = want_pool; s->patch = patch; s->gemm8 = gemm8;
+  s->par_mqp = par_mqp; s->g8_pairs = g8_pairs;
   s->out_bf16 = out_bf16; s->stp = stp; s->spp = spp; s->pt = pt;
   s->need = need; s->wt_off = wt_off; s->wt_one = wt_one; s->wt_all = wt_all;
   return 0;
@@ -1375,9 +1303,6 @@ int btx_contract_plan_info(int kind, const BtxGeom* g, int act_dtype, int prec, 
   else if (s.stem) out->family = BTX_FAMILY_STEM;
   else if (s.patch) out->family = s.pt.taps == 33 ? BTX_FAMILY_TAPS : s.pt.taps == 332 ? BTX_FAMILY_TAPS2 : BTX_FAMILY_PATCH;
   else if (s.dma && s.gemm8) out->family = BTX_FAMILY_GEMM8;
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-  else if (s.dma && s.pw) out->family = BTX_FAMILY_PW;
-#endif
   else if (s.dma) out->family = BTX_FAMILY_DMA;
   else out->family = s.gen ? BTX_FAMILY_GATHER : BTX_FAMILY_REGSTAGE;
   out->ksplits = s.pl.ksplits;
@@ -1407,8 +1332,8 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
   if (rc) return rc;
   const Plan& pl = sel.pl;
   const bool gen = sel.gen, dma = sel.dma, rowfuse = sel.rowfuse, par_major = sel.par_major, stem = sel.stem, patch = sel.patch;
-  const bool want_pool = sel.pool, gemm8 = sel.gemm8, pw = sel.pw;
-  const int dma_nw = sel.dma_nw, par_mqp = sel.par_mqp, g8_pairs = sel.g8_pairs, pw_ntb = sel.pw_ntb, pw_chunks = sel.pw_chunks;
+  const bool want_pool = sel.pool, gemm8 = sel.gemm8;
+  const int par_mqp = sel.par_mqp, g8_pairs = sel.g8_pairs;
   const int out_bf16 = sel.out_bf16;
   const StemPlan& stp = sel.stp;
   const StemPoolPlan& spp = sel.spp;
@@ -1417,10 +1342,6 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
   const void* sampled_w = (noise && noise->sampled_w) ? noise->sampled_w : nullptr;
   if (need && (!ws || ws_bytes < need)) return BTX_E_WORKSPACE;
   if (need && (((uintptr_t)ws) & 15)) return BTX_E_ALIGN;
-  // the persistent tap-unrolled kernel keeps its image-group queues (BTX_QUEUE_BYTES, zeroed per launch) behind everything
-  // else; a caller whose workspace has no room for them gets the plain kernel
-  const size_t queue_off = pad256(need);
-  const bool queue_fits = ws && !(((uintptr_t)ws) & 15) && ws_bytes >= queue_off + BTX_QUEUE_BYTES;
 
   ContractParams p;
   memset(&p, 0, sizeof(p));
@@ -1475,9 +1396,6 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     p.w_bytes = wb < 0xffffffffLL ? (uint32_t)wb : 0xffffffffu;
   }
 
-  if (const char* tp = tune_env("BTX_TRACE_PTR")) p.trace = (void*)strtoull(tp, nullptr, 0);  // BTX_PT_TRACE builds only
-  p.pt_nopw = tune_env("BTX_NO_DMA_PW") ? 1 : 0;
-  p.pt_nw = dma_nw;
   p.fd_inner = make_fastdiv((uint32_t)(pl.ntiles * g->groups * pl.ksplits)); p.fd_ksplits = make_fastdiv((uint32_t)pl.ksplits);
   p.fd_ntiles = make_fastdiv((uint32_t)pl.ntiles); p.fd_rtiles = make_fastdiv(1u);
   p.fd_mtiles = make_fastdiv((uint32_t)(pl.mtiles > 0 ? pl.mtiles : 1));
@@ -1492,9 +1410,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     // layer3 — 2.36 MB of tiles per lane, 6.4 MB of activations — moves 2.98x its algorithmic bytes weight-major, where the
     // activations are re-fetched once per n-tile, and 2.00x pixel-major; the launch time is the same either way.)
     const double w_b = (prec == BTX_PREC_BF16 ? 2.0 : 4.0) * (double)g->N * pl.K * (kind == BTX_KIND_FLIPOUT ? 2 : 1);
-    const char* wmb = tune_env("BTX_WG_MB");  // A/B: the weight-tile size (MiB) from which the order turns weight-major
-    p.wg_order = (dma && pl.mtiles > 1 && w_b >= (wmb ? atof(wmb) : BTX_WG_MB_DEFAULT) * 1048576.0) ? 1 : 0;
-    if (tune_env("BTX_WG_ORDER")) p.wg_order = atoi(tune_env("BTX_WG_ORDER"));
+    p.wg_order = (dma && pl.mtiles > 1 && w_b >= WG_MAJOR_MIB * 1048576.0) ? 1 : 0;
   }
   p.fd_Wo = make_fastdiv((uint32_t)pl.Wo); p.fd_Ho = make_fastdiv((uint32_t)pl.Ho); p.fd_Do = make_fastdiv((uint32_t)pl.Do);
   if (dma) {
@@ -1522,8 +1438,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     p.pt_G = pt.G; p.pt_R = pt.R; p.pt_Rp = pt.Rp; p.pt_Wp = pt.Wp; p.pt_PP = pt.PP; p.pt_NI = pt.NI;
     p.fd_ptWp = make_fastdiv((uint32_t)pt.Wp); p.fd_ptRp = make_fastdiv((uint32_t)pt.Rp); p.fd_ptR = make_fastdiv((uint32_t)pt.R);
     p.fd_rtiles = make_fastdiv((uint32_t)pt.rtiles);
-    p.pt_rtiles = pt.rtiles; p.pt_nw = pt.nw; p.pt_mi = pt.mi; p.pt_astage = pt.astage; p.pt_lds = pt.lds;
-    { const char* tn = tune_env("BTX_TAPS_TUNE"); p.pt_tune = tn ? atoi(tn) : 0; }
+    p.pt_rtiles = pt.rtiles; p.pt_nw = pt.nw; p.pt_astage = pt.astage; p.pt_lds = pt.lds;
     p.pt_taps = pt.taps; p.pt_kg = pt.kg; p.pt_lds_g = pt.lds_g;
     p.pt_wide = (pt.taps == 33 || pt.taps == 332) ? pt.wide : 0;
     if (p.pt_wide) {  // the grid's n-tiles are pairs of weight tiles (p.ntiles stays the tile count of the weight layout)
@@ -1532,73 +1447,15 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     }
     p.pt_tall = pt.tall; p.pt_P = pt.P; p.pt_Wt = pt.Wt; p.pt_ncs = pt.ncs;
     p.fd_P = make_fastdiv((uint32_t)pt.P); p.fd_Wt = make_fastdiv((uint32_t)pt.Wt); p.fd_ncs = make_fastdiv((uint32_t)pt.ncs);
-    // Persistent form of the tap-unrolled kernel (btx_contract_taps3.h): about two workgroups per CU, each walking one
-    // tile position through the images of all lanes; the K loop runs across tile boundaries and the store side works
-    // from the fragment registers.  bf16 in and out, 3x3, plain tiles, one K split, an even number of channel blocks,
-    // whole 64-channel n-tiles, 32-aligned s_out words, hashed signs, no bias.  MEASUREMENT ONLY (BTX_PERSIST=1 in tuning
-    // builds; the shipped library does not even contain the kernel): bit-identical results, 241 VGPRs and no scratch, a
-    // 56x56 tile in 29k instead of 35k cycles — and the same launch time, because the chip, at its package power limit,
-    // answers the higher matrix-pipe duty with a lower clock (profiles/r03_persistent_ab.txt, r03_power_probe.txt).
-    {
-      const int bk = NG * 8;
-      const int ncb = pl.Cg / bk;
-      const long long x_all = (long long)p.x_bytes + (long long)(lanes - 1) * (lanes > 1 ? ln->x_stride : 0);
-      const bool ok = pt.taps == 33 && pt.kg == 1 && !pt.tall && (g->NB % pt.G) == 0 && pl.ksplits == 1 && prec == BTX_PREC_BF16 && act_dtype == BTX_ACT_BF16 &&
-                      out_bf16 && (ncb % 2) == 0 && (pl.Ng % 64) == 0 && (g->N % 32) == 0 && !(noise && (noise->sign_in || noise->sign_out)) &&
-                      (pt.astage / 16) >= 1024 && x_all < 0xfff00000LL && !mu_b && queue_fits && pt.lds + 16 <= 81920 &&
-                      (long long)g->NB * pl.Do * pl.Ho * pl.Wo * g->N * 2 < 0x7ff00000LL && tune_env("BTX_PERSIST") && !tune_env("BTX_NO_PERSIST");
-      if (ok) {
-        static int n_cu = 0;
-        if (!n_cu) {
-          int dev = 0;
-          hipDeviceProp_t prop;
-          if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-          if (n_cu <= 0) n_cu = 256;
-        }
-        // a workgroup = one (row tile, n-tile, group) position x a range of image groups: `nseg` ranges per position
-        const long long combos = (long long)pt.rtiles * pl.ntiles * g->groups;
-        const long long igt = (long long)lanes * (g->NB / pt.G);
-        long long nseg = (2LL * n_cu) / combos;
-        if (nseg < 1) nseg = 1;
-        if (nseg > igt) nseg = igt;
-        if (combos * 4 <= (long long)BTX_QUEUE_BYTES) {
-          p.pt_persist = (int)(combos * nseg);
-          p.pt_queue = (uint32_t*)((unsigned char*)ws + queue_off);
-          hipError_t e = hipMemsetAsync(p.pt_queue, 0, (size_t)combos * 4, st);
-          if (e != hipSuccess) return (int)e;
-        }
-      }
-    }
-    // MEASUREMENT ONLY (tuning builds, BTX_DIRECT=1): the store side straight from the fragment registers (direct_epilogue,
-    // btx_epilogue.h) for the tap-unrolled 4-wave kernel — bf16 in and out, one K split, whole aligned 64-channel tiles,
-    // hashed s_out, offsets with an out-of-range value to spare.  Bit-identical; measured (profiles/r04_direct_store_ab.txt):
-    // its 32-byte pieces drain more slowly than the staged side's whole 128-byte lines — 6.1k against 4.9k cycles on a
-    // 56x56 tile, 6.5k against 8.3k on a tall strip — and the launch time does not move either way (+1.7 % .. -0.3 %).
-    p.ep_direct = (tune_env("BTX_DIRECT") && pt.taps == 33 && pt.kg == 1 && pl.ksplits == 1 && prec == BTX_PREC_BF16 &&
-                   act_dtype == BTX_ACT_BF16 && out_bf16 && p.ep_relu != 2 && (pl.Ng % 64) == 0 && (g->N % 32) == 0 && !(noise && noise->sign_out) &&
-                   (long long)pl.M * g->N * 2 < 0x7ff00000LL) ? 1 : 0;
     rc = (prec == BTX_PREC_BF16) ? launch_contract_patch_bf16(kind, p, pl.nwg * lanes, st)
          : (prec == BTX_PREC_BF16X3) ? launch_contract_patch_x3(kind, p, pl.nwg * lanes, st)
                                      : launch_contract_patch_f32(kind, p, pl.nwg * lanes, st);
   } else if (dma && gemm8) {
     p.pt_rtiles = g8_pairs;
     p.fd_rtiles = make_fastdiv((uint32_t)g8_pairs); p.fd_inner = make_fastdiv((uint32_t)(g8_pairs * g->groups));
-    // MEASUREMENT ONLY (tuning builds, BTX_G8_DIRECT=1): the store side from the fragment registers (direct_epilogue,
-    // btx_epilogue.h) where its contract holds — outputs of the activation dtype, hashed s_out, 32-bit byte offsets with an
-    // out-of-range value to spare (per lane).  Bit-identical and 5-25 % slower than the staged side.
-    p.ep_direct = (tune_env("BTX_G8_DIRECT") && (out_bf16 != 0) == (prec == BTX_PREC_BF16) && (g->N % 32) == 0 && p.ep_relu != 2 &&
-                   !(noise && noise->sign_out) && (long long)pl.M * g->N * (out_bf16 ? 2 : 4) < 0x7ff00000LL) ? 1 : 0;
     rc = (prec == BTX_PREC_BF16) ? launch_contract_gemm8_bf16(kind, p, pl.nwg * lanes, st)
          : (prec == BTX_PREC_BF16X3) ? launch_contract_gemm8_x3(kind, p, pl.nwg * lanes, st)
                                      : launch_contract_gemm8_f32(kind, p, pl.nwg * lanes, st);
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-  } else if (dma && pw) {
-    p.pt_R = pw_ntb; p.pt_rtiles = pw_chunks;
-    p.fd_rtiles = make_fastdiv((uint32_t)pw_chunks); p.fd_inner = make_fastdiv((uint32_t)(pw_chunks * g->groups));
-    rc = (prec == BTX_PREC_BF16) ? launch_contract_pw_bf16(kind, p, pl.nwg * lanes, st)
-         : (prec == BTX_PREC_BF16X3) ? launch_contract_pw_x3(kind, p, pl.nwg * lanes, st)
-                                     : launch_contract_pw_f32(kind, p, pl.nwg * lanes, st);
-#endif
   } else if (dma)
     rc = (prec == BTX_PREC_BF16) ? launch_contract_dma_bf16(kind, p, pl.nwg * lanes, st)
          : (prec == BTX_PREC_BF16X3) ? launch_contract_dma_x3(kind, p, pl.nwg * lanes, st)

@@ -132,11 +132,7 @@ struct ContractParams {
   FastDiv fd_sd, fd_sh, fd_sw;  // transposed launches: the gather rule divides by the strides once per pixel, tap and K stage
   int wg_order;  // 0: workgroups that share a pixel tile are neighbours (same XCD L2 holds the activations);
                  // 1: workgroups that share a weight tile are (layers whose sampled weights outweigh their activations)
-  void* trace;  // BTX_PT_TRACE builds: per-wave phase timings (measurement only)
   int pt_nw, pt_astage, pt_lds;
-  int pt_mi;      // patch variant: 32-pixel MFMA tiles per wave (2 | 4)
-  int pt_tune;    // BTX_PT_TRACE builds: bit 6 = report the per-stage split instead of the phase timers
-  int pt_nopw;    // tuning builds (BTX_NO_DMA_PW=1): the generic LDS-DMA kernel for pointwise shapes too (A/B)
   int pt_kg;      // tap-unrolled kernel: K-groups per workgroup (1 | 2)
   int pt_lds_g;   //                      LDS bytes of one K-group
   int pt_taps;    // 10*KH + KW when the tap-unrolled kernel (btx_contract_taps.h) takes the launch, else 0
@@ -161,9 +157,6 @@ struct ContractParams {
   long long lane_x, lane_out, lane_res, lane_wt, lane_partial;
   int lane_wt_delta;  // 1 (Flipout): the lanes share the mu tiles at wt, lane l's delta tiles sit at wt_delta_off + l*lane_wt
   int reverse;        // BTX_FLAG_REVERSE: the grid's tiles in descending order
-  int ep_direct;      // the store side runs from the fragment registers (direct_epilogue_pm, btx_epilogue.h): host-checked
-  int pt_persist;     // > 0: the persistent form of the tap-unrolled kernel (btx_contract_taps3.h) with this many workgroups
-  uint32_t* pt_queue; // persistent form: one zeroed counter per tile position (the image-group queue of its workgroups)
 };
 
 // the MC sample word of a launch whose index lives in device memory, as a SCALAR load: the word does not change while the
@@ -893,10 +886,6 @@ int launch_contract_dma_x3(int kind, const ContractParams& p, int nwg, hipStream
 int launch_contract_gemm8_bf16(int kind, const ContractParams& p, int nwg, hipStream_t st);  // btx_contract_gemm8.h
 int launch_contract_gemm8_f32(int kind, const ContractParams& p, int nwg, hipStream_t st);
 int launch_contract_gemm8_x3(int kind, const ContractParams& p, int nwg, hipStream_t st);
-// pointwise Flipout-GEMM with the n-tile loop inside the workgroup (btx_contract_pw.h)
-int launch_contract_pw_f32(int kind, const ContractParams& p, int nwg, hipStream_t st);
-int launch_contract_pw_bf16(int kind, const ContractParams& p, int nwg, hipStream_t st);
-int launch_contract_pw_x3(int kind, const ContractParams& p, int nwg, hipStream_t st);
 int launch_presample_batch_x3(const PresampleBatch& b, hipStream_t st);
 
 template <int PREC>

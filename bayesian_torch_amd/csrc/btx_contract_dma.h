@@ -33,10 +33,6 @@
 #include "btx_presample.h"
 #include "btx_mma.h"
 
-#ifndef BTX_DMA_RPRE
-#define BTX_DMA_RPRE 1  // residual rows requested in front of the store side's first stage (btx_epilogue.h, RES_PRE): +2 % on cfg5
-#endif
-
 namespace btx {
 
 constexpr int DBM = 512;                    // pixels per workgroup tile, 8-wave blocks (one per CU)
@@ -106,10 +102,6 @@ __global__ __launch_bounds__(64 * NW, 2) void contract_dma_kernel(const Contract
   using LD = DmaLds<NW>;
   constexpr int TP = LD::TP, WD = LD::WD, DA_STAGE = LD::A_STAGE, DS_STAGE = LD::S_STAGE, DA_OFF = LD::A_OFF,
                 DS_OFF = LD::S_OFF, DW_OFF = LD::W_OFF;
-#ifdef BTX_PT_TRACE
-  const uint32_t tr_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-  uint32_t tr_ab = 0, tr_bc = 0, tr_cd = 0, tr_t1 = 0, tr_t2 = 0, tr_tg = 0;
-#endif
   const RngLive rl = rng_live<KIND>(p);
   using ACT = typename std::conditional<PREC == 1, __bf16, float>::type;
   constexpr int G = (PREC == 1) ? 8 : 4;
@@ -414,21 +406,12 @@ __global__ __launch_bounds__(64 * NW, 2) void contract_dma_kernel(const Contract
   // The DMA instructions block at issue while the memory pipeline is full: waves 0-3 issue at the top of the
   // iteration, waves 4-7 after their MFMA block, so that of the two waves sharing a SIMD one is free to compute while
   // the other is stuck issuing.
-#ifdef BTX_PT_TRACE
-  tr_tg = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
   if (nstages > 0) {
     issue_acts();
     if (nstages > 1) issue_acts();
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     int a_slot = 0;
-#ifdef BTX_PT_TRACE
-    tr_t1 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
     for (int s = 0; s < nstages; ++s) {
-#ifdef BTX_PT_TRACE
-      const uint32_t tA = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
       const bool acts_issued = s + 2 < nstages;
       const bool w_issued = s + WD - 1 < nstages;
       if (!upper) {
@@ -440,21 +423,8 @@ __global__ __launch_bounds__(64 * NW, 2) void contract_dma_kernel(const Contract
         if (w_issued) issue_w(s + WD - 1);
         if (acts_issued) issue_acts();
       }
-#ifdef BTX_PT_TRACE
-      __builtin_amdgcn_sched_barrier(0);
-      const uint32_t tB = (uint32_t)__builtin_amdgcn_s_memtime();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       wait_vmcnt((acts_issued ? 4 : 0) + (w_issued ? w_nops : 0));
-#ifdef BTX_PT_TRACE
-      const uint32_t tC = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef BTX_PT_TRACE
-      const uint32_t tD = (uint32_t)__builtin_amdgcn_s_memtime();
-      tr_ab += tB - tA; tr_bc += tC - tB; tr_cd += tD - tC;
-#endif
       a_slot = (a_slot == DMA_D - 1) ? 0 : a_slot + 1;
     }
   }
@@ -464,14 +434,6 @@ __global__ __launch_bounds__(64 * NW, 2) void contract_dma_kernel(const Contract
     BTX_SECTION_PARAMS(pe, logical2);
     const uint32_t m0 = (uint32_t)tile_m0;
     const int nvalid = par ? par_nvalid : min(TP, pe.M - (int)m0);
-#ifdef BTX_PT_TRACE
-    tr_t2 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-#ifdef BTX_EP_TRACE
-    uint32_t ep_t[2] = {0, 0};
-    staged_epilogue<KIND, NW, BTX_DMA_RPRE != 0>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, m0, nvalid, ep_t);
-    tr_ab = ep_t[0] - tr_t2; tr_bc = ep_t[1] - ep_t[0];
-#else
     bool par_ep = false;
     if constexpr (!PW && TR) par_ep = pe.par_major != 0;
     if (par_ep) {
@@ -479,28 +441,10 @@ __global__ __launch_bounds__(64 * NW, 2) void contract_dma_kernel(const Contract
         const PixParity pm = {pe, m0, nvalid};
         staged_epilogue_pm<KIND, NW, PixParity, false>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, pm);
       }
-    } else {
-      staged_epilogue<KIND, NW, BTX_DMA_RPRE != 0>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, m0, nvalid);
-    }
-#endif
-  }
-#ifdef BTX_PT_TRACE
-  if (p.trace) {
-#ifdef BTX_EP_TRACE
-    const uint32_t tr_tx = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t tr_t3 = (uint32_t)__builtin_amdgcn_s_memtime();
-#ifdef BTX_EP_TRACE
-    tr_cd = tr_t3 - tr_tx;
-#endif
-    if (lane == 0) {
-      uint32_t* tr = (uint32_t*)p.trace + (size_t)(blockIdx.x * NW + wave) * 8;
-      tr[0] = tr_t1 - tr_t0; tr[1] = tr_ab; tr[2] = tr_bc; tr[3] = tr_cd; tr[4] = tr_t3 - tr_t2; tr[5] = tr_t3 - tr_t0;
-      tr[6] = tr_t0; tr[7] = tr_tg - tr_t0;  // geometry part of the prologue
+    } else {  // RES_PRE: residual rows requested in front of the store side's first stage (+2 % on cfg5)
+      staged_epilogue<KIND, NW, true>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, m0, nvalid);
     }
   }
-#endif
 }
 
 template <int PREC>
@@ -519,12 +463,10 @@ static int launch_contract_dma_impl(int kind, const ContractParams& p, int nwg, 
   int rc = launch_presample_impl<PREC>(kind, p, st);
   if (rc) return rc;
   // the pointwise form where its contract holds (two workgroups per CU: the shapes that are all prologue and store side)
-  const bool pw = p.pointwise && !p.transposed && !p.sign_unaligned && p.pt_nw == 4 && !p.pt_nopw;
+  const bool pw = p.pointwise && !p.transposed && !p.sign_unaligned;
   if (pw) { if (kind == 0) BTX_LAUNCH_DMA(0, 4, true, false); else BTX_LAUNCH_DMA(1, 4, true, false); }
-  else if (p.pt_nw == 4 && p.transposed) { if (kind == 0) BTX_LAUNCH_DMA(0, 4, false, true); else BTX_LAUNCH_DMA(1, 4, false, true); }
-  else if (p.pt_nw == 4) { if (kind == 0) BTX_LAUNCH_DMA(0, 4, false, false); else BTX_LAUNCH_DMA(1, 4, false, false); }
-  else if (p.transposed) { if (kind == 0) BTX_LAUNCH_DMA(0, 8, false, true); else BTX_LAUNCH_DMA(1, 8, false, true); }
-  else { if (kind == 0) BTX_LAUNCH_DMA(0, 8, false, false); else BTX_LAUNCH_DMA(1, 8, false, false); }
+  else if (p.transposed) { if (kind == 0) BTX_LAUNCH_DMA(0, 4, false, true); else BTX_LAUNCH_DMA(1, 4, false, true); }
+  else { if (kind == 0) BTX_LAUNCH_DMA(0, 4, false, false); else BTX_LAUNCH_DMA(1, 4, false, false); }
 #undef BTX_LAUNCH_DMA
   return (int)hipGetLastError();
 }

@@ -28,9 +28,6 @@
 #include "btx_mma.h"
 #include "btx_contract_taps.h"
 #include "btx_contract_taps2.h"
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-#include "../../tools/experimental/btx_contract_taps3.h"  // persistent form: measured and parked, measurement builds only
-#endif
 
 namespace btx {
 
@@ -43,9 +40,9 @@ namespace btx {
 
 // ContractParams fields used in addition: pt_G, pt_R, pt_Rp, pt_Wp, pt_PP, pt_NI, pt_rtiles, wt (pre-sampled weight
 // tiles), wt_bytes, wt_delta_off; kper = channel blocks per split * BK.
-// MI = 32-pixel MFMA tiles per wave: 2 (64 pixels, 128 accumulator registers, two waves per SIMD) or 4 (128 pixels, 256
-// accumulators — the unified 512-entry register file of a single wave per SIMD; every weight fragment read from LDS
-// then feeds twice as many MFMAs).
+// MI = 32-pixel MFMA tiles per wave: 2 (64 pixels, 128 accumulator registers, two waves per SIMD), the form the launcher
+// instantiates.  4 (128 pixels, 256 accumulators — the unified 512-entry register file of a single wave per SIMD; every
+// weight fragment read from LDS then feeds twice as many MFMAs) spills about 700 B of scratch and is not launched.
 template <int PREC, int KIND, int NW, int MI>
 __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_kernel(const ContractParams) {
   BTX_SECTION_PARAMS(p, logical);  // prologue + K loop; the store side has its own view (btx_contract.h)
@@ -65,10 +62,6 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
   const int h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-#ifdef BTX_PT_TRACE
-  const uint32_t tr_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-  uint32_t tr_ab = 0, tr_bc = 0, tr_cd = 0, tr_t1 = 0, tr_t2 = 0;
-#endif
   uint32_t u_mtile, u_rem, u_split, u_ntile, u_group, u_t;
   if (p.wg_order) fdivmod((uint32_t)logical, p.fd_mtiles, (uint32_t)p.mtiles, u_rem, u_mtile);  // weight-major (btx_api.hip)
   else fdivmod((uint32_t)logical, p.fd_inner, (uint32_t)(p.ntiles * p.groups * p.ksplits), u_mtile, u_rem);
@@ -214,28 +207,17 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
     int q[MI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) q[mi] = q0[mi] + toff;
-    if constexpr (BTX_PT_ABL & 2) {
 #pragma unroll
-      for (int kk = 0; kk < NG / 2; ++kk)
+    for (int kk = 0; kk < NG / 2; ++kk) {
+      const int row = 2 * kk + h;
 #pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          f.a[kk][i] = (u32x4){(uint32_t)q[0], (uint32_t)kk, 3u, 4u};
-          f.wm[kk][i & 1] = (u32x4){(uint32_t)q[1], 7u, (uint32_t)wslot, 4u};
-          f.sw[i] = (uint32_t)toff;
-        }
-    } else {
+      for (int mi = 0; mi < MI; ++mi) f.a[kk][mi] = *(const u32x4*)(as + q[mi] * 64 + ((row ^ ((q[mi] >> 2) & 3)) * 16));
 #pragma unroll
-      for (int kk = 0; kk < NG / 2; ++kk) {
-        const int row = 2 * kk + h;
+      for (int ni = 0; ni < 2; ++ni) f.wm[kk][ni] = *(const u32x4*)(ws + (row * BN + ni * 32 + l31) * 16);
+    }
+    if constexpr (KIND == 1) {
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) f.a[kk][mi] = *(const u32x4*)(as + q[mi] * 64 + ((row ^ ((q[mi] >> 2) & 3)) * 16));
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) f.wm[kk][ni] = *(const u32x4*)(ws + (row * BN + ni * 32 + l31) * 16);
-      }
-      if constexpr (KIND == 1) {
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) f.sw[mi] = *(const uint32_t*)(ss + q[mi] * 4);
-      }
+      for (int mi = 0; mi < MI; ++mi) f.sw[mi] = *(const uint32_t*)(ss + q[mi] * 4);
     }
   };
   // =================== main loop ==========================================================================
@@ -247,11 +229,7 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
   //      other waves at the barrier.
   // vmcnt retires in order, so "landed" = at most as many operations outstanding as this wave has issued after the one
   // it needs; those counts are wave-uniform scalars.
-#ifdef BTX_PT_PIECE_STAGES
-  const int ppst = (p.pt_NI + BTX_PT_PIECE_STAGES - 1) / BTX_PT_PIECE_STAGES;  // measurement: pieces within N stages
-#else
   const int ppst = (p.pt_NI + (T > 3 ? T - 4 : 0)) / (T > 3 ? T - 3 : 1);  // pieces per stage: done 3 stages early
-#endif
   if (nstages > 0) {
     write_signs(0);
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -267,17 +245,11 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
     Frag fa, fb;
     load_frag(fa, 0, 0, 0);
     advance_load();
-#ifdef BTX_PT_TRACE
-    tr_t1 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
     auto iter = [&](int s, Frag& cur, Frag& nxt) __attribute__((always_inline)) {
       const bool next_cb = cbi + 1 < ncb;
       int m2 = nissued;
-#ifdef BTX_PT_TRACE
-      const uint32_t tA = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-      if (!(BTX_PT_ABL & (4 | 128)) && wi_s < nstages) { issue_w_next(); nissued += w_nops; m2 = nissued; }
-      if (!(BTX_PT_ABL & (4 | 256)) && next_cb) {
+      if (wi_s < nstages) { issue_w_next(); nissued += w_nops; m2 = nissued; }
+      if (next_cb) {
         for (int j = t * ppst; j < (t + 1) * ppst && j < p.pt_NI; ++j)
           if (16 * (wave + NW * j) < p.pt_PP) { issue_patch_piece(cbi + 1, j); mpiece = ++nissued; }
         if (t == 0) write_signs(cbi + 1);  // the sign slot of block cbi+1 was last read during block cbi-1
@@ -286,24 +258,10 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
       load_delta<KIND>(dfrag, smem + PT_W_OFF + (s & (PT_WD - 1)) * DW_STAGE, l31, h);
       if (s + 1 < nstages) { load_frag(nxt, l_cbi, l_toff, (s + 1) & (PT_WD - 1)); advance_load(); }
       stage_mma<PREC, KIND, MI>(cur, dfrag, accm, accd, l31, h);
-#ifdef BTX_PT_TRACE
-      __builtin_amdgcn_sched_barrier(0);
-      const uint32_t tB = (uint32_t)__builtin_amdgcn_s_memtime();
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       int allowed = nissued - m1;
       if (next_cb && t == (T >= 2 ? T - 2 : 0)) allowed = min(allowed, nissued - mpiece);
-      if constexpr (!(BTX_PT_ABL & 64)) wait_vmcnt(allowed);
-#ifdef BTX_PT_TRACE
-      const uint32_t tC = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
-      if constexpr (BTX_PT_ABL & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef BTX_PT_TRACE
-      const uint32_t tD = (uint32_t)__builtin_amdgcn_s_memtime();
-      tr_ab += tB - tA; tr_bc += tC - tB; tr_cd += tD - tC;
-#endif
+      wait_vmcnt(allowed);
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       m1 = m2;
       if (++t == T) { t = 0; ++cbi; }
     };
@@ -314,10 +272,6 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
     }
     if (s < nstages) iter(s, fa, fb);
   }
-  if constexpr (BTX_PT_ABL & 32) return;
-#ifdef BTX_PT_TRACE
-  tr_t2 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
 
   // =================== epilogue (btx_epilogue.h) ============================================================
   {
@@ -334,21 +288,10 @@ __global__ __launch_bounds__(64 * NW, (MI == 4) ? 1 : 2) void contract_patch_ker
         __builtin_amdgcn_sched_barrier(0);  // one half of the 256 accumulators at a time
         staged_epilogue<KIND, NW>(pe, rl, reinterpret_cast<const f32x16(&)[2][2]>(accm[2 * hf]),
                                   reinterpret_cast<const f32x16(&)[2][2]>(accd[2 * hf]), smem, tid, wave, lane, ntile,
-                                  group, split, m0, nvalid, nullptr, wave * (MI / 2) + hf, hf == 0);
+                                  group, split, m0, nvalid, wave * (MI / 2) + hf, hf == 0);
       }
     }
   }
-#ifdef BTX_PT_TRACE
-  if (p.trace) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t tr_t3 = (uint32_t)__builtin_amdgcn_s_memtime();
-    if (lane == 0) {
-      uint32_t* tr = (uint32_t*)p.trace + (size_t)(blockIdx.x * NW + wave) * 8;
-      tr[0] = tr_t1 - tr_t0; tr[1] = tr_ab; tr[2] = tr_bc; tr[3] = tr_cd; tr[4] = tr_t3 - tr_t2; tr[5] = tr_t3 - tr_t0;
-      tr[6] = tr_t0; tr[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-    }
-  }
-#endif
 }
 
 template <int PREC>
@@ -388,26 +331,6 @@ static int launch_contract_patch_impl(int kind, const ContractParams& p, int nwg
 #undef BTX_LAUNCH_T2
     return (int)hipGetLastError();
   }
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-  if constexpr (PREC == 1) {
-    if (p.pt_taps == 33 && p.pt_persist > 0) {  // persistent form (btx_contract_taps3.h): the grid is pt_persist workgroups
-#define BTX_LAUNCH_T3(KIND)                                                                                       \
-  do {                                                                                                            \
-    auto kfn = contract_taps3_kernel<KIND>;                                                                       \
-    static bool attr_done = false;                                                                                \
-    if (!attr_done) {                                                                                             \
-      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 163840);   \
-      if (e != hipSuccess) return (int)e;                                                                         \
-      attr_done = true;                                                                                           \
-    }                                                                                                             \
-    hipLaunchKernelGGL(kfn, dim3(p.pt_persist), dim3(256), p.pt_lds + 16, st, p);                                      \
-  } while (0)
-      if (kind == 0) BTX_LAUNCH_T3(0); else BTX_LAUNCH_T3(1);
-#undef BTX_LAUNCH_T3
-      return (int)hipGetLastError();
-    }
-  }
-#endif
   if (p.pt_taps == 33) {  // 3x3, 4-wave K-groups: the tap-unrolled kernel (btx_contract_taps.h)
 #define BTX_LAUNCH_TP(KIND, KG, ...)                                                                               \
   do {                                                                                                            \
@@ -422,17 +345,9 @@ static int launch_contract_patch_impl(int kind, const ContractParams& p, int nwg
   } while (0)
     if (p.pt_kg == 2) { if (kind == 0) BTX_LAUNCH_TP(0, 2); else BTX_LAUNCH_TP(1, 2); }
     else {
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-      if constexpr (PREC == 1) {
-        if (p.ep_direct) {  // MEASUREMENT ONLY (BTX_DIRECT=1): the store side from the fragment registers, btx_epilogue.h
-          if (kind == 0) BTX_LAUNCH_TP(0, 1, true); else BTX_LAUNCH_TP(1, 1, true);
-          return (int)hipGetLastError();
-        }
-      }
-#endif
       if constexpr (PREC == 1) {
         if (p.pt_wide && kind == 0) {  // Reparameterization on 64 x 128 wave tiles (btx_contract_taps.h, WIDE)
-          BTX_LAUNCH_TP(0, 1, false, true);
+          BTX_LAUNCH_TP(0, 1, true);
           return (int)hipGetLastError();
         }
       }
@@ -441,8 +356,7 @@ static int launch_contract_patch_impl(int kind, const ContractParams& p, int nwg
 #undef BTX_LAUNCH_TP
     return (int)hipGetLastError();
   }
-  if (p.pt_mi == 4) { if (kind == 0) BTX_LAUNCH_PT(0, 4, 4); else BTX_LAUNCH_PT(1, 4, 4); }
-  else if (p.pt_nw == 4) { if (kind == 0) BTX_LAUNCH_PT(0, 4, 2); else BTX_LAUNCH_PT(1, 4, 2); }
+  if (p.pt_nw == 4) { if (kind == 0) BTX_LAUNCH_PT(0, 4, 2); else BTX_LAUNCH_PT(1, 4, 2); }
   else { if (kind == 0) BTX_LAUNCH_PT(0, 8, 2); else BTX_LAUNCH_PT(1, 8, 2); }
 #undef BTX_LAUNCH_PT
   return (int)hipGetLastError();

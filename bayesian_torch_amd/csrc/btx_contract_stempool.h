@@ -43,24 +43,11 @@
 
 namespace btx {
 
-#ifndef BTX_STEM_STEPS
-#define BTX_STEM_STEPS 1  // step layout of a Flipout K phase (run_k): 0 = round 2's (sign copy + mean) | delta 0-3 | delta 4-6,
-#endif                    // 1 = sign copy | mean | delta
-#ifndef BTX_SP_ABL
-#define BTX_SP_ABL 0  // measurement-only ablation bits (wrong results; tools/r06/e6.sh, with -DBTX_STEM_PASS3=0 -DBTX_STEM_NB=2): 1 no MFMA in
-#endif                // the two-register-set passes (run_pass), 2 no fragment reads after their first stage, 4 the store role does nothing
-#ifndef BTX_STEM_NB
-#define BTX_STEM_NB 1  // workgroup barriers INSIDE a phase (besides its closing one).  2 (rounds 2-5): sign copy | mean | delta against
-#endif                 // stage 0-31 | stage 32-63 | pool.  1 (round 6): [copy +] first part | rest against staging | pool — the barrier between
-                       // the two staging halves guarded nothing (the pool is what reads the rows), and with the store role's steps now 2.1k |
-                       // 1.6k cycles (Reparameterization) the three-way split left the K role's first third (patch DMA issue + stages) alone
-                       // on the critical path
-#ifndef BTX_STEM_PRIO
-#define BTX_STEM_PRIO 2
-#endif
-#ifndef BTX_STEM_PASS3
-#define BTX_STEM_PASS3 1  // fragments two stages ahead in the Reparameterization pass and in Flipout's mean pass (run_pass3)
-#endif
+// Workgroup barriers INSIDE a phase (besides its closing one): [copy +] first part | rest against staging | pool.  Rounds 2-5
+// had two (sign copy | mean | delta against stage 0-31 | stage 32-63 | pool): the barrier between the two staging halves
+// guarded nothing (the pool is what reads the rows), and with the store role's steps now 2.1k | 1.6k cycles
+// (Reparameterization) the three-way split left the K role's first third (patch DMA issue + stages) alone on the critical path.
+constexpr int SP_NB = 1;
 constexpr int SP_HROWS = 2;  // conv rows per half tile
 constexpr int SP_LROWS = 3;  // LDS rows (64 channels each) of the store side: r0, r1 and the carry row
 constexpr int SP_MAXST = 7;  // K-stages whose weight tiles stay resident
@@ -96,7 +83,6 @@ __device__ __forceinline__ void sp_mma(const SpFrag& f, f32x16 (&acc)[2][2]) {
     for (int mi = 0; mi < MIA; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) {
-        if constexpr (BTX_SP_ABL & 1) { asm volatile("" ::"v"(f.w[kk][ni]), "v"(f.a[kk][mi])); acc[mi][ni][0] += 1.f; continue; }
         if constexpr (ZERO) {
           const f32x16 zc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, f.w[kk][ni]),
@@ -118,19 +104,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
   const ContractParams p = lane_view(pk, logical);
   constexpr int G = 8, BK = NG * G;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#ifdef BTX_PT_TRACE
-  const uint32_t tr_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-  uint32_t tr_pro = 0, tr_k = 0, tr_st = 0, tr_pool = 0, tr_bar = 0, tr_x = 0, tr_bld = 0;
-#define SP_T(var) { __builtin_amdgcn_sched_barrier(0); const uint32_t n_ = (uint32_t)__builtin_amdgcn_s_memtime(); var += n_ - tr_x; tr_x = n_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define SP_T(var)
-#endif
-#if defined(BTX_PT_TRACE) && defined(BTX_SP_TR2)  // the passes of a Flipout K role without their barrier waits (tr[0] mean, tr[1] delta, tr[2] waits)
-  uint32_t tr_m = 0, tr_d = 0, tr_w = 0, tr_y = 0;
-#define SP_T2(var) { __builtin_amdgcn_sched_barrier(0); const uint32_t n_ = (uint32_t)__builtin_amdgcn_s_memtime(); var += n_ - tr_y; tr_y = n_; __builtin_amdgcn_sched_barrier(0); }
-#else
-#define SP_T2(var)
-#endif
 #define SP_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   const RngLive rl = rng_live<KIND>(p);
 
@@ -332,8 +305,7 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
     load(fa, 0);
     auto iter = [&](int s, SpFrag& cur, SpFrag& nxt, auto zero_tag) __attribute__((always_inline)) {
       if (s == bs0 || s == bs1) { SP_BARRIER(); ++nb; }
-      if constexpr (BTX_SP_ABL & 2) { nxt = cur; asm volatile("" : "+v"(nxt.a[0][0]), "+v"(nxt.w[0][0])); }
-      else if (s + 1 < nstages) load(nxt, s + 1);
+      if (s + 1 < nstages) load(nxt, s + 1);
       sp_mma<MIA, decltype(zero_tag)::value>(cur, acc);
     };
     iter(0, fa, fb, std::true_type{});
@@ -429,42 +401,25 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
     const unsigned char* raw = smem + A_OFF + (u & 1) * p.pt_astage;
     int nb;
     // the K role's wave ahead of the store role's in the SIMD's issue arbitration: Flipout band 139.2k -> 136.8k cycles (E11)
-    __builtin_amdgcn_s_setprio(BTX_STEM_PRIO);
+    __builtin_amdgcn_s_setprio(2);
     if constexpr (KIND == 1) {
-#if BTX_STEM_STEPS == 0
-      run_pass(raw, 0, accm, -1, -1, mia_tag);
-      SP_BARRIER();  // the signed copy is complete (build_signed ran before this pass)
-      nb = 1 + run_pass(smem + X_OFF, 4096, accd, (nstages + 1) >> 1, -1, mia_tag);
-#else
       // steps of the phase: sign copy | mean pass | delta pass, against the store group's stage 0-31 | stage 32-63 | pool.
       // Phase timers (profiles/r02_stem_pool.txt, per wave and step): sign copy 2.35k cycles, each pass 2.6k; store steps 1.9k,
       // 1.9k, 2.5k.  With the mean pass in the first step (round 2) the phase cost max(4.95, 1.9) + max(1.5, 1.9) + max(1.1,
       // 2.5) = 9.35k; one K step per store step: 2.35 + 2.6 + 2.6 = 7.55k.  Measured at 20 lanes: 1300 -> 1200 us per launch.
       // (Also measured, not kept: the sign copy sliced into the shadow of the mean pass's MFMAs with the delta pass in two
       // steps: 1350 us; the copy's LDS reads four chunks deep instead of one at a time: no change.)
-#if BTX_STEM_NB == 2
-      SP_BARRIER();  // the signed copy is complete (build_signed ran before this call)
-#endif
-      SP_T2(tr_w)
-      if (decltype(mia_tag)::value == 2 && BTX_STEM_PASS3 && (nstages - 1) % 3 == 0) run_pass3(raw, 0, accm, -1, -1);  // (accd is not live yet)
+      if (decltype(mia_tag)::value == 2 && (nstages - 1) % 3 == 0) run_pass3(raw, 0, accm, -1, -1);  // (accd is not live yet)
       else run_pass(raw, 0, accm, -1, -1, mia_tag);
-      SP_T2(tr_m)
-      SP_BARRIER();  // (BTX_STEM_NB == 1: this is the barrier behind which every wave's part of the signed copy is complete)
-      SP_T2(tr_w)
+      SP_BARRIER();  // (the barrier behind which every wave's part of the signed copy is complete)
       run_pass(smem + X_OFF, 4096, accd, -1, -1, mia_tag);
-      SP_T2(tr_d)
-      nb = BTX_STEM_NB;
-#endif
+      nb = SP_NB;
     } else {
-#if BTX_STEM_NB == 2
-      const int b0_ = (nstages + 2) / 3, b1_ = 2 * b0_;
-#else
       const int b0_ = (nstages * 4 + 3) / 7 > 0 ? (nstages * 4 + 3) / 7 : -1, b1_ = -1;  // one inner barrier, before stage 4 of 7
-#endif
-      if (decltype(mia_tag)::value == 2 && BTX_STEM_PASS3 && (nstages - 1) % 3 == 0) nb = run_pass3(raw, 0, accm, b0_, b1_);
+      if (decltype(mia_tag)::value == 2 && (nstages - 1) % 3 == 0) nb = run_pass3(raw, 0, accm, b0_, b1_);
       else nb = run_pass(raw, 0, accm, b0_, b1_, mia_tag);
     }
-    for (; nb < BTX_STEM_NB; ++nb) SP_BARRIER();
+    for (; nb < SP_NB; ++nb) SP_BARRIER();
     __builtin_amdgcn_s_setprio(0);
   };
 
@@ -625,10 +580,6 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
   bool carry_pending = false;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // weights, first patch, constants
   SP_BARRIER();
-#ifdef BTX_PT_TRACE
-  tr_x = tr_t0;
-  SP_T(tr_pro)
-#endif
   using T = std::true_type;
   using F = std::false_type;
   for (int ph = 0; ph <= NH; ++ph) {
@@ -646,16 +597,14 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
       if (ph < NH) {
         if (ph + 1 < NH) issue_patch(ph + 1, w4, 4);
         build_signed(ph);
-        SP_T(tr_bld)
         const int mia = mia_of(ph);
         if (mia == 2) run_k(ph, std::integral_constant<int, 2>{});
         else if (mia == 1) { clear_acc(1); run_k(ph, std::integral_constant<int, 1>{}); }
-        else { clear_acc(0); for (int b_ = 0; b_ < BTX_STEM_NB; ++b_) SP_BARRIER(); }
-        SP_T(tr_k)
+        else { clear_acc(0); for (int b_ = 0; b_ < SP_NB; ++b_) SP_BARRIER(); }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the next patch: issued a whole K loop ago
       } else {
         clear_acc(0);
-        for (int b_ = 0; b_ < BTX_STEM_NB; ++b_) SP_BARRIER();
+        for (int b_ = 0; b_ < SP_NB; ++b_) SP_BARRIER();
       }
     } else {
       // ---------------- store role: half tile ph-1 (this group's accumulators of the previous phase)
@@ -663,47 +612,20 @@ __global__ __launch_bounds__(512, 2) void stem_pool_kernel(const ContractParams 
       // (measured, not kept: the next patch requested HERE, by the group that multiplies it next phase — the K role's step gets 1k
       // cycles shorter, the band not one cycle: E10)
       if (ph + 1 < NH) write_signs(ph + 1, gtid, 256);
-      if ((BTX_SP_ABL & 4) && u >= 0) {
-        for (int b_ = 0; b_ < BTX_STEM_NB; ++b_) SP_BARRIER();
-      } else if (u >= 0) {
+      if (u >= 0) {
         const int mia = mia_of(u);
         stage_dispatch(u, mia, std::integral_constant<int, 0>{});
-        SP_T(tr_st)
-#if BTX_STEM_NB == 2
-        SP_BARRIER();
-        SP_T(tr_bar)
-#endif
         stage_dispatch(u, mia, std::integral_constant<int, 1>{});
-        SP_T(tr_st)
         SP_BARRIER();
-        SP_T(tr_bar)
         if (relu) pool_all(u, cnew, T{}); else pool_all(u, cnew, F{});
         carry_pending = true;
-        SP_T(tr_pool)
       } else {
-        for (int b_ = 0; b_ < BTX_STEM_NB; ++b_) SP_BARRIER();
+        for (int b_ = 0; b_ < SP_NB; ++b_) SP_BARRIER();
       }
     }
     SP_BARRIER();
-    SP_T(tr_bar)
   }
-#ifdef BTX_PT_TRACE
-  if (p.trace) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t tr_t3 = (uint32_t)__builtin_amdgcn_s_memtime();
-    if (lane == 0) {
-      uint32_t* tr = (uint32_t*)p.trace + (size_t)(blockIdx.x * 8 + wave) * 8;
-      tr[0] = tr_pro; tr[1] = tr_bld; tr[2] = tr_k; tr[3] = tr_st; tr[4] = tr_pool; tr[5] = tr_t3 - tr_t0; tr[6] = tr_bar;
-#ifdef BTX_SP_TR2
-      tr[0] = tr_m; tr[1] = tr_d; tr[6] = tr_w;
-#endif
-      tr[7] = tr_t0;
-    }
-  }
-#endif
 }
-#undef SP_T
-#undef SP_T2
 #undef SP_BARRIER
 
 static int launch_stem_pool_impl(int kind, const ContractParams& p, int nwg, hipStream_t st) {

@@ -42,17 +42,6 @@ __device__ __forceinline__ void end_stage() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
-// the lane view of the prologue: BTX_TAPS_FLAT=1 reads every field of the lane arithmetic in ONE batch of scalar loads
-// (lane_view_flat, btx_contract.h) instead of one dependent batch per `if` of lane_view
-#ifndef BTX_TAPS_FLAT
-#define BTX_TAPS_FLAT 0
-#endif
-#if BTX_TAPS_FLAT
-#define BTX_TAPS_PARAMS(name, logical_var) BTX_SECTION_PARAMS_FLAT(name, logical_var)
-#else
-#define BTX_TAPS_PARAMS(name, logical_var) BTX_SECTION_PARAMS(name, logical_var)
-#endif
-
 template <int I, int N, class F>
 __device__ __forceinline__ void static_for(F&& f) {
   if constexpr (I < N) {
@@ -87,21 +76,20 @@ constexpr int tp_pieces(int t) {
 // (measured: 1800 cycles per stage), so a K-group's stage is two halves — H1: DMA issue + the LDS reads of THIS stage's
 // fragments, H2: the MFMAs — with a barrier after each, and group 1 runs half a stage behind group 0 (one extra barrier
 // before its first stage, group 0 one after its last): one group's MFMA half sits beside the other's load half.
-// DIRECT (bf16, KG == 1; the host launches it when ContractParams.ep_direct): the store side runs from the fragment registers
-// (direct_epilogue, btx_epilogue.h) — its own instantiation of the kernel, because with both store sides behind a run-time
-// branch of one kernel hipcc spills (the staged side's address arithmetic is interleaved with the fold).
+// The store side is staged through LDS.  A store side straight from the fragment registers was measured and not kept
+// (profiles/r04_direct_store_ab.txt): bit-identical, but its 32-byte pieces drain more slowly than whole 128-byte lines — 6.1k
+// against 4.9k cycles on a 56x56 tile — and the launch time does not move either way.
 // WIDE (Reparameterization, bf16, KG == 1; the host launches it when ContractParams.pt_wide): the wave's tile is 64 pixels x 128
 // channels — 2 x 4 MFMA tiles, the register budget Flipout spends on its second accumulator set.  A Reparameterization stage on
 // the 2 x 2 tile reads 8 fragments for 8 MFMAs and re-fetches the patch once per 64 output channels; here the stage's second
 // weight tile (n-tile 2*ntile + 1, in the LDS slot Flipout's delta tile takes) shares the activation fragments of the first:
 // 12 reads for 16 MFMAs, half the patch DMA per MFMA, the K loop of the Flipout kernel without its sign masks.  The workgroup
 // stores two 64-channel tiles, one after the other, through the same staging area.
-template <int PREC, int KIND, int KH, int KW, int KG, bool DIRECT = false, bool WIDE = false>
+template <int PREC, int KIND, int KH, int KW, int KG, bool WIDE = false>
 __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const ContractParams) {
-  static_assert(!DIRECT || (PREC == 1 && KG == 1), "direct store side: bf16, one K-group");
-  static_assert(!WIDE || (PREC == 1 && KG == 1 && KIND == 0 && !DIRECT), "wide tile: bf16 Reparameterization, one K-group");
+  static_assert(!WIDE || (PREC == 1 && KG == 1 && KIND == 0), "wide tile: bf16 Reparameterization, one K-group");
   constexpr int K2 = (KIND == 1 || WIDE) ? 1 : 0;  // two weight tiles per stage and two accumulator sets
-  BTX_TAPS_PARAMS(p, logical);  // prologue + K loop; the store side has its own view (btx_contract.h)
+  BTX_SECTION_PARAMS(p, logical);  // prologue + K loop; the store side has its own view (btx_contract.h)
   constexpr int NW = 4, NT = 256, MI = 2, T = KH * KW;
   static_assert(T >= 5 && T <= 32, "tap-unrolled kernel: 5..32 taps");
   constexpr int MAXNI = TP_MAXNI;
@@ -126,15 +114,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
   const int kg = (KG == 1) ? 0 : (wave_all >> 2);
   unsigned char* const smem = smem_all + kg * p.pt_lds_g;
 
-#ifdef BTX_PT_TRACE
-  const uint32_t tr_t0 = (uint32_t)__builtin_amdgcn_s_memtime();
-  const uint32_t tr_r0 = (uint32_t)__builtin_amdgcn_s_memrealtime();  // constant 100 MHz reference clock
-  uint32_t tr_t1 = 0, tr_t2 = 0, tr_s[4] = {0, 0, 0, 0};
-  uint32_t tr_p[6] = {0, 0, 0, 0, 0, 0};  // prologue sub-stamps (pt_tune bit 7)
-#define BTX_TR_P(i) do { __builtin_amdgcn_sched_barrier(0); tr_p[i] = (uint32_t)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define BTX_TR_P(i) do { } while (0)
-#endif
   uint32_t u_mtile, u_rem, u_split, u_ntile, u_group, u_t;
   const uint32_t ntg = (uint32_t)(WIDE ? p.ntiles >> 1 : p.ntiles);  // n-tiles of the grid (wide: fd_ntiles / fd_inner are made for it)
   if (p.wg_order) fdivmod((uint32_t)logical, p.fd_mtiles, (uint32_t)p.mtiles, u_rem, u_mtile);  // weight-major (btx_api.hip)
@@ -241,7 +220,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     }
   }
   pmask = __builtin_amdgcn_readfirstlane(pmask);
-  BTX_TR_P(0);  // patch DMAs issued
   if (ncb > 0) {  // stages 1 and 2 (taps 1, 2 of the first block)
     issue_w(1u, (uint32_t)cb0, 1);
     issue_w(2u, (uint32_t)cb0, 2);
@@ -260,7 +238,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     }
   }
 
-  BTX_TR_P(1);  // sign keys derived (sample word arrived)
   auto write_signs = [&](int slot, int cb) __attribute__((always_inline)) {
     if constexpr (KIND == 1) {
       unsigned char* ss = smem + PT_S_OFF + slot * s_stage;
@@ -295,12 +272,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
       q0[mi] = ok ? (gi * p.pt_Rp + r) * p.pt_Wp + c : 0;
     }
   }
-#ifdef BTX_PT_NOJUMP
-  // MEASUREMENT ONLY (wrong results): the lane's patch pixel = its raster index — 32 consecutive pixels per MFMA tile, no +2 step
-  // at a row end, i.e. fragment reads free of LDS bank conflicts whatever the tap: the time the conflicts cost, as an upper bound
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) q0[mi] = (wave * 64 + mi * 32 + l31) & 127;
-#endif
   const int row_step = p.dh * p.pt_Wp;  // patch-pixel offset of tap (kh, kw) = kh*row_step + kw*dw (wave-uniform)
 
   // bf16, one K-group: the accumulators are started by the first stage's MFMAs (zero C operand, stage_mma<..., ZERO>) instead
@@ -328,17 +299,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     int q[MI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) q[mi] = q0[mi] + toffv;
-    if constexpr (BTX_PT_ABL & 2) {  // measurement builds: no fragment reads
-#pragma unroll
-      for (int kk = 0; kk < NG / 2; ++kk) {
-#pragma unroll
-        for (int mi = 0; mi < MIA; ++mi) f.a[kk][mi] = (u32x4){(uint32_t)q[mi], 5u, 1u, 4u};
-        f.wm[kk][0] = f.wm[kk][1] = (u32x4){7u, 7u, 1u, (uint32_t)wsl};
-      }
-#pragma unroll
-      for (int mi = 0; mi < MIA; ++mi) f.sw[mi] = (uint32_t)q[mi];
-      return;
-    }
 #pragma unroll
     for (int kk = 0; kk < NG / 2; ++kk) {
       const int row = 2 * kk + h;
@@ -353,14 +313,11 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     }
   };
 
-  BTX_TR_P(2);  // index arithmetic of the sign and MFMA roles
   if (ncb > 0) {
     write_signs(0, cb0);
-    BTX_TR_P(3);
     // KG == 1: patch of the first block, W(0) and W(1) landed — iteration 0 prefetches the fragments of stage 1; W(2),
     // issued last, may still be in flight.  KG == 2: a stage reads its own fragments: W(1) may be in flight as well.
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)\n\ts_barrier" ::"n"(KG == 1 ? WOPS : 2 * WOPS) : "memory");
-    BTX_TR_P(4);  // first patch + W(0), W(1) landed, all waves met
     Frag fa, fb;
     // The wave's second 32-pixel tile may be pure tile padding (224-pixel tiles: 4 rows of 56, wave 3; 196-pixel tiles:
     // wave 3 as well): its MFMAs, fragment reads and sign masks are skipped — an eighth of the block's matrix work.  The
@@ -370,10 +327,6 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     auto kloop = [&](auto mia_tag) __attribute__((always_inline)) {
     constexpr int MIA = decltype(mia_tag)::value;
     if constexpr (KG == 1) load_frag(fa, 0, 0, 0, mia_tag);
-#ifdef BTX_PT_TRACE
-    tr_t1 = (uint32_t)__builtin_amdgcn_s_memtime();
-    uint32_t tr_tA = tr_t1, tr_ab = 0, tr_lg = 0, tr_bc = 0, tr_cd = 0;
-#endif
     // One channel block = T unrolled stages.  PAR = parity of the block = its patch / sign slot; the fragment register
     // sets alternate per stage (KG == 1), T may be odd, hence two instantiations.  `last` (wave-uniform): no next block.
     auto block = [&](auto par_tag, auto first_tag, int cbi, bool last) __attribute__((always_inline)) {
@@ -390,16 +343,14 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
         asm volatile("" : "+v"(q0[0]), "+v"(q0[1]));
         // 1. W(s+3)
         constexpr int t3 = (t + 3) % T, c3 = (t + 3) / T;
-        if constexpr (!(BTX_PT_ABL & 4)) {
-          if constexpr (c3 == 0) {
-            issue_w((uint32_t)t3, (uint32_t)(cb0 + cbi), (wslot + 3) & 3);
-          } else {
-            if (!last) issue_w((uint32_t)t3, (uint32_t)(cb0 + cbi + 1), (wslot + 3) & 3);
-          }
+        if constexpr (c3 == 0) {
+          issue_w((uint32_t)t3, (uint32_t)(cb0 + cbi), (wslot + 3) & 3);
+        } else {
+          if (!last) issue_w((uint32_t)t3, (uint32_t)(cb0 + cbi + 1), (wslot + 3) & 3);
         }
         // 2. this stage's share of the next block's patch (+ its sign words at the first stage)
         constexpr int KP = tp_pieces<T>(t);
-        if constexpr (t < PST && !(BTX_PT_ABL & 4)) {
+        if constexpr (t < PST) {
           if (!last) {
             const uint32_t cboff = (uint32_t)((cb0 + cbi + 1) * BK * ESZ);
 #pragma unroll
@@ -423,23 +374,8 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
           if constexpr (FIRST && t == 0) stage_mma<PREC, K2, MI, MIA, true, KIND == 1>(cur, df, accm, accd, l31, h);
           else stage_mma<PREC, K2, MI, MIA, false, KIND == 1>(cur, df, accm, accd, l31, h);
           // 5. W(s+2) — and, from stage T-3 on, every piece of the next patch — landed; meet the other waves
-#ifdef BTX_PT_TRACE
-          {  // split the stage end: issue+MFMA | LDS reads back | VMEM wait | barrier
-            __builtin_amdgcn_sched_barrier(0);
-            const uint32_t tB = (uint32_t)__builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const uint32_t tB2 = (uint32_t)__builtin_amdgcn_s_memtime();
-            if (!last) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WOPS + KP) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((c3 == 0) ? WOPS : 0) : "memory");
-            const uint32_t tC = (uint32_t)__builtin_amdgcn_s_memtime();
-            asm volatile("s_barrier" ::: "memory");
-            const uint32_t tD = (uint32_t)__builtin_amdgcn_s_memtime();
-            tr_ab += tB - tr_tA; tr_lg += tB2 - tB; tr_bc += tC - tB2; tr_cd += tD - tC; tr_tA = tD;
-          }
-#else
           if (!last) end_stage<WOPS + KP>();
           else end_stage<(c3 == 0) ? WOPS : 0>();
-#endif
         } else {
           // H1: this stage's own fragments (their latency hides behind the other group's MFMA half)
           load_delta<KIND>(df, smem + PT_W_OFF + wslot * DW_STAGE, l31, h);
@@ -483,25 +419,12 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
       if (cbi < ncb) block(P0{}, std::false_type{}, cbi, true);
     }
     if (KG == 2 && kg == 0) asm volatile("s_barrier" ::: "memory");
-#ifdef BTX_PT_TRACE
-    tr_s[0] = tr_ab; tr_s[1] = tr_lg; tr_s[2] = tr_bc; tr_s[3] = tr_cd;
-#endif
     };  // kloop
     if (mi1_dead) kloop(std::integral_constant<int, 1>{});
     else kloop(std::integral_constant<int, 2>{});
   }
-#ifdef BTX_PT_TRACE
-  tr_t2 = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
 
   // =================== epilogue (btx_epilogue.h) ============================================================
-  if constexpr (BTX_PT_ABL & 32) {  // measurement builds: no store side at all (the accumulators stay live up to here)
-#pragma unroll
-    for (int a = 0; a < MI; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) asm volatile("" ::"v"(accm[a][b]), "v"(accd[a][b]));
-    return;
-  }
   {
     BTX_SECTION_PARAMS(pe, logical2);  // the store side's own reads
     const int nimg = min(pe.pt_G, pe.NB - img0), nrow = min(pe.pt_R, pe.Ho - row0);
@@ -509,47 +432,31 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
     const uint32_t m0 = (uint32_t)(img0 * pe.Ho + row0) * (uint32_t)pe.Wo;
     const PixTall pmt = {pe, row0, col0};
     if constexpr (KG == 1) {
-      if constexpr (DIRECT) {
-        // opaque copies of the thread's ids: without them the compiler computes the store side's lane-dependent addresses
-        // in front of the K loop and keeps them alive across it (the loop then spills)
-        int lane_o = lane, tid_o = tid;
-        asm volatile("" : "+v"(lane_o), "+v"(tid_o));
-        uint32_t gp[2];
-        bool gok[2];
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi) {
-          const int pl = wave * 64 + mi * 32 + (lane_o & 31);
-          if (tall) gp[mi] = pmt(pl, gok[mi]);
-          else { gok[mi] = pl < nvalid; gp[mi] = m0 + (uint32_t)pl; }
+      if constexpr (WIDE) {
+        // the two 64-channel tiles one after the other through the wave's private staging area; the per-channel constants of
+        // BOTH are written first (waves 0 and 1, side by side behind the staging areas: the host reserves 2 KiB there for a
+        // wide launch), so the store side has one workgroup barrier, not three
+        float* const ba0 = (float*)(smem + NW * PT_EP_WAVE);
+        float* const ba1 = ba0 + 4 * BN;
+        {
+          const bool has_bias = (split == 0) && (pe.mu_b != nullptr);
+          const bool has_aff = (pe.ksplits == 1) && ((pe.ep_scale != nullptr) || (pe.ep_shift != nullptr));
+          if (has_bias || has_aff) {
+            if (tid < 64) ep_fill_constants<0>(pe, rl, ba0, tid, 2 * ntile, group, has_bias, has_aff);
+            else if (tid < 128) ep_fill_constants<0>(pe, rl, ba1, tid - 64, 2 * ntile + 1, group, has_bias, has_aff);
+          }
+          __syncthreads();
         }
-        direct_epilogue<KIND>(pe, rl, accm, accd, (float*)smem, tid_o, lane_o, ntile, group, gp, gok);
-      } else {
-        if constexpr (WIDE) {
-          // the two 64-channel tiles one after the other through the wave's private staging area; the per-channel constants of
-          // BOTH are written first (waves 0 and 1, side by side behind the staging areas: the host reserves 2 KiB there for a
-          // wide launch), so the store side has one workgroup barrier, not three
-          float* const ba0 = (float*)(smem + NW * PT_EP_WAVE);
-          float* const ba1 = ba0 + 4 * BN;
-          {
-            const bool has_bias = (split == 0) && (pe.mu_b != nullptr);
-            const bool has_aff = (pe.ksplits == 1) && ((pe.ep_scale != nullptr) || (pe.ep_shift != nullptr));
-            if (has_bias || has_aff) {
-              if (tid < 64) ep_fill_constants<0>(pe, rl, ba0, tid, 2 * ntile, group, has_bias, has_aff);
-              else if (tid < 128) ep_fill_constants<0>(pe, rl, ba1, tid - 64, 2 * ntile + 1, group, has_bias, has_aff);
-            }
-            __syncthreads();
-          }
-          if (tall) {
-            staged_epilogue_pm<0, NW, PixTall>(pe, rl, accm, accm, smem, tid, wave, lane, 2 * ntile, group, split, pmt, nullptr, -1, true, ba0);
-            staged_epilogue_pm<0, NW, PixTall>(pe, rl, accd, accd, smem, tid, wave, lane, 2 * ntile + 1, group, split, pmt, nullptr, -1, true, ba1);
-          } else {
-            staged_epilogue<0, NW>(pe, rl, accm, accm, smem, tid, wave, lane, 2 * ntile, group, split, m0, nvalid, nullptr, -1, true, ba0);
-            staged_epilogue<0, NW>(pe, rl, accd, accd, smem, tid, wave, lane, 2 * ntile + 1, group, split, m0, nvalid, nullptr, -1, true, ba1);
-          }
-        } else
-        if (tall) staged_epilogue_pm<KIND, NW, PixTall>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, pmt);
-        else staged_epilogue<KIND, NW>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, m0, nvalid);
-      }
+        if (tall) {
+          staged_epilogue_pm<0, NW, PixTall>(pe, rl, accm, accm, smem, tid, wave, lane, 2 * ntile, group, split, pmt, -1, true, ba0);
+          staged_epilogue_pm<0, NW, PixTall>(pe, rl, accd, accd, smem, tid, wave, lane, 2 * ntile + 1, group, split, pmt, -1, true, ba1);
+        } else {
+          staged_epilogue<0, NW>(pe, rl, accm, accm, smem, tid, wave, lane, 2 * ntile, group, split, m0, nvalid, -1, true, ba0);
+          staged_epilogue<0, NW>(pe, rl, accd, accd, smem, tid, wave, lane, 2 * ntile + 1, group, split, m0, nvalid, -1, true, ba1);
+        }
+      } else
+      if (tall) staged_epilogue_pm<KIND, NW, PixTall>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, pmt);
+      else staged_epilogue<KIND, NW>(pe, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, m0, nvalid);
     } else {
       // Every wave is behind the barrier of its last stage: the whole LDS is free.  Group 1 -> exchange area
       // [chunk i][thread] x 16 B (a wave writes 1 KiB per instruction; 128 KiB Flipout, 64 KiB Reparameterization),
@@ -597,27 +504,13 @@ __global__ __launch_bounds__(256 * KG, 2) void contract_taps_kernel(const Contra
       }
       __syncthreads();  // the staging area of the store overlaps the exchange area
       if (kg == 0) {
-        if (tall) staged_epilogue_pm<KIND, NW, PixTall>(pe, rl, accm, accd, smem_all, tid, wave, lane, ntile, group, split, pmt,
-                                                        nullptr, -1, true, ba_lds);
-        else staged_epilogue<KIND, NW>(pe, rl, accm, accd, smem_all, tid, wave, lane, ntile, group, split, m0, nvalid, nullptr,
-                                       -1, true, ba_lds);
+        if (tall) staged_epilogue_pm<KIND, NW, PixTall>(pe, rl, accm, accd, smem_all, tid, wave, lane, ntile, group, split, pmt, -1,
+                                                        true, ba_lds);
+        else staged_epilogue<KIND, NW>(pe, rl, accm, accd, smem_all, tid, wave, lane, ntile, group, split, m0, nvalid, -1, true,
+                                       ba_lds);
       }
     }
   }
-#ifdef BTX_PT_TRACE
-  if (p.trace) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const uint32_t tr_t3 = (uint32_t)__builtin_amdgcn_s_memtime();
-    if (lane == 0) {
-      uint32_t* tr = (uint32_t*)p.trace + (size_t)(blockIdx.x * NW * KG + wave_all) * 8;
-      tr[0] = tr_t1 - tr_t0; tr[1] = tr_t2 - tr_t1; tr[2] = (uint32_t)__builtin_amdgcn_s_memrealtime() - tr_r0; tr[3] = 0;
-      tr[4] = tr_t3 - tr_t2; tr[5] = tr_t3 - tr_t0;
-      if (p.pt_tune & 64) { tr[0] = tr_s[0]; tr[1] = tr_s[1]; tr[3] = tr_s[2]; tr[4] = tr_s[3]; }  // stage split instead
-      if (p.pt_tune & 128) { tr[0] = tr_p[0] - tr_t0; tr[1] = tr_p[1] - tr_t0; tr[2] = tr_p[2] - tr_t0; tr[3] = tr_p[3] - tr_t0; tr[4] = tr_p[4] - tr_t0; tr[5] = tr_t1 - tr_t0; }
-      tr[6] = tr_t0; tr[7] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
-    }
-  }
-#endif
 }
 
 }  // namespace btx

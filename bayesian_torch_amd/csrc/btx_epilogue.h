@@ -13,12 +13,6 @@
 #pragma once
 #include <type_traits>
 #include "btx_contract.h"
-#ifndef BTX_PT_ABL
-#define BTX_PT_ABL 0
-#endif
-#ifndef BTX_EP_PRED_STORES
-#define BTX_EP_PRED_STORES 0  // A/B: 1 = the bf16 stores of stage 2 under `if (pixel exists)` again (rounds 1-5)
-#endif
 
 namespace btx {
 
@@ -166,7 +160,7 @@ template <int KIND, int NW, class PM = PixContig, bool RES_PRE = false, class HO
 __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, const RngLive& rl, const f32x16 (&accm)[2][2],
                                                    const f32x16 (&accd)[2][2], unsigned char* smem, int tid, int wave,
                                                    int lane, int ntile, int group, int split, const PM& pm,
-                                                   uint32_t* ep_t = nullptr, int pwave = -1, bool first = true,
+                                                   int pwave = -1, bool first = true,
                                                    float* ba_ext = nullptr, const HOOK& hook = HOOK{},
                                                    const uint32_t* wsh_ext = nullptr) {
   // wsh_ext: the four hashed s_out words of the lane's fragment blocks ([mi][ni], already shifted by 2h), computed by the
@@ -298,15 +292,9 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
         }
       });
     };
-#ifdef BTX_EP_TRACE2
-    if (ep_t) { __builtin_amdgcn_sched_barrier(0); ep_t[2] = (uint32_t)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-#endif
     if (has_bias) body(std::true_type{}, std::true_type{});
     else if (has_ba) body(std::false_type{}, std::true_type{});
     else body(std::false_type{}, std::false_type{});
-#ifdef BTX_EP_TRACE2
-    if (ep_t) { __builtin_amdgcn_sched_barrier(0); ep_t[3] = (uint32_t)__builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-#endif
   } else {
     // generic path: ragged channel tiles, unaligned s_out words, explicit sign arrays (parity mode)
 #pragma unroll 1
@@ -349,9 +337,6 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
       }
     }
   }
-#ifdef BTX_EP_TRACE
-  if (ep_t) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); ep_t[0] = (uint32_t)__builtin_amdgcn_s_memtime(); }
-#endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the staging area is private to the wave
   __builtin_amdgcn_sched_barrier(0);  // nothing of stage 2 (index arithmetic) above this line: the accumulators are dead only now
 
@@ -430,7 +415,7 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
           }
-          if constexpr (OUTK == 1 && !BUFIO && !(BTX_PT_ABL & 64) && !BTX_EP_PRED_STORES) {
+          if constexpr (OUTK == 1 && !BUFIO) {
             // bf16 outputs: the store is a buffer store whose offset is out of the descriptor's range for a pixel that does not
             // exist (dropped by the hardware) — no exec-mask block per store.  Under `if (pk[i])` each of the lane's eight stores
             // sat in a basic block of its own together with its ReLU / rounding arithmetic (s_and_saveexec .. s_or exec around
@@ -455,8 +440,6 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
                 const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, io_bytes, 0x00020000);
                 __builtin_amdgcn_raw_buffer_store_b128((u32x4){p0[0], p0[1], p1[0], p1[1]}, out_rsrc, io_voff,
                                                        io_step * (uint32_t)(hf * NP + i), 0);
-              } else if constexpr (BTX_PT_ABL & 64) {  // measurement builds: everything but the store itself
-                asm volatile("" ::"v"(p0), "v"(p1), "v"(idx[i]));
               } else {
                 *(u32x4*)((__bf16*)p.out + idx[i]) = (u32x4){p0[0], p0[1], p1[0], p1[1]};
               }
@@ -506,156 +489,6 @@ __device__ __forceinline__ void staged_epilogue_pm(const ContractParams& p, cons
       }
     }
   }
-#ifdef BTX_EP_TRACE
-  if (ep_t) { __builtin_amdgcn_sched_barrier(0); ep_t[1] = (uint32_t)__builtin_amdgcn_s_memtime(); }
-#endif
-}
-
-// ---- the store side straight from the fragment registers (bf16 outputs, whole aligned 64-channel tiles) -----------------
-// No staging through LDS: bias + Flipout combine fold the delta accumulators into the mean ones in place, the affine runs on
-// the lane's 4-channel runs, v_permlane32_swap pairs the two half-waves' runs into one 8-channel run per lane, then residual,
-// ReLU, rounding and ONE 16-byte buffer store per (pixel, 16 channels) — the 2 lanes of a pixel write 32 contiguous bytes,
-// four store instructions complete its 128-byte line in L2.  A lane addresses its two pixels directly (gp = pm(pixel)), so
-// tiles whose pixels are not consecutive output pixels (the tall strips of btx_contract_taps.h) cost two divisions per lane
-// instead of a (row, column) walk per stored pixel.  First written for the persistent kernel (btx_contract_taps3.h: ~2k
-// cycles against the 4.8k of the staged store of a 56x56 tile, 8.1k for a tall strip; profiles/r03_phase_timers.txt).
-// Contract: as staged_epilogue_pm, plus: ksplits == 1, outputs bf16, N % 32 == 0, (group * Ng) % 32 == 0, the tile's 64
-// channels exist, hashed s_out, M * N * 2 < 0x7ff00000 (32-bit offsets with an out-of-range value to spare): the host sets
-// ContractParams.ep_direct only then.
-// gp[mi] / gok[mi]: output pixel index of the lane's pixel (wave * 64 + mi * 32 + lane % 32) of the tile, and whether it exists
-// (the caller evaluates its pixel map — PixContig or PixTall — so that this body exists ONCE per kernel: with one copy per
-// map behind a run-time branch the compiler hoists the copies' common sign-word shifts above the branch and spills them).
-// OUT: the output element type (bf16: one 16-byte store per (pixel, 16 channels); float: two).  FILLED: the caller has
-// written the tile's constants to ba_lds (ep_fill_constants) and passed a barrier since — else this call does both.
-template <int KIND, typename OUT = __bf16, bool FILLED = false>
-__device__ __forceinline__ void direct_epilogue(const ContractParams& p, const RngLive& rl, const f32x16 (&accm)[2][2],
-                                                const f32x16 (&accd)[2][2], float* ba_lds, int tid, int lane,
-                                                int ntile, int group, const uint32_t (&gp)[2], const bool (&gok)[2]) {
-  constexpr bool BF = sizeof(OUT) == 2;
-  constexpr uint32_t ESZ = (uint32_t)sizeof(OUT);
-  const int h = lane >> 5;
-  const bool has_bias = p.mu_b != nullptr;
-  const bool has_aff = (p.ep_scale != nullptr) || (p.ep_shift != nullptr);
-  // ba_lds: [bias mean | bias delta | scale | shift] x 64, identities where absent
-  if constexpr (!FILLED) ep_fill_constants<KIND>(p, rl, ba_lds, tid, ntile, group, has_bias, has_aff);
-  const uint32_t cbase = (uint32_t)(group * p.Ng + ntile * BN);
-  const uint32_t out_bytes = (uint32_t)p.M * (uint32_t)p.N * ESZ;
-  const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.out, 0, out_bytes, 0x00020000);
-  uint32_t eo[2];  // byte offset of the lane's 8-channel run of (pixel mi, half 0, pair 0); a pixel that does not exist
-#pragma unroll     // gets an out-of-range offset: its loads return zeros, its stores are dropped
-  for (int mi = 0; mi < 2; ++mi) eo[mi] = gok[mi] ? (gp[mi] * (uint32_t)p.N + cbase + 8u * (uint32_t)h) * ESZ : 0x80000000u;
-  const bool res = p.ep_res != nullptr;
-  const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.ep_res, 0, res ? out_bytes : 0u, 0x00020000);
-  // residual rows of pixel mi: (32-channel half ni) x (16-channel pair k) -> 8 channels of this lane (16 | 32 bytes)
-  struct Res { u32x4 a[2][2], b[2][2]; };
-  auto load_res = [&](Res& r, int mi) __attribute__((always_inline)) {
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {  // (no residual: a zero-length descriptor, the loads return zeros without a memory access)
-        const uint32_t o = eo[mi] + (uint32_t)(ni * 32 + 16 * k) * ESZ;
-        r.a[ni][k] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, o, 0, 0);
-        if constexpr (!BF) r.b[ni][k] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, o + 16u, 0, 0);
-      }
-  };
-  uint32_t wsh[2][2];
-  if constexpr (KIND == 1) {
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-      const uint32_t orow = gp[mi] * (uint32_t)p.N + cbase;
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) wsh[mi][ni] = btx_sign_word((orow + 32u * ni) >> 5, rl.kout_a, rl.kout_b) << (2 * h);
-    }
-  }
-  uint32_t SB = 0x80000000u;
-  asm volatile("" : "+s"(SB));
-  // ReLU as a lower bound: one instruction stream for both.  (ReLU6, BtxEpilogue.relu == 2, never gets here: the host sets
-  // ContractParams.ep_direct only for relu 0 / 1, and the staged store side applies the upper bound.)
-  const float lowb = p.ep_relu ? 0.f : -__builtin_inff();
-  if constexpr (!FILLED) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // the constants are in LDS
-  // Phase A — (mean + bias) + s_out * (delta + bias delta) -> o (scalars, not the MFMA tuples: written back in place, the
-  // partially updated 16-register tuples made the allocator copy and spill).  ONE instantiation: without a bias the
-  // constants are zeros (16 LDS reads, 128 additions).
-  float o[2][2][16];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int cl = ni * 32 + 8 * q + 4 * h;
-      const f32x4 bm = *(const f32x4*)(ba_lds + cl);
-      const f32x4 bd = *(const f32x4*)(ba_lds + BN + cl);
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          float val = accm[mi][ni][4 * q + rr] + bm[rr];
-          if constexpr (KIND == 1) {
-            const float dl = accd[mi][ni][4 * q + rr] + bd[rr];
-            const int sft = 31 - (((rr & 1) ? 31 : 15) - 4 * q - (rr >> 1));
-            val += u2f(__builtin_amdgcn_bitop3_b32(f2u(dl), wsh[mi][ni] << sft, SB, 0x78));  // dl ^ (w & SB)
-          }
-          o[mi][ni][4 * q + rr] = val;
-        }
-#ifndef BTX_DIRECT_NO_FOLD_FENCE
-      __builtin_amdgcn_sched_barrier(0);  // one (ni, q) group at a time: left alone the scheduler requests the constants of
-#endif                                    // all eight groups up front (64 registers) and the fold's results go to scratch
-    }
-  __builtin_amdgcn_sched_barrier(0);
-  // Phase B — one (pixel mi, 32-channel half ni, 16-channel pair k) group at a time: affine, pairing, residual, ReLU, store
-  Res rv, rnx;
-  load_res(rv, 0);  // (behind the fold: in front of it these registers push the fold's results into scratch)
-  struct Cst { f32x4 sc[2], sh[2]; };
-  auto load_cst = [&](Cst& c, int ni, int k) __attribute__((always_inline)) {
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int cl = ni * 32 + 8 * (2 * k + hf) + 4 * h;
-      c.sc[hf] = *(const f32x4*)(ba_lds + 2 * BN + cl);
-      c.sh[hf] = *(const f32x4*)(ba_lds + 3 * BN + cl);
-    }
-  };
-  Cst cst[2];
-  load_cst(cst[0], 0, 0);
-  static_for_ep<0, 8>([&](auto g_tag) __attribute__((always_inline)) {
-    constexpr int g = decltype(g_tag)::value;
-    constexpr int mi = g >> 2, ni = (g >> 1) & 1, k = g & 1;
-    if constexpr (g + 1 < 8) load_cst(cst[(g + 1) & 1], ((g + 1) >> 1) & 1, (g + 1) & 1);
-    if constexpr (g == 0) load_res(rnx, 1);  // pixel 1's residual rows land while pixel 0 is stored
-    const Cst& c = cst[g & 1];
-    float t[2][4];
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) t[hf][rr] = __builtin_fmaf(o[mi][ni][4 * (2 * k + hf) + rr], c.sc[hf][rr], c.sh[hf][rr]);
-    float v[8];
-#pragma unroll
-    for (int rr = 0; rr < 4; ++rr) {
-      const auto r = __builtin_amdgcn_permlane32_swap(f2u(t[0][rr]), f2u(t[1][rr]), false, false);
-      v[rr] = u2f(r[0]);
-      v[4 + rr] = u2f(r[1]);
-    }
-    const Res& rr_ = (mi == 0) ? rv : rnx;
-    if constexpr (BF) {
-      const u32x4 rw = rr_.a[ni][k];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[2 * j] += u2f(rw[j] << 16); v[2 * j + 1] += u2f(rw[j] & 0xffff0000u); }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += u2f(rr_.a[ni][k][j]); v[4 + j] += u2f(rr_.b[ni][k][j]); }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], lowb);
-    const uint32_t so = eo[mi] + (uint32_t)(ni * 32 + 16 * k) * ESZ;
-    if constexpr (BF) {
-      const f32x4 x0 = {v[0], v[1], v[2], v[3]}, x1 = {v[4], v[5], v[6], v[7]};
-      const u32x2 p0 = __builtin_bit_cast(u32x2, __builtin_convertvector(x0, bf16x4));
-      const u32x2 p1 = __builtin_bit_cast(u32x2, __builtin_convertvector(x1, bf16x4));
-      __builtin_amdgcn_raw_buffer_store_b128((u32x4){p0[0], p0[1], p1[0], p1[1]}, out_rsrc, so, 0, 0);
-    } else {
-      __builtin_amdgcn_raw_buffer_store_b128((u32x4){f2u(v[0]), f2u(v[1]), f2u(v[2]), f2u(v[3])}, out_rsrc, so, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128((u32x4){f2u(v[4]), f2u(v[5]), f2u(v[6]), f2u(v[7])}, out_rsrc, so + 16u, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  });
 }
 
 // the contiguous-tile form every other kernel uses
@@ -663,11 +496,10 @@ template <int KIND, int NW, bool RES_PRE = false>
 __device__ __forceinline__ void staged_epilogue(const ContractParams& p, const RngLive& rl, const f32x16 (&accm)[2][2],
                                                 const f32x16 (&accd)[2][2], unsigned char* smem, int tid, int wave,
                                                 int lane, int ntile, int group, int split, uint32_t m0, int nvalid,
-                                                uint32_t* ep_t = nullptr, int pwave = -1, bool first = true,
-                                                float* ba_ext = nullptr) {
+                                                int pwave = -1, bool first = true, float* ba_ext = nullptr) {
   const PixContig pm = {m0, nvalid};
-  staged_epilogue_pm<KIND, NW, PixContig, RES_PRE>(p, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, pm, ep_t, pwave,
-                                                   first, ba_ext);
+  staged_epilogue_pm<KIND, NW, PixContig, RES_PRE>(p, rl, accm, accd, smem, tid, wave, lane, ntile, group, split, pm, pwave, first,
+                                                   ba_ext);
 }
 
 }  // namespace btx

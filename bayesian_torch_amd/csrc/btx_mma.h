@@ -2,10 +2,6 @@
 #pragma once
 #include "btx_contract.h"
 
-#ifndef BTX_PT_ABL
-#define BTX_PT_ABL 0  // measurement-only ablation bits: 1 no MFMA, 2 no LDS fragment reads, 4 no DMA in the loop,
-#endif                // 8 no per-stage barrier, 16 no sign masks, 32 no epilogue
-
 namespace btx {
 
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -58,16 +54,11 @@ struct DeltaFrag {
 template <int KIND>
 __device__ __forceinline__ void load_delta(DeltaFrag& d, const unsigned char* ws, int l31, int h) {
   if constexpr (KIND == 1) {
-    if constexpr (BTX_PT_ABL & 2) {
 #pragma unroll
-      for (int kk = 0; kk < NG / 2; ++kk) d.w[kk][0] = d.w[kk][1] = (u32x4){7u, 7u, 1u, 4u};
-    } else {
+    for (int kk = 0; kk < NG / 2; ++kk)
 #pragma unroll
-      for (int kk = 0; kk < NG / 2; ++kk)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          d.w[kk][ni] = *(const u32x4*)(ws + NG * BN * 16 + ((2 * kk + h) * BN + ni * 32 + l31) * 16);
-    }
+      for (int ni = 0; ni < 2; ++ni)
+        d.w[kk][ni] = *(const u32x4*)(ws + NG * BN * 16 + ((2 * kk + h) * BN + ni * 32 + l31) * 16);
   }
 }
 
@@ -83,9 +74,6 @@ template <int PREC, int KIND, int MI = 2, int MIA = MI, bool ZERO = false, bool 
 __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& dfrag, f32x16 (&accm)[MI][2],
                                           f32x16 (&accd)[MI][2], int l31, int h) {
     const u32x4 (&wd)[NG / 2][2] = dfrag.w;
-#ifdef BTX_MMA_PRIO
-    __builtin_amdgcn_s_setprio(BTX_MMA_PRIO);
-#endif
     if constexpr (PREC == 2) {
       static_assert(NG == 4, "split-bf16: one 32x32x16 K-step per 16-k stage");
       // weight fragments: granule = [hi k0..3 | lo k0..3]; rows h and 2+h make the lane's 8 k
@@ -120,9 +108,6 @@ __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& df
           for (int mi = 0; mi < MIA; ++mi) accd[mi][ni] = mfma3(dh, dl, ah[mi], al[mi], accd[mi][ni]);
         }
       }
-#ifdef BTX_MMA_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       return;
     }
 #pragma unroll
@@ -132,8 +117,7 @@ __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& df
         for (int mi = 0; mi < MIA; ++mi)
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni) {
-            if constexpr (BTX_PT_ABL & 1) { asm volatile("" ::"v"(f.wm[kk][ni]), "v"(f.a[kk][mi])); accm[mi][ni][0] += 1.f; }
-            else if constexpr (ZERO) {
+            if constexpr (ZERO) {
               const f32x16 zc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
               accm[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                   __builtin_bit_cast(bf16x8, f.wm[kk][ni]), __builtin_bit_cast(bf16x8, f.a[kk][mi]), kk == 0 ? zc : accm[mi][ni], 0, 0, 0);
@@ -155,7 +139,7 @@ __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& df
       for (int kk = 0; kk < NG / 2; ++kk) {
         const int row = 2 * kk + h;
         if constexpr (PREC == 1) {
-          if constexpr (MASK && !(BTX_PT_ABL & 16)) {
+          if constexpr (MASK) {
 #pragma unroll
             for (int mi = 0; mi < MIA; ++mi) {
               const uint32_t swr = f.sw[mi] << (4 * row);
@@ -167,8 +151,7 @@ __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& df
           for (int mi = 0; mi < MIA; ++mi)
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) {
-              if constexpr (BTX_PT_ABL & 1) { asm volatile("" ::"v"(wd[kk][ni]), "v"(f.a[kk][mi])); accd[mi][ni][0] += 1.f; }
-              else if constexpr (ZERO) {
+              if constexpr (ZERO) {
                 const f32x16 zc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                 accd[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                     __builtin_bit_cast(bf16x8, wd[kk][ni]), __builtin_bit_cast(bf16x8, f.a[kk][mi]), kk == 0 ? zc : accd[mi][ni], 0, 0, 0);
@@ -192,9 +175,6 @@ __device__ __forceinline__ void stage_mma(StageFragT<MI>& f, const DeltaFrag& df
         }
       }
     }
-#ifdef BTX_MMA_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 }  // namespace btx

@@ -50,7 +50,6 @@ struct WgradParams {
   const uint32_t* sample_ptr;  // BtxRng.sample_idx_dev: the sign keys are then derived on the device (captured training steps)
   uint32_t seed_lo, seed_hi, layer;
   int swap;
-  int tune;     // measurement builds (BTX_WGRAD_T3_ABL): 1 = no slab stores, 2 = no MFMA section (results wrong: time only)
   int pair, Tw; // pair: a tap has 32 channels (row-fused stems) — a workgroup takes TWO taps, one per 32-column half of its x tile, and
                 // shares the dy tile between them (Tw = workgroups along the tap axis: ceil(T / 2), else T)
   int direct;   // slab mode with ONE chunk: its sums are the result — plain stores straight into dW, no reduction launch
@@ -593,15 +592,6 @@ __global__ __launch_bounds__(256) void wgrad_rho_kernel(const float* dw, size_t 
   }
 }
 
-static inline const char* wg_tune_env(const char* name) {
-#if defined(BTX_TUNING) || defined(BTX_PT_TRACE)
-  return getenv(name);
-#else
-  (void)name;
-  return nullptr;
-#endif
-}
-
 // the pixel chunking of the two kernels (shared by btx_wgrad_workspace_bytes and the launch).  Atomics path (rounds 2-5): about
 // `target_wgs` workgroups.  Slab paths: at most `target_wgs` = the workgroups the chip holds at once (one round: a second, partly
 // filled round costs a whole round's prologue, epilogue and slab; profiles/r05_experiments.txt E13), a single chunk when one
@@ -616,14 +606,9 @@ void wgrad_chunks(long long base, long long M, long long target_wgs, bool round_
   *cpx_out = cpx;
 }
 long long wgrad_target_wgs(bool slab) {
-  const char* e = wg_tune_env(slab ? "BTX_WGRAD_SLAB_WGS" : "BTX_WGRAD_WGS");
-  return e ? atoll(e) : (slab ? 512 : 2048);  // slabs: two 4-wave workgroups per CU
+  return slab ? 512 : 2048;  // slabs: two 4-wave workgroups per CU
 }
-bool wgrad_pair_geom() { return wg_tune_env("BTX_WGRAD_NO_PAIR") == nullptr; }
-long long wgrad_taps3_target_wgs() {
-  const char* e = wg_tune_env("BTX_WGRAD_T3_WGS");
-  return e ? atoll(e) : 256;  // one 12-wave workgroup per CU
-}
+constexpr long long WGRAD_TAPS3_TARGET_WGS = 256;  // one 12-wave workgroup per CU
 
 int wgrad_fill_params(int kind, const BtxGeom* g, const void* x, const void* dy, const BtxNoise* noise, uint32_t flags, WgradParams& p) {
   if (flags & BTX_FLAG_TRANSPOSED) return BTX_E_UNSUPPORTED;  // transposed layers: swap x and dy (host)
@@ -655,7 +640,7 @@ int wgrad_fill_params(int kind, const BtxGeom* g, const void* x, const void* dy,
 bool wgrad_taps3_geom(const WgradParams& p, int act_dtype) {
   return act_dtype == BTX_ACT_BF16 && p.groups == 1 && p.D == 1 && p.KD == 1 && p.KH == 3 && p.KW == 3 && p.sh == 1 && p.sw == 1 &&
          p.ph == 1 && p.pw == 1 && p.dh == 1 && p.dw == 1 && p.Ho == p.H && p.Wo == p.W && p.W >= 2 && p.W <= 63 && p.H >= 2 &&
-         (p.C % 64) == 0 && (p.N % 64) == 0 && !wg_tune_env("BTX_WGRAD_NO_TAPS3");
+         (p.C % 64) == 0 && (p.N % 64) == 0;
 }
 
 int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float* dw_mu, float* dw_delta, float* db_mu, float* db_delta,
@@ -685,11 +670,11 @@ int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float*
                        !p.sign_in && !p.sign_out && ((((uintptr_t)x) | ((uintptr_t)dy)) % 16 == 0);
   // a tap of 32 channels (row-fused 7x7x3 stems: 8 columns x 4 channels) fills half of the 64-column x tile: two taps per workgroup,
   // one dy tile for both (the kernel is bound by its loads per MFMA; profiles/r05_experiments.txt E16)
-  p.pair = (!taps3 && fast_ok && p.Cg == 32 && p.T >= 2 && wgrad_pair_geom()) ? 1 : 0;
+  p.pair = (!taps3 && fast_ok && p.Cg == 32 && p.T >= 2) ? 1 : 0;
   p.Tw = p.pair ? (p.T + 1) / 2 : p.T;
   const long long base = taps3 ? (long long)p.ntiles * p.ctiles : (long long)p.groups * p.ntiles * p.ctiles * p.Tw;
   long long chunks, cpx;
-  wgrad_chunks(base, M, taps3 ? wgrad_taps3_target_wgs() : wgrad_target_wgs(slab), slab, &chunks, &cpx);
+  wgrad_chunks(base, M, taps3 ? WGRAD_TAPS3_TARGET_WGS : wgrad_target_wgs(slab), slab, &chunks, &cpx);
   p.chunks = (int)chunks; p.chunk_px = (int)cpx;
   if (base * chunks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
   if (slab && (size_t)chunks * nk * E * sizeof(float) > ws_bytes) return BTX_E_WORKSPACE;
@@ -699,7 +684,6 @@ int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float*
   sign_keys_host(rng, swap ? BTX_STREAM_SIGN_IN : BTX_STREAM_SIGN_OUT, &p.kout_a, &p.kout_b);
   p.sample_ptr = rng->sample_idx_dev; p.seed_lo = (uint32_t)rng->seed; p.seed_hi = (uint32_t)(rng->seed >> 32); p.layer = rng->layer_id;
   p.swap = swap ? 1 : 0;
-  { const char* tn = wg_tune_env("BTX_WGRAD_T3_ABL"); p.tune = tn ? atoi(tn) : 0; }
   p.fd_Wo = make_fastdiv((uint32_t)p.Wo); p.fd_Ho = make_fastdiv((uint32_t)p.Ho); p.fd_Do = make_fastdiv((uint32_t)p.Do);
   p.fd_T = make_fastdiv((uint32_t)p.Tw); p.fd_ctiles = make_fastdiv((uint32_t)p.ctiles);
   p.fd_ntiles = make_fastdiv((uint32_t)p.ntiles); p.fd_groups = make_fastdiv((uint32_t)p.groups);
@@ -808,7 +792,7 @@ extern "C" size_t btx_wgrad_workspace_bytes(int kind, const BtxGeom* g, int act_
     if (chunks > most) most = chunks;
   }
   if (wgrad_taps3_geom(p, act_dtype)) {
-    wgrad_chunks((long long)p.ntiles * p.ctiles, p.M, wgrad_taps3_target_wgs(), true, &chunks, &cpx);
+    wgrad_chunks((long long)p.ntiles * p.ctiles, p.M, WGRAD_TAPS3_TARGET_WGS, true, &chunks, &cpx);
     if (chunks > most) most = chunks;
   }
   return (size_t)most * nk * E * sizeof(float);

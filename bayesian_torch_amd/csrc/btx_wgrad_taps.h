@@ -190,9 +190,6 @@ __global__ __launch_bounds__(KIND == 1 ? 768 : 384) void wgrad_taps3_kernel(cons
       fetch_x(m0 + 128, nx);
     }
     const int ytile = L::y(kind, buf) + g16 * T3_YBLK + (8 * hk + rsel) * 32 + csel;
-#if defined(BTX_TUNING)
-    if (!(p.tune & 2))
-#endif
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       bf16x8 a[2], b[3];
@@ -240,9 +237,6 @@ __global__ __launch_bounds__(KIND == 1 ? 768 : 384) void wgrad_taps3_kernel(cons
   // ---- the chunk's partial sums: C/D layout of 32x32 MFMAs, reg r of lane (l31, hk) = D[n = (r&3) + 8 (r>>2) + 4 hk][c = l31]
   const size_t E = (size_t)p.N * 9 * p.C;
   float* slab = p.direct ? (kind ? p.dwd : p.dwm) : p.slab + ((size_t)chunk * NK + kind) * E;
-#if defined(BTX_TUNING)
-  if (p.tune & 1) return;
-#endif
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -34,8 +34,8 @@ def get_precision():
 
 
 # Successive contraction launches walk their tiles in alternating directions (BTX_FLAG_REVERSE on every other call): a
-# layer then starts on the activations its producer wrote last.  Values do not depend on it.  BTX_ALT_ORDER=0 disables (A/B).
-_ALT_ORDER = os.environ.get("BTX_ALT_ORDER", "1") != "0"
+# layer then starts on the activations its producer wrote last.  Values do not depend on it.
+_ALT_ORDER = True
 _ORDER_TOGGLE = [0]
 _OUT_LAYOUT = "channels_last"
 _CONCURRENT = False  # set by mc.GraphedMC(lanes > 1) while it captures: BTX_FLAG_CONCURRENT on every contraction launch

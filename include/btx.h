@@ -272,7 +272,6 @@ int btx_contract_fwd_lanes(int kind, const BtxGeom* g,
 #define BTX_FAMILY_TAPS2     6  /* tap-unrolled 3x3 stride-2 kernel (btx_contract_taps2.h) */
 #define BTX_FAMILY_STEM      7  /* row-fused stem (btx_contract_stem.h) */
 #define BTX_FAMILY_STEM_POOL 8  /* row-fused stem + max-pool (btx_contract_stempool.h) */
-#define BTX_FAMILY_PW        9  /* pointwise Flipout-GEMM (tuning builds only) */
 typedef struct BtxPlanInfo {
   int32_t  family;     /* BTX_FAMILY_* */
   int32_t  ksplits;    /* K splits (> 1: partial sums in the workspace + one reduce launch) */

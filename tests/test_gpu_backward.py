@@ -368,7 +368,7 @@ BN_CASES = [((8, 64, 56, 56), torch.float32, 2e-5), ((64, 64, 56, 56), torch.bfl
 def test_hip_batchnorm_training_matches_torch(shape, dtype, tol):
     """BatchNorm in training mode on channels-last activations: y, running_mean / running_var / num_batches_tracked, dx, dgamma,
     dbeta against torch.nn.BatchNorm evaluated in FLOAT64 on the same, dtype-rounded, inputs (torch's own f32 kernel loses the
-    variance of a channel whose mean dwarfs its spread — 6e-3 on the +300 channels below, tools/r05_experiments/bn_diag.py — the
+    variance of a channel whose mean dwarfs its spread — 6e-3 on the +300 channels below — the
     shifted sums of btx_bn.hip do not: 1e-7).  bf16: outputs are rounded once to bf16 (bar 1e-2 rel-L2, measured ~2e-3); f32: 2e-5."""
     from bayesian_torch_amd.models.fuse import hip_batchnorm
     from bayesian_torch_amd import autograd as ag

@@ -110,8 +110,8 @@ FUSED_CASES = [
     ("Conv2dFlipout", dict(in_channels=32, out_channels=64, kernel_size=3, stride=2, padding=1), (2, 32, 51, 37)),
     ("Conv2dReparameterization", dict(in_channels=64, out_channels=64, kernel_size=3, stride=2, padding=1, groups=2), (5, 64, 13, 18)),
     ("Conv2dFlipout", dict(in_channels=32, out_channels=32, kernel_size=3, stride=2, padding=1), (1, 32, 2, 2)),
-    # pointwise Flipout-GEMM (btx_contract_pw.h: 1x1 / stride 1 / no padding and Linear with N % 64 == 0): resident and
-    # streamed activation stages, several n-tiles per workgroup, n-tile chunks, ragged pixel tiles, bias, groups
+    # pointwise shapes (1x1 / stride 1 / no padding): the pointwise form of the LDS-DMA kernel and, for Flipout with a long K,
+    # the 8-wave GEMM (btx_contract_gemm8.h): resident and streamed activation stages, ragged pixel tiles, bias, groups
     ("Conv2dFlipout", dict(in_channels=64, out_channels=256, kernel_size=1, bias=False), (3, 64, 19, 17)),
     ("Conv2dFlipout", dict(in_channels=256, out_channels=64, kernel_size=1), (2, 256, 14, 14)),
     ("Conv2dFlipout", dict(in_channels=128, out_channels=512, kernel_size=1, bias=False), (2, 128, 28, 28)),

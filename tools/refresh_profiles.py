@@ -10,15 +10,10 @@ steps (each writes the files named in its docstring, with the command that produ
   pmc         profiles/<PREFIX>_pmc_taps_lanes.txt                          SQ counters of contract_taps_kernel, many-tiles regime
   cfg3        profiles/<PREFIX>_cfg3_kernel_trace_stats.txt, _cfg3_pmc_taps.txt, _cfg3_bench_line.json   BASELINE cfg3 (Reparameterization):
                                                                             kernel trace of its bench command, SQ counters of its wide kernel
-  phase       profiles/<PREFIX>_phase_timers.txt, r03_phase_timers_sustained.txt   block phase timers (trace build)
-  ablation    profiles/<PREFIX>_kloop_ablation.txt                          what the K loop pays for (ablation builds)
   ubench      profiles/<PREFIX>_mfma_mix_ubench.txt                         tools/ubench/mfma_mix.hip
-  persistent  profiles/<PREFIX>_persistent_kbench.txt                       persistent kernel A/B (tuning build)
-  tall        profiles/<PREFIX>_tall_tiles_ab.txt                           tall-strip tiles A/B
   power       profiles/<PREFIX>_power_probe.txt                             socket power / clock under sustained launches
   train       profiles/<PREFIX>_train_step_captured_trace.txt               kernel trace of the captured training step
   wgrad       profiles/<PREFIX>_wgrad_bench.txt, _dgrad_bench.txt           weight-gradient paths / stride-2 data gradients per layer
-The measurement builds (build_variants/libbtx_{tune,trace,abl*}.so) are made by tools/build_variants.sh when missing.
 """
 import glob
 import json
@@ -43,13 +38,6 @@ def write(name, header, body):
     os.makedirs(OUT, exist_ok=True)
     open(os.path.join(OUT, name), "w").write("".join("# " + l + "\n" for l in header.strip().splitlines()) + body)
     print("wrote", os.path.join("gpurun_out/profiles", name))
-
-
-def variant(name, flags):
-    so = os.path.join(ROOT, "build_variants", "libbtx_%s.so" % name)
-    if not os.path.exists(so):
-        print(sh("bash tools/build_variants.sh %s '%s'" % (name, flags), timeout=3000))
-    return so
 
 
 def step_bench():
@@ -116,13 +104,12 @@ def step_train():
 
 def step_wgrad():
     """profiles/<PREFIX>_wgrad_bench.txt, _dgrad_bench.txt: the weight-gradient paths and the stride-2 data gradients, layer by layer"""
-    lib = variant("tune", "-DBTX_TUNING")
-    write(PREFIX + "_wgrad_bench.txt", "BTX_LIB=build_variants/libbtx_tune.so python tools/wgrad_bench.py --ablate   (1 MI355X; columns: btx_contract_wgrad with f32\n"
-          "atomics | btx_contract_wgrad_ws on the tap-per-workgroup kernel | btx_contract_wgrad_ws as shipped (all-taps kernel on the 3x3/s1 rows))",
-          sh("python tools/wgrad_bench.py --ablate", env={"BTX_LIB": lib}, timeout=400))
-    write(PREFIX + "_dgrad_bench.txt", "BTX_LIB=build_variants/libbtx_tune.so python tools/dgrad_bench.py   (1 MI355X; autograd._data_grad_hip of the strided ResNet18\n"
-          "convolutions: transposed launch in raster order (BTX_NO_PAR_MAJOR=1) | parity-major order as shipped)",
-          sh("python tools/dgrad_bench.py", env={"BTX_LIB": lib}, timeout=300))
+    write(PREFIX + "_wgrad_bench.txt", "python tools/wgrad_bench.py   (1 MI355X; columns: btx_contract_wgrad with f32 atomics |\n"
+          "btx_contract_wgrad_ws (all-taps kernel on the 3x3/s1 rows, the tap-per-workgroup kernel elsewhere))",
+          sh("python tools/wgrad_bench.py", timeout=400))
+    write(PREFIX + "_dgrad_bench.txt", "python tools/dgrad_bench.py   (1 MI355X; autograd._data_grad_hip of the strided ResNet18\n"
+          "convolutions: the transposed launch, parity-major order where the plan takes it)",
+          sh("python tools/dgrad_bench.py", timeout=300))
 
 
 def derived(rep):
@@ -203,45 +190,6 @@ def step_cfg3():
           "56x56: the narrow tile (one n-tile), 28x28 / 14x14: contract_taps_kernel<bf16, Reparameterization, WIDE>; tools/pmc_report.py)", body)
 
 
-def step_phase():
-    lib = variant("trace", "-DBTX_PT_TRACE -DBTX_TUNING")
-    body = ""
-    for shp in SHAPES[:2]:
-        for v in ("X=0", "BTX_NO_TALL=1", "BTX_TAPS_TUNE=128 BTX_NO_TALL=1"):
-            body += "== %s %s\n" % (shp, v) + "".join(
-                l + "\n" for l in sh("env %s python tools/gpu_diag.py trace --prec bf16 --shape %s" % (v, shp), env={"BTX_LIB": lib}).splitlines()
-                if " wave " not in l and "column 7" not in l)
-    write(PREFIX + "_phase_timers.txt", "BTX_LIB=build_variants/libbtx_trace.so python tools/gpu_diag.py trace --prec bf16 --shape <s>  (batch 64, one launch;\n"
-          "X=0: tall-strip tiles where the plan takes them, BTX_NO_TALL=1: plain tiles, BTX_TAPS_TUNE=128: prologue sub-stamps)", body)
-    body = ""
-    for shp in SHAPES[:2]:
-        for v in ("BTX_PERSIST=1", "X=0"):
-            body += "== %s %s (600 warm launches)\n" % (shp, v) + "".join(
-                l + "\n" for l in sh("env %s BTX_NO_TALL=1 python tools/gpu_diag.py trace --throughput-plan --bs 256 --warm 600 --prec bf16 --shape %s" % (v, shp),
-                                     env={"BTX_LIB": lib}).splitlines() if " wave " not in l and "column 7" not in l)
-    write(PREFIX + "_phase_timers_sustained.txt", "BTX_LIB=build_variants/libbtx_trace.so [BTX_PERSIST=1] BTX_NO_TALL=1 python tools/gpu_diag.py trace --throughput-plan --bs 256\n"
-          "--warm 600 --prec bf16 --shape <s>: block phase timers and the shader clock (s_memtime / s_memrealtime) under sustained load,\n"
-          "persistent kernel (contract_taps3_kernel) against contract_taps_kernel.  Reading: per tile the persistent kernel needs fewer\n"
-          "cycles (56x56: (K loops + store sides) / 7 tiles ~ 29k against ~35k for a one-tile block) but runs at a lower clock under the\n"
-          "higher duty (1.9 against 2.2 GHz): the launch takes the same time (r03_persistent_kbench.txt, r03_persistent_ab.txt)", body)
-
-
-def kbench(lib, envs, shapes, bs=256, env=None):
-    return sh("python tools/kbench.py --throughput-plan --env %s --bs %d --rounds 3 --reps 10 --shapes %s" % (" ".join(envs), bs, " ".join(shapes)),
-              env=dict({"BTX_LIB": lib}, **(env or {})), timeout=900)
-
-
-def step_ablation():
-    body = ""
-    for name, flags in (("tune", "-DBTX_TUNING"), ("abl4", "-DBTX_TUNING -DBTX_PT_ABL=4"), ("abl16", "-DBTX_TUNING -DBTX_PT_ABL=16"),
-                        ("abl2", "-DBTX_TUNING -DBTX_PT_ABL=2"), ("abl22", "-DBTX_TUNING -DBTX_PT_ABL=22")):
-        body += "## %s\n" % name + kbench(variant(name, flags), ["-"], [SHAPES[0], SHAPES[1], SHAPES[3]], env={"BTX_NO_TALL": "1"})
-    write(PREFIX + "_kloop_ablation.txt", "BTX_NO_TALL=1 BTX_LIB=build_variants/libbtx_<v>.so python tools/kbench.py --throughput-plan --env - --bs 256 ...\n"
-          "builds with -DBTX_PT_ABL=<bits>: 4 no weight/patch DMA in the K loop, 16 no s_in masks, 2 no LDS fragment reads, 22 all three\n"
-          "(results wrong by construction; time only).  Reading (128->128, 28x28): no DMA -19 %, no masks -7 %, no fragment reads -27 %,\n"
-          "none of the three: the floor set by MFMA issue, barriers, prologue and store side (118 GFLOP at ~2.1 GHz = 54 us of matrix time)", body)
-
-
 def step_ubench():
     sh("/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o tools/ubench/mfma_mix tools/ubench/mfma_mix.hip", timeout=900)
     write(PREFIX + "_mfma_mix_ubench.txt", "hipcc --offload-arch=gfx950 -O3 -o tools/ubench/mfma_mix tools/ubench/mfma_mix.hip && tools/ubench/mfma_mix\n"
@@ -258,62 +206,39 @@ def step_ubench():
           sh("tools/ubench/mfma_mix", timeout=600))
 
 
-def step_persistent():
-    lib = variant("tune", "-DBTX_TUNING")
-    write(PREFIX + "_persistent_kbench.txt", "BTX_NO_TALL=1 BTX_LIB=build_variants/libbtx_tune.so python tools/kbench.py --throughput-plan --env BTX_PERSIST=1 - --bs 256 ...\n"
-          "(contract_taps3_kernel against contract_taps_kernel; '== variant0: True' = bit-identical results)",
-          sh("python tools/kbench.py --throughput-plan --env BTX_PERSIST=1 - --bs 256 --rounds 3 --reps 10 --shapes %s" % " ".join(SHAPES),
-             env={"BTX_LIB": lib, "BTX_NO_TALL": "1"}, timeout=900))
-
-
-def step_tall():
-    lib = variant("tune", "-DBTX_TUNING")
-    body = ""
-    for bs in (64, 256, 512):
-        body += "## batch %d\n" % bs + kbench(lib, ["-", "BTX_NO_TALL=1"], SHAPES, bs=bs)
-    write(PREFIX + "_tall_tiles_ab.txt", "BTX_LIB=build_variants/libbtx_tune.so python tools/kbench.py --throughput-plan --env - BTX_NO_TALL=1 --bs <b> ...\n"
-          "(tall-strip tiles where the plan takes them against plain tiles)", body)
-
-
 def step_power():
     """profiles/<PREFIX>_power_probe.txt: socket power and sclk (rocm-smi, every ~0.3 s) while 60 000 back-to-back launches of one
-    layer run — contract_taps_kernel against the persistent kernel; needs the tuning build"""
+    layer run (contract_taps_kernel)"""
     import threading
     import time
-    lib = variant("tune", "-DBTX_TUNING")
     body = sh("rocm-smi --showmaxpower 2>/dev/null | grep -i 'max graphics'")
     for shp in SHAPES[:2]:
-        for tag, env in (("contract_taps_kernel", {}), ("persistent (BTX_PERSIST=1)", {"BTX_PERSIST": "1"})):
-            samples, done = [], []
+        samples, done = [], []
 
-            def poll():
-                while not done:
-                    o = sh("rocm-smi --showpower --showclocks", timeout=20)
-                    try:
-                        w = float([l for l in o.splitlines() if "Socket Graphics" in l][0].split(":")[-1])
-                        c = float([l for l in o.splitlines() if "sclk" in l][0].split("(")[1].split("Mhz")[0])
-                        samples.append((w, c))
-                    except Exception:  # noqa
-                        pass
-                    time.sleep(0.3)
-            th = threading.Thread(target=poll)
-            th.start()
-            out = sh("python tools/gpu_diag.py timeone --throughput-plan --prec bf16 --bs 256 --iters 60000 --shape %s" % shp,
-                     env=dict({"BTX_LIB": lib, "BTX_NO_TALL": "1"}, **env), timeout=400)
-            done.append(1)
-            th.join()
-            busy = [(w, c) for w, c in samples if w > 500]
-            body += "%s  %-28s %s" % (shp, tag, [l for l in out.splitlines() if "us / launch" in l][-1].split(":")[-1])
-            if busy:
-                body += "   busy samples %d: mean power %.0f W (max %.0f), mean sclk %.0f MHz\n" % (
-                    len(busy), sum(w for w, _ in busy) / len(busy), max(w for w, _ in busy), sum(c for _, c in busy) / len(busy))
-            else:
-                body += "   (no busy samples)\n"
-    write(PREFIX + "_power_probe.txt", "BTX_LIB=build_variants/libbtx_tune.so BTX_NO_TALL=1 [BTX_PERSIST=1] python tools/gpu_diag.py timeone --throughput-plan\n"
-          "--prec bf16 --bs 256 --iters 60000 --shape <s>, with `rocm-smi --showpower --showclocks` polled meanwhile (1 MI355X).\n"
-          "Reading: both kernels run at 92-99 % of the 1400 W package limit with the clock throttled to 1.86-2.03 GHz (peak 2.4 GHz;\n"
-          "boxes of the pool differ by a few percent): the operating point is set by power, and a kernel that keeps the matrix pipe\n"
-          "busier per cycle (the persistent one) gets fewer cycles per second.  tools/ubench/mfma_mix draws 1260-1340 W at 2.3-2.4 GHz.", body)
+        def poll():
+            while not done:
+                o = sh("rocm-smi --showpower --showclocks", timeout=20)
+                try:
+                    w = float([l for l in o.splitlines() if "Socket Graphics" in l][0].split(":")[-1])
+                    c = float([l for l in o.splitlines() if "sclk" in l][0].split("(")[1].split("Mhz")[0])
+                    samples.append((w, c))
+                except Exception:  # noqa
+                    pass
+                time.sleep(0.3)
+        th = threading.Thread(target=poll)
+        th.start()
+        out = sh("python tools/gpu_diag.py timeone --throughput-plan --prec bf16 --bs 256 --iters 60000 --shape %s" % shp, timeout=400)
+        done.append(1)
+        th.join()
+        busy = [(w, c) for w, c in samples if w > 500]
+        body += "%s  %s" % (shp, [l for l in out.splitlines() if "us / launch" in l][-1].split(":")[-1])
+        if busy:
+            body += "   busy samples %d: mean power %.0f W (max %.0f), mean sclk %.0f MHz\n" % (
+                len(busy), sum(w for w, _ in busy) / len(busy), max(w for w, _ in busy), sum(c for _, c in busy) / len(busy))
+        else:
+            body += "   (no busy samples)\n"
+    write(PREFIX + "_power_probe.txt", "python tools/gpu_diag.py timeone --throughput-plan --prec bf16 --bs 256 --iters 60000 --shape <s>,\n"
+          "with `rocm-smi --showpower --showclocks` polled meanwhile (1 MI355X).", body)
 
 
 def step_install():
