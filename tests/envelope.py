@@ -1,0 +1,276 @@
+"""Per-element rounding envelopes, exact-integer inputs and impulse probes for the contraction kernels (plain module,
+like helpers.py; DESIGN.md §2 states the same formulas).
+
+ENVELOPE.  For out_j = sum_i a_i w_i computed with rounded operands and f32 accumulation, |got_j - ref_j| <= c * A_j with
+A_j = sum_i |a_i| |w_i| — the same contraction on absolute values, so float64 torch produces it with one more call:
+
+  forward          A = op(|x|, |mu| + |sigma eps|) + |mu_b| + |sigma_b eps_b|   (|mu + sigma eps| <= |mu| + |sigma eps| covers
+                                                                                 Reparameterization; the Flipout signs are +-1)
+  data gradient    A = op^T(|dy|, |mu| + |sigma eps|)
+  weight gradient  A = corr(|x|, |dy|)                                           (dW_mu and dW_delta alike)
+
+The constant is derived, not fitted.  u = 2^-8, the unit roundoff of bf16 under round-to-nearest-even (8 significant bits: 7
+stored + the hidden one, so half an ulp is 2^-8 of the binade's lower end — 1 + 2^-8 rounds to 1), K = length of the reduction.
+(2^-9 is NOT a bound: a single rounding reaches 1.99 * 2^-9, which the K = 1 impulse probes and every bf16 store of an
+f32-accurate result show on all kernel families alike; test_envelope_cpu.py pins this on the CPU.)
+
+  operand term   f32     delta_w                       the sampled weight is the only rounded operand
+                 bf16    2u + u^2 + delta_w            both operands rounded once
+                 bf16x3  3u^2 + 2u^3 + delta_w         x = x_h + x_l (+u^2), w likewise, the w_l x_l product is dropped
+  accumulation   (K_acc + 8) 2^-23, K_acc = K (3K for bf16x3: three MFMAs per product).  2^-23 rather than 2^-24: the rounding
+                 inside one bf16 MFMA K-step is not documented; +8 covers split-K combine, Flipout combine and bias adds
+  bf16 store     + u (|ref_j| + bound_j)
+  f32 reference  + (K + 8) 2^-24 A_j when the reference itself was evaluated in f32
+
+delta_w is the relative error of the weight the kernel samples for itself (hardware exp / log softplus, eps as
+materialised) against float64 log1p(exp rho).  It is MEASURED by the impulse probes of test_gpu_elementwise.py (an impulse
+input makes every output a single product, so an f32 launch returns the sampled weights themselves) and DELTA_W below is
+twice the measured maximum; profiles/elementwise_envelope.txt holds the measurement.
+
+The bias is added in f32 by the epilogue: its share of the bound uses the f32 constant whatever the MFMA precision.
+Eval-BN multiplies a bound by |scale_n| and adds 4 * 2^-24 of the magnitudes involved; a residual adds only its store
+rounding; ReLU, ReLU6 and max are 1-Lipschitz in the sup norm, so a bound passes ReLU unchanged and MaxPool2d as the max-pool
+of the bound.
+
+check() compares EVERY element; none is excluded, there is no percentile and no mean.  Where the bound is 0 (padding-only
+outputs without a bias) the output must equal the reference exactly.
+
+KNOWN LIMIT.  For the weight gradient at the baseline sizes K is the pixel count (200 704): the rigorous accumulation term
+reaches 1.2e-2 * A and the envelope says nothing in f32.  Use it for weight gradients on small cases only; the
+exact-integer inputs below (small_ints) cover the large ones with zero tolerance: with |v| <= 3 every product and partial
+sum is an integer below 2^24, f32 accumulation is exact in any order and bf16 / the hi+lo split hold the operands exactly.
+"""
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+U_BF16 = 2.0 ** -8
+ACC_UNIT = 2.0 ** -23
+REF32_UNIT = 2.0 ** -24
+# relative error of the in-kernel sampled weight against float64: 2 x the maximum the impulse probes measured on an MI355X.
+# Three runs with different noise draws gave 4.76e-7, 4.77e-7 and 4.68e-7 (run-time-tap patch kernel and the 8-wave GEMM; the
+# other families 1.8e-7 .. 4.2e-7; rho uniform in [-9, 2] and MOPED-style rho): profiles/elementwise_envelope.txt
+DELTA_W = 9.55e-7
+
+PRECISIONS = ("f32", "bf16", "bf16x3")
+
+
+def operand_term(prec, delta_w=DELTA_W):
+    u = U_BF16
+    if prec == "f32":
+        return delta_w
+    if prec == "bf16":
+        return 2 * u + u * u + delta_w
+    if prec == "bf16x3":
+        return 3 * u * u + 2 * u ** 3 + delta_w
+    raise ValueError(prec)
+
+
+def rel_constant(prec, K, delta_w=DELTA_W, ref_f32=False):
+    """c of |got - ref| <= c * A for a reduction of length K"""
+    k_acc = 3 * K if prec == "bf16x3" else K
+    c = operand_term(prec, delta_w) + (k_acc + 8) * ACC_UNIT
+    if ref_f32:
+        c += (K + 8) * REF32_UNIT
+    return c
+
+
+def bound(A, prec, K, ref=None, A_bias=None, store_bf16=False, ref_f32=False, delta_w=DELTA_W):
+    """per-element bound (float64 numpy).  A: the contraction on absolute values; A_bias: |mu_b| + |sigma_b eps_b| broadcast
+    to A's shape (added in f32 by the epilogue); store_bf16 needs ref (the result is rounded once more on store)."""
+    A = _np(A)
+    b = rel_constant(prec, K, delta_w, ref_f32) * A
+    if A_bias is not None:
+        b = b + rel_constant("f32", 0, delta_w, ref_f32) * _np(A_bias)
+    if store_bf16:
+        b = store_rounding(b, ref)
+    return b
+
+
+def store_rounding(b, ref, u=U_BF16):
+    """the bound after one more rounding of the result to bf16"""
+    return _np(b) + u * (np.abs(_np(ref)) + _np(b))
+
+
+def through_affine(b, ref_pre, scale, shift, channel_axis=1):
+    """eval-BN folded into the store: out = pre * scale[c] + shift[c] in f32"""
+    b, ref_pre = _np(b), _np(ref_pre)
+    shp = [1] * b.ndim
+    shp[channel_axis] = -1
+    s = np.abs(_np(scale)).reshape(shp)
+    t = np.abs(_np(shift)).reshape(shp) if shift is not None else 0.0
+    return b * s + 4 * REF32_UNIT * ((np.abs(ref_pre) + b) * s + t)
+
+
+def through_maxpool2d(b, kernel, stride, padding):
+    """max is 1-Lipschitz in the sup norm: the bound of a pooled output is the max of the bounds in its window"""
+    return F.max_pool2d(torch.as_tensor(_np(b)), kernel, stride, padding).numpy()
+
+
+def _np(t):
+    if isinstance(t, torch.Tensor):
+        return t.detach().to(torch.float64).cpu().numpy()
+    return np.asarray(t, dtype=np.float64)
+
+
+class Report:
+    """worst: max err / bound over all elements (inf where the bound is 0 and the values differ); violations: elements with
+    err > bound; index: position of the worst element in the tensor's logical shape — (image, channel, row, col) for 2-D"""
+
+    def __init__(self, worst, violations, index, err, bnd, numel):
+        self.worst, self.violations, self.index, self.err, self.bnd, self.numel = worst, violations, index, err, bnd, numel
+
+    @property
+    def ok(self):
+        return self.violations == 0
+
+    def line(self, name, prec):
+        return "%s %s: worst err/bound %.3g at %s (%d of %d outside)" % (name, prec, self.worst, self.index, self.violations,
+                                                                       self.numel)
+
+    def __str__(self):
+        return "worst err/bound %.4g at %s (err %.4g, bound %.4g); %d of %d elements outside the envelope" % (
+            self.worst, self.index, self.err, self.bnd, self.violations, self.numel)
+
+
+def check(got, ref, bnd):
+    """|got - ref| <= bnd for EVERY element -> Report.  NaN / inf in got is a violation."""
+    g, r, b = _np(got), _np(ref), _np(bnd)
+    assert g.shape == r.shape == b.shape, (g.shape, r.shape, b.shape)
+    err = np.abs(g - r)
+    err = np.where(np.isfinite(err), err, np.inf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(err == 0.0, 0.0, np.where(b > 0.0, err / b, np.inf))
+    flat = int(np.argmax(ratio)) if ratio.size else 0
+    idx = tuple(int(v) for v in np.unravel_index(flat, ratio.shape)) if ratio.size else ()
+    return Report(float(ratio.max()) if ratio.size else 0.0, int((err > b).sum()), idx,
+                  float(err.reshape(-1)[flat]) if ratio.size else 0.0, float(b.reshape(-1)[flat]) if ratio.size else 0.0,
+                  int(ratio.size))
+
+
+def check_exact(got, ref):
+    """zero tolerance (exact-integer runs): Report with the bound 0 everywhere"""
+    r = _np(ref)
+    return check(got, r, np.zeros_like(r))
+
+
+# ---- A: the contraction on absolute values, float64 on the CPU -----------------------------------------------------------
+_CONV = {1: F.conv1d, 2: F.conv2d, 3: F.conv3d}
+_CONVT = {1: F.conv_transpose1d, 2: F.conv_transpose2d, 3: F.conv_transpose3d}
+
+
+def contract(x, w, b, op):
+    """op as in oracle/bt_ref.py: dict(kind='linear') | dict(kind='conv'|'convT', nd, stride, padding, dilation, groups[, output_padding])"""
+    if op["kind"] == "linear":
+        return F.linear(x, w, b)
+    if op["kind"] == "conv":
+        return _CONV[op["nd"]](x, w, b, op["stride"], op["padding"], op["dilation"], op["groups"])
+    return _CONVT[op["nd"]](x, w, b, op["stride"], op["padding"], op.get("output_padding", 0), op["groups"], op["dilation"])
+
+
+def reduction_length(w_shape, op):
+    """K of the forward: taps x input channels per group"""
+    if op["kind"] == "linear":
+        return int(w_shape[1])
+    taps = int(np.prod(w_shape[2:]))
+    if op["kind"] == "conv":
+        return int(w_shape[1]) * taps
+    return int(w_shape[0]) // int(op["groups"]) * taps  # transposed: the weight is [Cin, Cout/groups, *k]
+
+
+def dgrad_reduction_length(w_shape, op):
+    """K of the data gradient: taps x output channels per group"""
+    if op["kind"] == "linear":
+        return int(w_shape[0])
+    taps = int(np.prod(w_shape[2:]))
+    if op["kind"] == "conv":
+        return int(w_shape[0]) // int(op["groups"]) * taps
+    return int(w_shape[1]) * taps
+
+
+def d64(t):
+    return None if t is None else t.detach().to(torch.float64).cpu().contiguous()
+
+
+def sigma64(rho):
+    return torch.log1p(torch.exp(d64(rho)))
+
+
+def abs_weight(mu, rho, eps):
+    """|mu| + |sigma eps| in float64"""
+    return d64(mu).abs() + (sigma64(rho) * d64(eps)).abs()
+
+
+def reference_forward(x, mu, rho, eps, mu_b, rho_b, eps_b, sign_in, sign_out, op):
+    """the layer's value in float64 (Flipout when sign_in is given, else Reparameterization) and the parts of its envelope:
+    -> (ref, A, A_bias | None), float64 CPU tensors"""
+    x, mu, eps = d64(x), d64(mu), d64(eps)
+    delta = sigma64(rho) * eps
+    bias = bias_d = None
+    if mu_b is not None:
+        bias, bias_d = d64(mu_b), sigma64(rho_b) * d64(eps_b)
+    if sign_in is not None:
+        ref = contract(x, mu, bias, op) + contract(x * d64(sign_in), delta, bias_d, op) * d64(sign_out)
+    else:
+        ref = contract(x, mu + delta, None if bias is None else bias + bias_d, op)
+    A = contract(x.abs(), mu.abs() + delta.abs(), None, op)
+    A_bias = None
+    if bias is not None:
+        shp = [1] * ref.dim()
+        shp[-1 if op["kind"] == "linear" else 1] = -1
+        A_bias = (bias.abs() + bias_d.abs()).reshape(shp).expand_as(ref)
+    return ref, A, A_bias
+
+
+def dgrad_A(dy, x_shape, w_abs, op):
+    """op^T(|dy|, |W|): autograd through the float64 contraction on absolute values"""
+    xz = torch.zeros(x_shape, dtype=torch.float64, requires_grad=True)
+    (g,) = torch.autograd.grad(contract(xz, d64(w_abs), None, op), xz, d64(dy).abs())
+    return g
+
+
+def wgrad_A(x, dy, w_shape, op):
+    """corr(|x|, |dy|) in the weight's logical shape"""
+    wz = torch.zeros(w_shape, dtype=torch.float64, requires_grad=True)
+    (g,) = torch.autograd.grad(contract(d64(x).abs(), wz, None, op), wz, d64(dy).abs())
+    return g
+
+
+def wgrad64(x, dy, w_shape, op):
+    """dW = corr(x, dy) in float64"""
+    wz = torch.zeros(w_shape, dtype=torch.float64, requires_grad=True)
+    (g,) = torch.autograd.grad(contract(d64(x), wz, None, op), wz, d64(dy))
+    return g
+
+
+def wgrad_reduction_length(dy_shape, op):
+    """K of the weight gradient: output pixels x batch"""
+    if op["kind"] == "linear":
+        return int(np.prod(dy_shape[:-1]))
+    return int(dy_shape[0]) * int(np.prod(dy_shape[2:]))
+
+
+# ---- exact-integer inputs ---------------------------------------------------------------------------------------------------
+def small_ints(shape, seed, lim=3, dtype=torch.float32):
+    """integers in [-lim, lim]: exact in bf16, products and sums of up to 2^24 / lim^2 of them exact in f32"""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-lim, lim + 1, tuple(shape), generator=g).to(dtype)
+
+
+def dyadic(shape, seed, m=128, shift=7, dtype=torch.float32):
+    """m' * 2^-shift with |m'| <= m: 8 significant bits, exact in bf16"""
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randint(-m, m + 1, tuple(shape), generator=g).to(torch.float64) * 2.0 ** -shift).to(dtype)
+
+
+# ---- impulse probes ---------------------------------------------------------------------------------------------------------
+def impulse_batch(channels, spatial, pixels):
+    """one image per (channel, pixel): x[i] = e_c at pixel p -> (x [len(pixels) * channels, channels, *spatial], list of (c, p))"""
+    n = len(pixels) * channels
+    x = torch.zeros((n, channels) + tuple(spatial))
+    where = []
+    for p in pixels:
+        for c in range(channels):
+            x[(len(where), c) + tuple(p)] = 1.0
+            where.append((c, tuple(p)))
+    return x, where

@@ -46,12 +46,16 @@ def _build(arch, typ, moped, dev, bf16):
     return m
 
 
-def _check_every_layer(model, x, typ, sample, tol):
+def _check_every_layer(model, x, typ, sample, tol, prec):
     """forward hooks compare each variational layer with the reference chain AS IT RUNS (nothing is kept: ResNet50 at
-    batch 128 moves 11 GB of activations); returns (worst rel-L2, number of layers, logits)"""
+    batch 128 moves 11 GB of activations); returns (worst rel-L2, number of layers, logits, worst err / envelope).
+    Besides the rel-L2 bar every ELEMENT must lie inside the rounding envelope of tests/envelope.py: A = the same contraction on
+    absolute values, by torch on the GPU in f32 like the reference itself (hence the reference's own (K + 8) 2^-24 A term, and A
+    is widened by its own rounding)."""
     import bayesian_torch_amd as bt
+    import envelope as E
     from oracle import bt_ref
-    worst = [0.0, 0]
+    worst = [0.0, 0, 0.0]
 
     def hook(mod, inp, out):
         xin = inp[0].detach()
@@ -72,6 +76,24 @@ def _check_every_layer(model, x, typ, sample, tol):
         worst[0] = max(worst[0], err)
         worst[1] += 1
         assert err < tol, (mod.__class__.__name__, tuple(xin.shape), mod._op.kernel, mod._op.stride, err)
+        K = E.reduction_length(tuple(mu.shape), op)
+        bound = bt_ref._contract(xf.abs(), mu.abs() + (bt_ref.softplus(rho) * nz["eps_w"]).abs(), None, op)
+        bound *= E.rel_constant(prec, K, ref_f32=True) * (1.0 + (K + 8) * E.REF32_UNIT)
+        if mod.mu_bias is not None:
+            ab = mod.mu_bias.abs() + (bt_ref.softplus(mod.rho_bias) * nz["eps_b"]).abs()
+            bound += E.rel_constant("f32", 0, ref_f32=True) * ab.view((1, -1) + (1,) * (ref.dim() - 2))
+        if out.dtype == torch.bfloat16:  # rounded once more on store
+            bound += E.U_BF16 * (ref.abs() + bound)
+        dev = (out.detach().float() - ref).abs()
+        outside = ~(dev <= bound)  # NaN counts as outside
+        ratio = torch.where(dev == 0, torch.zeros_like(dev), dev / bound)  # bound 0 (padding only) and dev > 0 -> inf
+        flat = int(ratio.argmax())
+        idx = tuple(int(v) for v in np.unravel_index(flat, tuple(ratio.shape)))
+        r = float(ratio.reshape(-1)[flat])
+        worst[2] = max(worst[2], r)
+        assert not bool(outside.any()), ("outside the envelope", mod.__class__.__name__, tuple(xin.shape), mod._op.kernel,
+                                         mod._op.stride, prec, "worst err/bound %.4g at %s" % (r, idx),
+                                         "%d of %d elements" % (int(outside.sum()), outside.numel()))
     hs = [mod.register_forward_hook(hook) for mod in model.modules() if hasattr(mod, "kl_loss")]
     try:
         with torch.no_grad():
@@ -80,7 +102,7 @@ def _check_every_layer(model, x, typ, sample, tol):
     finally:
         for h in hs:
             h.remove()
-    return worst[0], worst[1], logits
+    return worst[0], worst[1], logits, worst[2]
 
 
 @pytest.mark.parametrize("prec,tol", [("f32", 1e-4), ("bf16", 1e-2), ("bf16x3", 1e-4)])
@@ -95,9 +117,10 @@ def test_resnet18_bs64_every_layer(typ, prec, tol):
         m = _build("resnet18", typ, False, dev, prec == "bf16")
         torch.manual_seed(1234)
         x = torch.randn(64, 3, 224, 224, device=dev).to(torch.bfloat16 if prec == "bf16" else torch.float32)
-        worst, n, logits = _check_every_layer(m, x, typ, 5, tol)
+        worst, n, logits, env = _check_every_layer(m, x, typ, 5, tol, prec)
         assert n == 21 and logits.shape == (64, 1000) and torch.isfinite(logits).all()
         print("resnet18 %s %s bs64: worst per-layer rel-L2 %.3g" % (typ, prec, worst))
+        print("resnet18 %s bs64 every layer %s: worst err/bound %.3g" % (typ, prec, env))
     finally:
         bt.set_precision("f32")
 
@@ -113,7 +136,7 @@ def test_resnet50_moped_bs128_every_layer(prec, tol):
         m = _build("resnet50", "Flipout", True, dev, prec == "bf16")
         torch.manual_seed(1234)
         x = torch.randn(128, 3, 224, 224, device=dev).to(torch.bfloat16 if prec == "bf16" else torch.float32)
-        worst, n, logits = _check_every_layer(m, x, "Flipout", 2, tol)
+        worst, n, logits, env = _check_every_layer(m, x, "Flipout", 2, tol, prec)
         assert n == 54 and logits.shape == (128, 1000) and torch.isfinite(logits).all()
         kat = json.load(open(os.path.join(HERE, "golden", "kat.json")))["models"].get("resnet50_Flipout_moped")
         if kat:
@@ -121,6 +144,7 @@ def test_resnet50_moped_bs128_every_layer(prec, tol):
                 kl = float(bt.get_kl_loss(m))
             assert abs(kl - kat["kl"]) <= 1e-5 * abs(kat["kl"]), (kl, kat["kl"])
         print("resnet50+MOPED Flipout %s bs128: worst per-layer rel-L2 %.3g" % (prec, worst))
+        print("resnet50+MOPED Flipout bs128 every layer %s: worst err/bound %.3g" % (prec, env))
     finally:
         bt.set_precision("f32")
 
