@@ -90,7 +90,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_bn_workspace_bytes", "btx_bn_train_fwd", "btx_bn_train_bwd", "btx_dgrad_weights",
            "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd",
            "btx_lstm_workspace_bytes", "btx_lstm_fwd", "btx_lstm_train_saved_bytes", "btx_lstm_train_workspace_bytes",
-           "btx_lstm_fwd_train", "btx_lstm_bwd")
+           "btx_lstm_fwd_train", "btx_lstm_bwd",
+           "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd")
 
 
 def lib_path():
@@ -202,6 +203,16 @@ def lib():
     L.btx_lstm_bwd.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, vp, vp, vp, vp, vp,
                                vp, vp, vp, vp, ctypes.POINTER(LstmGrads), ctypes.POINTER(LstmGrads), i32, i32, i32, i32, i32,
                                i32, vp, sz, vp]
+    L.btx_calib_workspace_bytes.restype = sz
+    L.btx_calib_workspace_bytes.argtypes = [i32]
+    L.btx_avu_fwd.restype = i32
+    L.btx_avu_fwd.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, f32, vp, vp, sz, vp]
+    L.btx_avu_bwd.restype = i32
+    L.btx_avu_bwd.argtypes = [vp, i32, i32, i32, vp, vp, vp, sz, vp, vp]
+    L.btx_eau_fwd.restype = i32
+    L.btx_eau_fwd.argtypes = [vp, vp, i32, i32, f32, vp, f32, vp, f32, vp, vp, sz, vp]
+    L.btx_eau_bwd.restype = i32
+    L.btx_eau_bwd.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -522,6 +522,33 @@ int btx_lstm_bwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
                  void* dx, void* dh0, void* dc0, const BtxLstmGrads* g_ih, const BtxLstmGrads* g_hh, int B, int I, int H, int T,
                  int act_dtype, int prec, void* workspace, size_t ws_bytes, void* stream);
 
+/* K9. Uncertainty-calibration losses (reference utils/avuc_loss.py AvULoss / AUAvULoss, utils/uncertainty_calibration_loss.py
+ * EaULoss / EaCLoss / AvULoss), forward and backward, without a host read: capturable into a hipGraph.
+ *   loss = -beta * log(r + 1e-10),  r = (n_1 + n_4) / (n_1 + n_2 + n_3 + n_4 + 1e-10);  n_q = sum over the examples of a
+ *   quadrant (good / bad x certain / uncertain) of a product of two soft weights.  Gradients flow through the weights only.
+ * btx_avu_fwd: logits [B][C] in act_dtype, labels int64 [B].  area = 0: one threshold on the entropy H (certain = H <= th);
+ *   area = 1: the trapezoid over np.linspace(0, 1, 21) of r at th_k = umin + t_k * (umax - umin), evaluated in double from the
+ *   f32 umin / umax, th_20 = umax exactly (`th` is ignored).  out[0] = loss, out[1] = r (the AvU, or its area).
+ * btx_avu_bwd: the backward of the btx_avu_fwd call that filled `ws`, same logits.  g_loss / g_r: DEVICE scalars, the upstream
+ *   gradients of out[0] / out[1], either nullable (zero).  dlogits [B][C] in act_dtype, fully overwritten.
+ * btx_eau_fwd / btx_eau_bwd: error, other f32 [B].  conf_form = 0 (EaU): other = uncertainty, certain = other <= other_th,
+ *   weights (1 - tanh e | tanh e) x (1 - tanh u | tanh u);  conf_form = 1 (EaC): other = confidence, certain = other > other_th,
+ *   weights (1 - tanh e | tanh e) x (conf | 1 - conf).  good = error <= error_th.  derror / dother: either nullable.
+ * A threshold is the float argument, or — when its *_dev pointer is non-NULL — one f32 word in device memory that the kernel
+ * reads when it runs (a captured graph follows an updated threshold).
+ * ws: btx_calib_workspace_bytes(B) bytes, written by the forward and read by the backward.  Every sum has a fixed shape and
+ * no atomics: two runs give the same bits.  Three launches for forward + backward (AvU forms), two for EaU / EaC.
+ * Errors: BTX_E_NULL, BTX_E_SHAPE (B, C <= 0, area / conf_form not 0 or 1), BTX_E_DTYPE, BTX_E_WORKSPACE. */
+size_t btx_calib_workspace_bytes(int B);
+int btx_avu_fwd(const void* logits, const int64_t* labels, int B, int C, int act_dtype, int area, float th, const float* th_dev,
+                float beta, float* out, void* ws, size_t ws_bytes, void* stream);
+int btx_avu_bwd(const void* logits, int B, int C, int act_dtype, const float* g_loss, const float* g_r, const void* ws,
+                size_t ws_bytes, void* dlogits, void* stream);
+int btx_eau_fwd(const float* error, const float* other, int B, int conf_form, float error_th, const float* error_th_dev,
+                float other_th, const float* other_th_dev, float beta, float* out, void* ws, size_t ws_bytes, void* stream);
+int btx_eau_bwd(const float* error, const float* other, int B, int conf_form, const float* g_loss, const void* ws,
+                size_t ws_bytes, float* derror, float* dother, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
