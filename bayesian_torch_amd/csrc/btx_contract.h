@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "btx_rng.h"
+#include "btx_plan.h"  // the tile constants shared with the host planner: BM, BN, NG, DBM, PT_*
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -46,9 +47,6 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 namespace btx {
 
 constexpr int NTHREADS = 512;
-constexpr int BM = 256;        // pixels per workgroup tile
-constexpr int BN = 64;         // output channels per workgroup tile
-constexpr int NG = 4;          // granule rows per K-stage
 constexpr int ACTS_OFF = 0;                      // [NG][BM] x 16 B
 constexpr int SIGN_OFF = NG * BM * 16;           // [NG][BM] x 4 B
 constexpr int WMU_OFF = SIGN_OFF + NG * BM * 4;  // [NG][BN] x 16 B
@@ -74,17 +72,18 @@ __device__ __forceinline__ uint32_t fdiv(uint32_t x, const FastDiv& f) {
   const uint32_t t = __umulhi(x, f.m);
   return (t + ((x - t) >> (f.sh & 31u))) >> (f.sh >> 8);
 }
+// the two key words of a Flipout sign stream (host side; rng_live() derives the same on the device)
+static inline void sign_keys(const BtxRng* rng, uint32_t stream, uint32_t* ka, uint32_t* kb) {
+  const BtxPhilox4 k = btx_philox4x32_10(0u, rng->sample_idx, rng->layer_id, stream, (uint32_t)rng->seed,
+                                         (uint32_t)(rng->seed >> 32));
+  *ka = k.x[0];
+  *kb = k.x[1];
+}
 // quotient and remainder; d is the divisor the FastDiv was made for
 __device__ __forceinline__ void fdivmod(uint32_t x, const FastDiv& f, uint32_t d, uint32_t& q, uint32_t& r) {
   q = fdiv(x, f);
   r = x - q * d;
 }
-
-// patch variant (btx_contract_patch.h)
-constexpr int PT_WD = 4;  // depth of the weight-tile ring: W(s+3) is fetched while stage s multiplies and s+1 is read
-constexpr int PT_EP_ROW = 272;
-constexpr int PT_EP_WAVE = 64 * PT_EP_ROW;  // 17408: epilogue staging per wave
-constexpr int PT_MAXNI = 8;  // 1-KiB DMA instructions per wave per patch slot (host plan keeps pieces <= NW * 8)
 
 struct ContractParams {
   const void* x;
@@ -122,7 +121,7 @@ struct ContractParams {
   FastDiv fd_inner, fd_ksplits, fd_ntiles, fd_Cg, fd_KW, fd_KH, fd_rtiles;  // wave-uniform index splits
   FastDiv fd_mtiles;
   int swap_signs;  // BTX_FLAG_SWAP_SIGNS: input signs from stream SIGN_OUT, output signs from SIGN_IN
-  // Parity-major pixel order of a stride-2 transposed 2-D launch (btx_api.hip par_major_ok: the data gradient of a stride-2
+  // Parity-major pixel order of a stride-2 transposed 2-D launch (btx_plan.cpp select_fwd: the data gradient of a stride-2
   // convolution): logical pixel L = class * par_Mqp + q, class = 2 * (oh & 1) + (ow & 1), q < par_Mq the raster index of
   // (image, oh / 2, ow / 2) on the par_Hh x par_Wh half-resolution grid, par_Mqp = par_Mq rounded up to whole pixel tiles.  A tile
   // then lies inside ONE class, and of the KH x KW taps only those whose stride residue matches the class (1, 2, 2 or 4 of a 3x3

@@ -35,7 +35,6 @@
 
 namespace btx {
 
-constexpr int DBM = 512;                    // pixels per workgroup tile, 8-wave blocks (one per CU)
 constexpr int DMA_D = 3;                    // activation + sign ring depth
 constexpr int DW_STAGE = 2 * NG * BN * 16;  // 8192 : mu tile at +0, delta tile at +4096
 // LDS map of a block of NW waves (tile = 64*NW pixels): DMA_D activation stages, DMA_D sign stages, WD weight tiles

@@ -17,7 +17,7 @@
 //   * staged store side of btx_epilogue.h (8 x 17 KB: the rings are dead by then), per-half constants.
 //
 // Same K order per output element as every other variant: bit-identical to contract_dma_kernel on the same launch.
-// Host-checked (btx_api.hip): Flipout, bf16 activations and MFMA, pointwise geometry, K % 32 == 0, K >= 4 stages, an even
+// Host-checked (btx_plan.cpp): Flipout, bf16 activations and MFMA, pointwise geometry, K % 32 == 0, K >= 4 stages, an even
 // number of whole n-tiles per group, one K split.  ContractParams: pt_rtiles = n-tile pairs per group.
 #pragma once
 #include <type_traits>

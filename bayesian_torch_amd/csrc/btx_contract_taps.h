@@ -50,7 +50,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   }
 }
 
-constexpr int TP_MAXNI = 6;  // 1-KiB patch pieces per wave: the 4-wave plan caps the patch at 22 pieces (btx_api.hip)
+constexpr int TP_MAXNI = 6;  // 1-KiB patch pieces per wave: the 4-wave plan caps the patch at 22 pieces (btx_plan.cpp)
 
 // pieces of the next block's patch fetched in stage t of a block: stages 0..T-4 share the TP_MAXNI piece slots
 template <int T>

@@ -259,7 +259,7 @@ class _VariationalNd(BaseVariationalLayer_):
         if src and op0.transposed:
             return None  # the transposed GEMM-major order is not [N][taps][C] of the padded geometry: per-launch sampling
         # Single-sample launches of Linear layers with at most 256 rows are sampled INSIDE their contraction launch (libbtx routes them to
-        # the register-staged kernel: softplus + Philox in registers, no tile in HBM — btx_api.hip "sample where the weights are
+        # the register-staged kernel: softplus + Philox in registers, no tile in HBM — btx_plan.cpp select_fwd "sample where the weights are
         # used"): nothing to pre-sample.  (bf16x3 has no register-staged form and keeps its tiles.)
         if op0.nd == 0 and (self.precision or prec) != "bf16x3" and self._lanes()[0] == 1 and not BF._CONCURRENT:
             rows = 1

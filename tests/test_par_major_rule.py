@@ -1,6 +1,6 @@
 """The parity-major pixel order of stride-2 transposed launches (csrc/btx_contract_dma.h `par_major`, btx_epilogue.h `par_major_pixel`,
-btx_api.hip): restated in Python and checked against the gather rule it shortcuts — no GPU.  (The GPU parity tests of the kernel are
-tests/test_gpu_backward.py, the stride-2 cases of CASES.)"""
+the routing rule in btx_plan.cpp select_fwd): restated in Python and checked against the gather rule it shortcuts — no GPU.
+(The GPU parity tests of the kernel are tests/test_gpu_backward.py, the stride-2 cases of CASES.)"""
 import itertools
 
 
