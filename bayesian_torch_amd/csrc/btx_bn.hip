@@ -7,7 +7,7 @@
 // ATen kernels (batch_norm_collect_statistics / _backward_reduce / _backward_elemt / _transform_input, channels-last bf16) took
 // 3.65 ms of a 10.6 ms step for 2.5 GB of traffic (0.7 TB/s).  These are plain HBM-bound passes:
 //
-//   forward   stats: one pass over x  -> per-block sums of (x - pivot), (x - pivot)^2 per channel in f32 (pivot = row 0) -> fixed-order f64 fold: mean, 1/sqrt(var + eps),
+//   forward   stats: one pass over x  -> per-block sums of (x - pivot), (x - pivot)^2 per channel in f32 (pivot = median of rows 0, M/2, M-1) -> fixed-order f64 fold: mean, 1/sqrt(var + eps),
 //             the running estimates, and the per-channel (scale, shift) of the apply pass
 //             apply: y = x * scale[c] + shift[c]                                  (one read, one write)
 //   backward  reduce: one pass over (x, dy) -> sum(dy), sum(dy * xhat) per channel -> dgamma, dbeta and the three coefficients of
@@ -62,16 +62,18 @@ __device__ __forceinline__ void store8<__bf16>(__bf16* p, const float v[8]) {
   *(u32x4*)p = a;
 }
 
-__device__ __forceinline__ float param_load(const void* p, int dtype, int c) {
+__device__ __forceinline__ float param_load(const void* p, int dtype, long long c) {
   if (dtype == BTX_ACT_BF16) return __builtin_bit_cast(float, (uint32_t)((const uint16_t*)p)[c] << 16);
   return ((const float*)p)[c];
 }
+// median of three: the pivot of the shifted sums.  fminf / fmaxf on the same three floats give the same bits wherever they run.
+__device__ __forceinline__ float med3(float a, float b, float c) { return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c)); }
 __device__ __forceinline__ void param_store(void* p, int dtype, int c, float v) {
   if (dtype == BTX_ACT_BF16) ((uint16_t*)p)[c] = (uint16_t)bf16_rn(v);
   else ((float*)p)[c] = v;
 }
 
-// Per-channel partial sums of two quantities over the rows of this block:  MODE 0: (x, x*x)   MODE 1: (dy, dy * (x - mean) * invstd)
+// Per-channel partial sums of two quantities over the rows of this block:  MODE 0: (x - pivot, (x - pivot)^2)   MODE 1: (dy, dy * (x - mean) * invstd)
 // partial[blk][2][C] (f32).  Block = 256 threads = RPB rows x (C/8) channel groups per pass; rows of a block: blk, blk + nblk, ...
 // MASK (MODE 1, a fused ReLU behind the normalisation): dy counts only where the forward's output was positive — one bit per element,
 // the byte of this thread's 8 channels, written by the forward's apply pass.
@@ -93,9 +95,19 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const ACT* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) { mu[i] = mean[g * 8 + i]; is[i] = invstd[g * 8 + i]; }
   }
-  // MODE 0: sums of (x - pivot) and (x - pivot)^2 with pivot = the channel's value in row 0: E[x^2] - E[x]^2 on raw f32 sums loses
-  // the variance of a channel whose mean is large against its spread; shifted by any value of the channel it does not
-  if (MODE == 0 && act) load8<ACT>(x + g * 8, mu);
+  // MODE 0: sums of (x - pivot) and (x - pivot)^2.  E[x^2] - E[x]^2 on raw f32 sums loses the variance of a channel whose mean is
+  // large against its spread; shifted by a pivot p it loses (mean - p)^2 / var of it instead: nothing when p lies within the
+  // channel's spread, 4.8e-4 of the variance (M = 25 088, f32, emulated on the CPU) when p is an outlier 300 spreads out.  pivot = the median of the
+  // channel's values in rows 0, M/2 and M-1: one outlier among the three cannot be the pivot; two can (and a channel made of
+  // a few far-apart clusters has no good single pivot): the variance then degrades as above, the mean does not.
+  if (MODE == 0 && act) {
+    float p1[8], p2[8];
+    load8<ACT>(x + g * 8, mu);
+    load8<ACT>(x + (M / 2) * C + g * 8, p1);
+    load8<ACT>(x + (M - 1) * C + g * 8, p2);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) mu[i] = med3(mu[i], p1[i], p2[i]);
+  }
   if (act) {
     // four rows in flight per thread (the pass is bound by how many 16-byte loads a CU keeps outstanding), summed in row order
     const long long stride = (long long)gridDim.x * rpb;
@@ -184,7 +196,7 @@ __device__ __forceinline__ bool bn_fold(const float* __restrict__ partial, int n
 
 // forward: fold the partials, statistics, running estimates, (scale, shift) of the apply pass
 __global__ __launch_bounds__(1024) void bn_fwd_final_kernel(const float* __restrict__ partial, int nblk, long long M, int C,
-                                                           const void* x_row0, int act_dtype,
+                                                           const void* x, int act_dtype,
                                                            const void* gamma, const void* beta, void* running_mean,
                                                            void* running_var, int pdt, float momentum, float eps,
                                                            float* __restrict__ save_mean, float* __restrict__ save_invstd,
@@ -194,7 +206,9 @@ __global__ __launch_bounds__(1024) void bn_fwd_final_kernel(const float* __restr
   int c;
   double s, q;
   if (!bn_fold(partial, nblk, C, c, s, q)) return;
-  const double pivot = (double)param_load(x_row0, act_dtype, c);  // the sums are those of x - pivot (bn_partial_kernel)
+  // the sums are those of x - pivot, the pivot bn_partial_kernel took: the median of rows 0, M/2, M-1
+  const double pivot = (double)med3(param_load(x, act_dtype, c), param_load(x, act_dtype, (M / 2) * C + c),
+                                    param_load(x, act_dtype, (M - 1) * C + c));
   const double ms = s / (double)M;
   const double m = pivot + ms;
   double var = q / (double)M - ms * ms;

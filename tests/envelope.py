@@ -39,6 +39,30 @@ KNOWN LIMIT.  For the weight gradient at the baseline sizes K is the pixel count
 reaches 1.2e-2 * A and the envelope says nothing in f32.  Use it for weight gradients on small cases only; the
 exact-integer inputs below (small_ints) cover the large ones with zero tolerance: with |v| <= 3 every product and partial
 sum is an integer below 2^24, f32 accumulation is exact in any order and bf16 / the hi+lo split hold the operands exactly.
+
+REDUCTIONS (BatchNorm training, MC accumulate, KL gradients, global average pool; second half of this file).  u32 = 2^-24, the unit
+roundoff of f32.  Every constant below is a count of roundings, written out where it is used; none is fitted.
+
+  BatchNorm   the kernel sums d = x - pivot and d^2 per channel in f32 along a chain of K = rows per thread + rows per block
+              additions (bn_chain), then folds the blocks in f64.  Statistics term, per channel, with S1 = mean|d|, S2 = mean d^2,
+              ms = mean d:   |dmean| <= (K + 8) u32 S1      |dvar| <= (K + 8) u32 (S2 + 2 |ms| S1)
+              (K additions, the rounding of d, of d^2 and of the fma, slack for second order: the "+ 8").  invstd follows with the
+              derivative 1 / (2 (var + eps)).  The apply pass is y = fma(sc, x, shift), sc = fl(g fl(invstd)), shift =
+              fl(b - fl(fl(mean) sc)): roundings 3 on |sc x|, 6 on |sc mean|, 2 on |b|  ->  8 u32 (|sc x| + |sc mean| + |b|); the
+              statistics enter through (x - mean) dsc and sc dmean, because the SAME sc multiplies x and mean.
+              Backward: s = sum g, q = sum g xhat on the same chain: |ds| <= (K + 8) u32 sum|g|, |dq| <= (K + 8) u32 sum|g xhat| +
+              sum|g| |dxhat| with dxhat from the saved (f32) mean and invstd.  dx = fma(A, g, fma(B, x, D)) with A, B, D rounded
+              to f32 from f64 values: roundings 2 on |A g|, 3 on |B x|, 3 on |D|  ->  4 u32 (|A g| + |B x| + |D|); the reduction
+              term is |g - s/M| dA + |A| ds / M + |x - mean| dB + |B| dmean.  bf16 outputs: store_rounding on top.
+  MC          p = exp(x - max) / sum: relative bound (|x - max| + ceil(C / 256) + c0) 2^-23 — the argument's rounding scales with
+              |x - max|, the row sum is four chains of ceil(C / 256) additions, c0 = C0_ULP is the error of expf / logf in ulps —
+              plus (c0 + 1) 2^-149 where the result is subnormal.  Carried through p^2 and p log(p + 1e-15); the entropy adds
+              (ceil(C / 256) + 9) u32 sum|t| for its own chains and tree.  Accumulating S samples in f32 adds u32 times every
+              running sum (<= S u32 while the running sums stay below 1, which holds in every case of the tests).
+  KL          dmu = g (mu - pm) / ps^2: six roundings -> 8 u32 |dmu|.  drho = g (sig / ps^2 - 1 / sig) sig': the two terms
+              cancel near sig = ps, so the bound is on magnitudes: (c1 u32 + DELTA_W) g (sig / ps^2 + 1 / sig) sig' with
+              c1 = 12 + 2 c0 (ten roundings and the expf inside sig'; DELTA_W is the softplus, as for the sampled weights).
+  avg-pool    small integers: f32(sum) * f32(1 / HW), one rounding, then the store's: exact, zero tolerance.
 """
 import numpy as np
 import torch
@@ -274,3 +298,184 @@ def impulse_batch(channels, spatial, pixels):
             x[(len(where), c) + tuple(p)] = 1.0
             where.append((c, tuple(p)))
     return x, where
+
+
+# =============================================================================================================================
+# reductions: BatchNorm training, MC accumulate, KL gradients, global average pool (derivations in the docstring)
+# =============================================================================================================================
+# error of the device's f32 exp and log in ulps: 2 x the maximum of torch.exp on [-104, 0] and torch.log on [1e-38, 1] (the math
+# library functions btx_small.hip calls) against float64 on an MI355X, 4 M points each — exp 1.00 ulp (subnormal results
+# included), log 1.88 ulp: profiles/reduction_envelope.txt
+C0_ULP = 3.77
+TINY32 = 2.0 ** -149  # the smallest subnormal of f32
+
+
+def ulp32(v):
+    """the spacing of f32 at |v| (float64 numpy), 2^-149 below the normal range"""
+    a = np.abs(_np(v))
+    with np.errstate(divide="ignore"):
+        e = np.floor(np.log2(np.where(a > 0, a, 1.0)))
+    return np.maximum(np.where(a > 0, 2.0 ** (e - 23), TINY32), TINY32)
+
+
+def ulp_error(got, ref):
+    """max |got - ref| / ulp32(ref) -> (worst, index)"""
+    r = np.abs(_np(got) - _np(ref)) / ulp32(ref)
+    i = int(np.argmax(r))
+    return float(r.reshape(-1)[i]), i
+
+
+def bn_chain(M, C):
+    """K of btx_bn.hip: the longest f32 addition chain of a channel's sums — rows per thread plus rows per block"""
+    cg = C // 8
+    rpb = max(256 // cg, 1)
+    nblk = min(max(-(-M // (rpb * 8)), 1), 512)
+    return -(-M // (nblk * rpb)) + rpb
+
+
+def bn_pivot(x):
+    """the kernel's pivot: per channel the median of rows 0, M/2 and M-1 of x [M, C]"""
+    M = x.shape[0]
+    return torch.stack([x[0], x[M // 2], x[M - 1]]).median(0).values
+
+
+def bn_forward64(x, gamma, beta, eps, K, residual=None, relu=False):
+    """training-mode BatchNorm of x [M, C] (float64 torch, the dtype-rounded values) and the parts of its envelope -> dict of
+    float64 torch tensors: y, b_y (before any bf16 store), mean, var, invstd and their bounds d_mean, d_var, d_invstd (as SAVED
+    in f32: statistics + one rounding), dm_stat / dv_stat (statistics alone)"""
+    u = REF32_UNIT
+    M, C = x.shape
+    g = torch.ones(C, dtype=torch.float64) if gamma is None else d64(gamma)
+    b = torch.zeros(C, dtype=torch.float64) if beta is None else d64(beta)
+    eps = float(np.float32(eps))
+    d = x - bn_pivot(x)
+    ms, S1, S2 = d.mean(0), d.abs().mean(0), (d * d).mean(0)
+    mean = x.mean(0)
+    xc = x - mean
+    var = (xc * xc).mean(0)
+    st = (K + 8) * u
+    dm_stat = st * S1
+    dv_stat = st * (S2 + 2 * ms.abs() * S1)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    dis_stat = invstd * dv_stat / (2 * (var + eps))
+    sc = g * invstd
+    y = xc * sc + b
+    b_y = 8 * u * ((sc * x).abs() + (sc * mean).abs() + b.abs()) + xc.abs() * g.abs() * dis_stat + sc.abs() * dm_stat
+    if residual is not None:
+        b_y = b_y + 2 * u * (y.abs() + residual.abs() + b_y)
+        y = y + residual
+    if relu:
+        y = torch.relu(y)  # 1-Lipschitz: the bound passes unchanged
+    return dict(y=y, b_y=b_y, mean=mean, var=var, invstd=invstd, dm_stat=dm_stat, dv_stat=dv_stat, d_mean=dm_stat + u * mean.abs(),
+                d_var=dv_stat, d_invstd=dis_stat + u * invstd, g=g, xc=xc, M=M)
+
+
+def bn_running64(f, old_mean, old_var, momentum):
+    """running estimates after one step and their bounds (f32 storage) -> (rm, b_rm, rv, b_rv)"""
+    u = REF32_UNIT
+    mom = float(np.float32(momentum))
+    M = f["M"]
+    unb = f["var"] * (M / (M - 1.0)) if M > 1 else f["var"]
+    a, c = (1.0 - mom) * d64(old_mean), mom * f["mean"]
+    rm, b_rm = a + c, 4 * u * (a.abs() + c.abs()) + mom * f["dm_stat"]
+    a, c = (1.0 - mom) * d64(old_var), mom * unb
+    rv, b_rv = a + c, 4 * u * (a.abs() + c.abs()) + mom * f["dv_stat"] * (M / (M - 1.0) if M > 1 else 1.0)
+    return rm, b_rm, rv, b_rv
+
+
+def bn_backward64(x, dy, f, K, mask=None):
+    """dx, dgamma, dbeta of training-mode BatchNorm in float64 with their bounds; f = bn_forward64(...); mask: where the fused ReLU
+    let the gradient pass (the kernel's own y > 0) -> dict(dx, b_dx, dgamma, b_dgamma, dbeta, b_dbeta, g)"""
+    u = REF32_UNIT
+    M = f["M"]
+    st = (K + 8) * u
+    gy = dy if mask is None else dy * mask
+    mean, invstd, gam, xc = f["mean"], f["invstd"], f["g"], f["xc"]
+    xhat = xc * invstd
+    s, q = gy.sum(0), (gy * xhat).sum(0)
+    Sa, Sq = gy.abs().sum(0), (gy * xhat).abs().sum(0)
+    ds = st * Sa
+    dq = st * Sq + Sa * invstd * f["d_mean"] + Sq * f["d_invstd"] / invstd
+    A = gam * invstd
+    B = -A * invstd * q / M
+    D = -A * s / M - B * mean
+    dA = gam.abs() * f["d_invstd"]
+    dB = B.abs() * 2 * f["d_invstd"] / invstd + A.abs() * invstd * dq / M
+    dx = A * (gy - s / M) + B * xc
+    b_dx = (4 * u * ((A * gy).abs() + (B * x).abs() + D.abs()) + dA * (gy - s / M).abs() + A.abs() * ds / M + dB * xc.abs()
+            + B.abs() * f["d_mean"])
+    return dict(dx=dx, b_dx=b_dx, dgamma=q, b_dgamma=dq, dbeta=s, b_dbeta=ds, g=gy)
+
+
+def bn_exact_stats(x, eps):
+    """integer x [M, C] (float64 torch): mean, unbiased variance and 1/sqrt(var + eps) from exact integer sums -> float64 numpy"""
+    M = x.shape[0]
+    xi = x.to(torch.int64)
+    sx, sxx = xi.sum(0).numpy().astype(object), (xi * xi).sum(0).numpy().astype(object)
+    mean = np.array([float(a) / M for a in sx])
+    num = [M * b - a * a for a, b in zip(sx, sxx)]  # python integers: exact
+    var = np.array([float(n) / (float(M) * M) for n in num])
+    unb = np.array([float(n) / (float(M) * (M - 1)) for n in num])
+    return mean, var, unb, 1.0 / np.sqrt(var + float(np.float32(eps)))
+
+
+def mc_reference(x, c0=C0_ULP):
+    """x [S, bs, C]: the dtype-rounded logits of S samples accumulated in order (float64 numpy) -> dict of the packed statistics
+    (sum_p, sum_p2 [bs, C], ent [bs]) and their bounds (b_sum_p, b_sum_p2, b_ent)"""
+    u = REF32_UNIT
+    x = np.asarray(x, dtype=np.float64)
+    S, bs, C = x.shape
+    chains = -(-C // 256)
+    mx = x.max(-1, keepdims=True)
+    with np.errstate(invalid="ignore"):
+        d = mx - x
+    fin = np.isfinite(d)
+    e = np.where(fin, np.exp(-np.where(fin, d, 0.0)), 0.0)
+    p = e / e.sum(-1, keepdims=True)
+    rel = (np.where(fin, d, 0.0) + chains + c0) * 2.0 ** -23
+    bp = np.where(fin, rel * p + (c0 + 1) * TINY32, 0.0)  # exp(-inf) = 0 exactly
+    p2 = p * p
+    bp2 = np.where(fin, 2 * p * bp + bp * bp + u * (p + bp) ** 2 + TINY32, 0.0)
+    a = p + 1e-15
+    L = np.log(a)
+    ra = (bp + u * 1e-15) / a + u
+    bL = ra / (1 - ra) + c0 * 2.0 ** -23 * np.abs(L)
+    t = p * L
+    bt = np.where(fin, bp * (np.abs(L) + bL) + p * bL + u * (np.abs(t) + bp * np.abs(L)) + TINY32, 0.0)
+    ent = -t.sum(-1)
+    b_ent = bt.sum(-1) + (chains + 9) * u * (np.abs(t) + bt).sum(-1)
+
+    def acc(v, b):  # S additions into an f32 word: u32 times every running sum
+        return v.sum(0), b.sum(0) + u * np.cumsum(np.abs(v) + b, axis=0).sum(0)
+    out = {}
+    out["sum_p"], out["b_sum_p"] = acc(p, bp)
+    out["sum_p2"], out["b_sum_p2"] = acc(p2, bp2)
+    out["ent"], out["b_ent"] = acc(ent, b_ent)
+    out["p"], out["bp"] = p, bp
+    return out
+
+
+def kl_reference(mu, rho, pm, ps, g, c0=C0_ULP):
+    """one item of btx_kl_gauss_model[_bwd] in float64 numpy: pm / ps scalars or arrays, g the upstream gradient ->
+    (mean KL, dmu, b_dmu, drho, b_drho)"""
+    u = REF32_UNIT
+    mu, rho = np.asarray(mu, dtype=np.float64), np.asarray(rho, dtype=np.float64)
+    pm, ps = np.asarray(pm, dtype=np.float64), np.asarray(ps, dtype=np.float64)
+    n = mu.size
+    sig = np.logaddexp(0.0, rho)
+    dsig = 1.0 / (1.0 + np.exp(-rho))
+    kl = (np.log(ps) - np.log(sig) + (sig * sig + (mu - pm) ** 2) / (2 * ps * ps) - 0.5).sum() / n
+    gn = float(g) / n
+    dmu = gn * (mu - pm) / (ps * ps)
+    drho = gn * (sig / (ps * ps) - 1.0 / sig) * dsig
+    c1 = 12 + 2 * c0
+    b_drho = (c1 * u + DELTA_W) * abs(gn) * (sig / (ps * ps) + 1.0 / sig) * dsig
+    return kl, dmu, 8 * u * np.abs(dmu), drho, b_drho
+
+
+def avgpool_exact(x, dtype):
+    """global average pool of integer x [NB, HW, C] as the kernel spells it: f32(sum) * f32(1 / HW), then the store's rounding"""
+    hw = x.shape[1]
+    s = _np(x).sum(1).astype(np.float32)
+    inv = np.float32(1.0) / np.float32(hw)
+    return torch.from_numpy((s * inv).astype(np.float32)).to(dtype)

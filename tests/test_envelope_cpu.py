@@ -418,3 +418,376 @@ def test_constants_are_the_derived_ones():
     assert E.rel_constant("f32", 576, delta_w=1e-6, ref_f32=True) == 1e-6 + 584 * 2.0 ** -23 + 584 * 2.0 ** -24
     assert E.rel_constant("f32", 200704) > 1e-2  # the known limit: vacuous for the weight gradient at size
     assert np.isclose(E.rel_constant("f32", 576), 7e-5, rtol=0.01)
+
+
+# =============================================================================================================================
+# the reducing kernels (BatchNorm training, MC accumulate, KL gradients, global average pool): numpy f32 emulations in the
+# summation shape their file headers describe, under HALF of the envelopes of envelope.py; planted faults that the per-element
+# checks flag and the rel-L2 / atol bars of the older GPU tests let through
+# =============================================================================================================================
+F32 = np.float32
+BAR_BN_BF16 = 1e-2   # tests/test_gpu_backward.py BN_CASES, bf16
+BAR_MC_ATOL = 1e-5   # the MC statistics against torch's f32 softmax
+BAR_KL_GRAD = 1e-5   # tests/test_gpu_backward.py: rel-L2 of the KL gradients per tensor
+
+
+def _bf(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(torch.bfloat16).float().numpy()
+
+
+def _fma(a, b, c):
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F32)
+
+
+def _bn_sums(v0, v1_of, M, C, rows):
+    """btx_bn.hip's two sums per channel: thread (block b, row slot r) takes rows b*rpb + r + k*nblk*rpb in order (f32), the block
+    folds its rpb slots in order (f32), the blocks are folded in f64.  rows: the rows the sums visit (a fault drops / repeats one)"""
+    cg = C // 8
+    rpb = max(256 // cg, 1)
+    nblk = min(max(-(-M // (rpb * 8)), 1), 512)
+    slab = nblk * rpb
+    s0 = np.zeros((slab, C), F32)
+    s1 = np.zeros((slab, C), F32)
+    for k in range(-(-len(rows) // slab)):
+        rw = rows[k * slab:(k + 1) * slab]
+        a, b = v0(rw), v1_of(rw)
+        s0[:len(rw)] = s0[:len(rw)] + a
+        s1[:len(rw)] = _fma(b[0], b[1], s1[:len(rw)])
+    s0, s1 = s0.reshape(nblk, rpb, C), s1.reshape(nblk, rpb, C)
+    a0, a1 = np.zeros((nblk, C), F32), np.zeros((nblk, C), F32)
+    for r in range(rpb):
+        a0, a1 = a0 + s0[:, r], a1 + s1[:, r]
+    return a0.astype(np.float64).sum(0), a1.astype(np.float64).sum(0)
+
+
+def emu_bn(x, gamma, beta, eps, dy=None, res=None, relu=False, bf16=False, rows=None, skip_last_group=False, mask_ge=False,
+           pivot_row0=False):
+    """training-mode BatchNorm forward (+ backward when dy is given) of x [M, C] (f32 numpy holding the dtype-rounded values) as
+    btx_bn.hip computes it -> dict(y, mean, invstd, var_unb[, dx, dgamma, dbeta, dres])"""
+    M, C = x.shape
+    rows = np.arange(M) if rows is None else rows
+    piv = x[0].copy() if pivot_row0 else np.median(np.stack([x[0], x[M // 2], x[M - 1]]), axis=0).astype(F32)
+    s, q = _bn_sums(lambda rw: x[rw] - piv, lambda rw: (x[rw] - piv, x[rw] - piv), M, C, rows)
+    ms = s / M
+    m = piv.astype(np.float64) + ms
+    var = np.maximum(q / M - ms * ms, 0.0)
+    invstd = (1.0 / np.sqrt(var + np.float64(F32(eps)))).astype(F32)
+    mean = m.astype(F32)
+    g = np.ones(C, F32) if gamma is None else gamma.astype(F32)
+    b = np.zeros(C, F32) if beta is None else beta.astype(F32)
+    sc = g * invstd
+    shift = b - mean * sc
+    pre = _fma(np.broadcast_to(sc, x.shape), x, np.broadcast_to(shift, x.shape))
+    if skip_last_group:
+        pre[:, -8:] = x[:, -8:]
+    if res is not None:
+        pre = pre + res
+    y = np.where(pre < 0, F32(0), pre) if relu else pre
+    out = dict(y=_bf(y) if bf16 else y, mean=mean, invstd=invstd, var_unb=(var * M / (M - 1)).astype(F32))
+    if dy is None:
+        return out
+    mask = ((pre >= 0) if mask_ge else (y > 0)).astype(F32) if relu else np.ones_like(x)
+    gy = dy * mask
+    s, q = _bn_sums(lambda rw: gy[rw], lambda rw: (gy[rw], (x[rw] - mean) * invstd), M, C, rows)
+    is64, mu64 = invstd.astype(np.float64), mean.astype(np.float64)
+    A = g.astype(np.float64) * is64
+    B = -A * is64 * q / M
+    D = -A * s / M - B * mu64
+    A, B, D = (np.broadcast_to(v.astype(F32), x.shape) for v in (A, B, D))
+    dx = _fma(A, gy, _fma(B, x, D))
+    out.update(dx=_bf(dx) if bf16 else dx, dgamma=q.astype(F32), dbeta=s.astype(F32), dres=gy)
+    return out
+
+
+BN_EMU_SHAPES = [(2, 8), (3, 2040), (105, 40), (1023, 72), (257, 1024), (256, 1024), (4099, 2048)]
+
+
+def _bn_inputs(M, C, seed, bf16, mean=0.3, std=1.7):
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    x, dy, res = rn(M, C) * std + mean, rn(M, C), rn(M, C)
+    gamma, beta = 0.5 + torch.rand(C, generator=g), 0.2 * rn(C)
+    if bf16:
+        x, dy, res = _r(x), _r(dy), _r(res)
+    return x, dy, res, gamma, beta
+
+
+def _bn_check_all(got, x, dy, res, gamma, beta, relu, bf16, half=False):
+    """every output of emu_bn against bn_forward64 / bn_backward64 -> {name: Report}"""
+    M, C = x.shape
+    K = E.bn_chain(M, C)
+    f = E.bn_forward64(E.d64(x), gamma, beta, 1e-5, K, residual=E.d64(res) if res is not None else None, relu=relu)
+    mask = torch.from_numpy((got["y"] > 0).astype(np.float64)) if relu else None
+    bw = E.bn_backward64(E.d64(x), E.d64(dy), f, K, mask=mask)
+    M1 = M / (M - 1.0)
+    h = 0.5 if half else 1.0  # the f32 arithmetic has to leave half of its share; one bf16 store fills its own
+    pairs = [("y", got["y"], f["y"], E.store_rounding(h * f["b_y"], f["y"]) if bf16 else h * f["b_y"]),
+             ("save_mean", got["mean"], f["mean"], h * f["d_mean"]), ("save_invstd", got["invstd"], f["invstd"], h * f["d_invstd"]),
+             ("var_unb", got["var_unb"], f["var"] * M1, h * (f["dv_stat"] * M1 + E.REF32_UNIT * f["var"] * M1)),
+             ("dx", got["dx"], bw["dx"], E.store_rounding(h * bw["b_dx"], bw["dx"]) if bf16 else h * bw["b_dx"]),
+             ("dgamma", got["dgamma"], bw["dgamma"], h * (bw["b_dgamma"] + E.REF32_UNIT * bw["dgamma"].abs())),
+             ("dbeta", got["dbeta"], bw["dbeta"], h * (bw["b_dbeta"] + E.REF32_UNIT * bw["dbeta"].abs()))]
+    return {name: E.check(a, r, b) for name, a, r, b in pairs}
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("shape", BN_EMU_SHAPES, ids=lambda s: "%dx%d" % s)
+def test_clean_batchnorm_emulation_stays_under_half_the_envelope(shape, bf16):
+    M, C = shape
+    for relu in (False, True):
+        x, dy, res, gamma, beta = _bn_inputs(M, C, 21, bf16)
+        res = res if relu else None
+        got = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5, dy.numpy(), res.numpy() if relu else None, relu, bf16)
+        reps = _bn_check_all(got, x, dy, res, gamma, beta, relu, bf16, half=True)
+        for name, rep in reps.items():
+            print(rep.line("emu bn %dx%d %s%s" % (M, C, name, " res_relu" if relu else ""), "bf16" if bf16 else "f32"))
+        assert all(r.ok for r in reps.values()), {k: str(v) for k, v in reps.items() if not v.ok}
+
+
+@pytest.mark.parametrize("what", ["dropped", "doubled"])
+def test_a_row_dropped_or_doubled_in_the_batchnorm_sums_is_flagged_where_rel_l2_is_blind(what):
+    """M = 25 088 (8 x 56 x 56), bf16 activations: one row missing from (or counted twice in) the sums moves mean and variance by
+    ~1/M.  Every quantity the rel-L2 test of BatchNorm bars at 1e-2 — y, dx, dgamma, dbeta and the running estimates at momentum
+    0.1 — stays under that bar; the per-channel statistics leave their envelope and, with integer dy, dbeta is not the exact sum
+    any more"""
+    M, C = 25088, 64
+    x, _, _, gamma, beta = _bn_inputs(M, C, 22, True)
+    dyi = E.small_ints((M, C), 23)
+    rows = np.delete(np.arange(M), 2500) if what == "dropped" else np.insert(np.arange(M), 2500, 2500)
+    clean = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5, dyi.numpy(), bf16=True)
+    bad = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5, dyi.numpy(), bf16=True, rows=rows)
+    assert all(r.ok for r in _bn_check_all(clean, x, dyi, None, gamma, beta, False, True).values())
+    reps = _bn_check_all(bad, x, dyi, None, gamma, beta, False, True)
+    print("bn row %s: save_mean %s | var %s" % (what, reps["save_mean"], reps["var_unb"]))
+    assert not reps["save_mean"].ok and reps["save_mean"].violations > 0.9 * C
+    assert not reps["var_unb"].ok
+    ref_dbeta = E.d64(dyi).sum(0)
+    assert E.check_exact(clean["dbeta"], ref_dbeta).ok and not E.check_exact(bad["dbeta"], ref_dbeta).ok
+    K = E.bn_chain(M, C)
+    f = E.bn_forward64(E.d64(x), gamma, beta, 1e-5, K)
+    bw = E.bn_backward64(E.d64(x), E.d64(dyi), f, K)
+    g = torch.Generator().manual_seed(27)
+    rm0, rv0 = 0.1 * torch.randn(C, generator=g), 0.5 + torch.rand(C, generator=g)
+    rm, _, rv, _ = E.bn_running64(f, rm0, rv0, 0.1)
+    bad["rm"] = F32(0.9) * rm0.numpy() + F32(0.1) * bad["mean"]
+    bad["rv"] = F32(0.9) * rv0.numpy() + F32(0.1) * bad["var_unb"]
+    errs = {k: rel_l2(bad[k], ref.numpy()) for k, ref in (("y", f["y"]), ("dx", bw["dx"]), ("dgamma", bw["dgamma"]),
+                                                          ("dbeta", bw["dbeta"]), ("rm", rm), ("rv", rv))}
+    print("bn row %s: rel-L2 %s (bar %.0e)" % (what, ", ".join("%s %.2e" % kv for kv in errs.items()), BAR_BN_BF16))
+    for k, v in errs.items():
+        assert v < BAR_BN_BF16, (k, v)
+
+
+def test_pivot_of_the_shifted_sums_row_zero_alone_against_the_median_of_three():
+    """one row-0 value 300 away from a unit-spread channel (eight channels of 64), M = 25 088, f32: with the pivot taken from row
+    0 alone the emulated sums lose more than 1e-4 of the variance of those channels; the median of rows 0, M/2, M-1 keeps it to
+    f32 rounding.  The figures printed here are the emulated ones quoted in btx_bn.hip, DESIGN.md and the profile file."""
+    g = torch.Generator().manual_seed(131)
+    x = torch.randn(25088, 64, generator=g) + 0.3
+    x[0, :8] += torch.tensor([300.0, -300.0] * 4)
+    M = x.shape[0]
+    x64 = x.double()
+    unb = (((x64 - x64.mean(0)) ** 2).sum(0) / (M - 1)).numpy()
+    err = {}
+    for row0 in (True, False):
+        got = emu_bn(x.numpy(), None, None, 1e-5, pivot_row0=row0)["var_unb"].astype(np.float64)
+        err[row0] = np.abs(got - unb) / unb
+        print("emulated variance error, pivot = %s: outlier channels %.3g, other channels %.3g"
+              % ("row 0" if row0 else "median of rows 0, M/2, M-1", err[row0][:8].max(), err[row0][8:].max()))
+    assert err[True][:8].max() > 1e-4 and err[True][8:].max() < 1e-6
+    assert err[False].max() < 1e-6
+
+
+def test_last_channel_group_left_unnormalised_is_flagged_where_rel_l2_is_blind():
+    """C = 2048 on activations that are close to normalised already (what a BatchNorm sees behind another one): the last eight
+    channels pass through untouched — 3e-3 rel-L2 of y, under the bf16 bar; every one of their elements is outside the envelope"""
+    M, C = 96, 2048
+    x, dy, _, _, _ = _bn_inputs(M, C, 24, True, mean=0.02, std=1.05)
+    gamma, beta = torch.ones(C), torch.zeros(C)
+    bad = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5, dy.numpy(), bf16=True, skip_last_group=True)
+    rep = _bn_check_all(bad, x, dy, None, gamma, beta, False, True)["y"]
+    f = E.bn_forward64(E.d64(x), gamma, beta, 1e-5, E.bn_chain(M, C))
+    r = rel_l2(bad["y"], f["y"].numpy())
+    print("bn last group unnormalised: %s | rel-L2 %.3g (bar %.0e)" % (rep, r, BAR_BN_BF16))
+    assert not rep.ok and rep.index[1] >= C - 8 and rep.violations > 0.5 * 8 * M
+    assert r < BAR_BN_BF16, r
+
+
+def test_relu_mask_taken_as_greater_or_equal_is_flagged_by_the_exact_check():
+    """torch's threshold_backward passes the gradient where y > 0.  Three pre-activations are made exactly 0 (the residual
+    cancels fma(sc, x, shift) in f32): a mask y >= 0 lets dy through there — three elements of 73 656, 4e-3 in rel-L2 and under
+    its 1e-2 bar, and exactly what dres == dy * [y > 0] on the stored y catches"""
+    M, C = 1023, 72
+    x, _, res, gamma, beta = _bn_inputs(M, C, 25, False)
+    dy = E.small_ints((M, C), 26)
+    dy[dy == 0] = 1.0
+    probe = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5)
+    resn = res.numpy().copy()
+    where = [(3, 5), (17, 63), (1022, 71)]
+    for r_, c_ in where:
+        resn[r_, c_] = -probe["y"][r_, c_]
+        dy[r_, c_] = 1.0
+    for ge in (False, True):
+        got = emu_bn(x.numpy(), gamma.numpy(), beta.numpy(), 1e-5, dy.numpy(), resn, True, False, mask_ge=ge)
+        assert all(got["y"][r_, c_] == 0 for r_, c_ in where)
+        want = dy.numpy() * (got["y"] > 0)
+        rep = E.check_exact(got["dres"], want)
+        assert rep.ok != ge and rep.violations == (3 if ge else 0), str(rep)
+        assert E.check_exact(got["dbeta"], want.astype(np.float64).sum(0)).ok != ge
+        assert rel_l2(got["dres"], want) < 1e-2
+
+
+# ---- MC accumulate ------------------------------------------------------------------------------------------------------------
+def _tree64(v):
+    """the shuffle tree of a 64-lane wave: lane i += lane i + off for off = 32 .. 1; lane 0 holds the sum"""
+    v = v.copy()
+    for off in (32, 16, 8, 4, 2, 1):
+        v[..., :off] = v[..., :off] + v[..., off:2 * off]
+    return v[..., 0]
+
+
+def _chains(v):
+    """column c of a row belongs to virtual wave (c / 64) % 4, lane c % 64; a lane adds its columns in order -> [4]"""
+    C = v.shape[0]
+    n = -(-C // 256)
+    pad = np.zeros(n * 256, F32)
+    pad[:C] = v
+    pad = pad.reshape(n, 4, 64)
+    s = np.zeros((4, 64), F32)
+    for k in range(n):
+        s = s + pad[k]
+    t = _tree64(s)
+    return ((t[0] + t[1]) + t[2]) + t[3]
+
+
+def emu_mc(x, skip_col=None):
+    """btx_mc_accumulate_lanes on x [S, bs, C] (f32 numpy, the dtype-rounded logits) -> (sum_p, sum_p2 [bs, C], ent [bs]) in f32"""
+    S, bs, C = x.shape
+    sp, sp2, ent = np.zeros((bs, C), F32), np.zeros((bs, C), F32), np.zeros(bs, F32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for s in range(S):
+            for r in range(bs):
+                lr = x[s, r]
+                ev = np.exp(lr - lr.max()).astype(F32)
+                es = ev.copy()
+                if skip_col is not None:
+                    es[skip_col] = 0
+                inv = F32(1) / _chains(es)
+                pv = ev * inv
+                t = pv * np.log(pv + F32(1e-15))
+                sp[r] = sp[r] + pv
+                sp2[r] = sp2[r] + pv * pv
+                ent[r] = ent[r] + _chains(-t)
+    return sp, sp2, ent
+
+
+def _mc_logits(S, bs, C, seed, bf16, spread=None):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(S, bs, C, generator=g) * 2.0
+    if spread:
+        x = (torch.rand(S, bs, C, generator=g) * 2 - 1) * spread
+    return _r(x) if bf16 else x
+
+
+def _mc_check(got, ref, scale=1.0):
+    return {k: E.check(g, ref[k], ref["b_" + k] * scale) for k, g in zip(("sum_p", "sum_p2", "ent"), got)}
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32", "bf16"])
+@pytest.mark.parametrize("C", [1, 2, 63, 64, 65, 255, 256, 257, 1000, 1025, 4099])
+def test_clean_mc_emulation_stays_under_half_the_envelope(C, bf16):
+    x = _mc_logits(3, 2, C, 31 + C, bf16)
+    reps = _mc_check(emu_mc(x.numpy()), E.mc_reference(x.double().numpy()), 0.5)
+    for k, rep in reps.items():
+        print(rep.line("emu mc C=%d %s" % (C, k), "bf16" if bf16 else "f32"))
+    assert all(r.ok for r in reps.values()), {k: str(v) for k, v in reps.items() if not v.ok}
+
+
+def test_clean_mc_emulation_with_wide_logits_and_minus_infinity():
+    x = _mc_logits(1, 3, 257, 41, False, spread=80.0)
+    x[0, 1, 5:40] = float("-inf")
+    ref = E.mc_reference(x.double().numpy())
+    assert float((ref["p"] < 1e-45).mean()) > 0.3  # a third of the classes underflow f32 altogether, most of the rest are tiny
+    reps = _mc_check(emu_mc(x.numpy()), ref, 0.5)
+    assert all(r.ok for r in reps.values()), {k: str(v) for k, v in reps.items() if not v.ok}
+    assert (emu_mc(x.numpy())[0][1, 5:40] == 0).all() and (ref["b_sum_p"][1, 5:40] == 0).all()
+
+
+def test_a_class_column_missing_from_the_softmax_sum_is_flagged_where_atol_is_blind():
+    """C = 1000: column 777 (past three strides of 256) never reaches the row sum.  Every probability of the row is 1e-3 too
+    large in relative terms — 1e-6 in absolute ones, under the atol 1e-5 of the older test; the relative envelope is 1e-6"""
+    x = _mc_logits(1, 2, 1000, 42, False)
+    ref = E.mc_reference(x.double().numpy())
+    got = emu_mc(x.numpy(), skip_col=777)
+    reps = _mc_check(got, ref)
+    print("mc column missing: %s" % reps["sum_p"])
+    assert not reps["sum_p"].ok and reps["sum_p"].violations > 0.9 * 2000 and not reps["ent"].ok
+    assert float(np.abs(got[0] - ref["sum_p"]).max()) < BAR_MC_ATOL
+
+
+# ---- KL gradients -------------------------------------------------------------------------------------------------------------
+def emu_kl_bwd(mu, rho, pm, ps, g, n=None):
+    """kl_model_bwd_kernel in f32 numpy; n: the count the mean is scaled by (a fault hands in a neighbour's)"""
+    mu, rho, pm, ps = (np.asarray(v, dtype=F32) for v in (mu, rho, pm, ps))
+    gn = F32(g) / F32(mu.size if n is None else n)
+    sig = np.log1p(np.exp(rho)).astype(F32)
+    dsig = F32(1) / (F32(1) + np.exp(-rho).astype(F32))
+    ips2 = F32(1) / (ps * ps)
+    return gn * (mu - pm) * ips2, gn * (sig * ips2 - F32(1) / sig) * dsig
+
+
+def _kl_inputs(n, seed, tensor_priors):
+    g = torch.Generator().manual_seed(seed)
+    mu = torch.randn(n, generator=g).numpy()
+    rho = (torch.rand(n, generator=g) * 40 - 20).numpy()
+    if tensor_priors:
+        return mu, rho, (0.3 * torch.randn(n, generator=g)).numpy(), (0.2 + torch.rand(n, generator=g)).numpy()
+    return mu, rho, F32(0.1), F32(0.7)
+
+
+@pytest.mark.parametrize("tensor_priors", [False, True], ids=["scalar-priors", "tensor-priors"])
+@pytest.mark.parametrize("n", [1, 3, 2049])
+def test_clean_kl_gradient_emulation_stays_under_half_the_envelope(n, tensor_priors):
+    mu, rho, pm, ps = _kl_inputs(n, 51 + n, tensor_priors)
+    dmu, drho = emu_kl_bwd(mu, rho, pm, ps, 1.7)
+    _, rmu, bmu, rrho, brho = E.kl_reference(mu, rho, pm, ps, float(F32(1.7)))
+    for name, rep in (("dmu", E.check(dmu, rmu, bmu / 2)), ("drho", E.check(drho, rrho, brho / 2))):
+        print(rep.line("emu kl n=%d %s" % (n, name), "f32"))
+        assert rep.ok, str(rep)
+
+
+def test_kl_gradient_scaled_by_a_neighbours_count_is_flagged_where_rel_l2_is_blind():
+    """two tensors of 150 001 and 150 000 elements: the first one's gradient divided by the second one's n is 6.7e-6 off in
+    every element — under the 1e-5 rel-L2 bar; dmu's envelope is 8 roundings"""
+    n = 150001
+    mu, rho, pm, ps = _kl_inputs(n, 55, False)
+    dmu, drho = emu_kl_bwd(mu, rho, pm, ps, 1.0, n=n - 1)
+    _, rmu, bmu, rrho, brho = E.kl_reference(mu, rho, pm, ps, 1.0)
+    rep = E.check(dmu, rmu, bmu)
+    print("kl neighbour's n: %s | rel-L2 %.3g" % (rep, rel_l2(dmu, rmu)))
+    assert not rep.ok and rep.violations > 0.9 * n
+    assert rel_l2(dmu, rmu) < BAR_KL_GRAD and rel_l2(drho, rrho) < BAR_KL_GRAD
+    assert E.check(emu_kl_bwd(mu, rho, pm, ps, 1.0)[0], rmu, bmu / 2).ok
+
+
+# ---- global average pool ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hw", [1, 31, 32, 33, 1000])
+def test_avgpool_emulation_on_integers_is_exact_and_a_dropped_pixel_group_is_not(hw):
+    """32 pixel groups (pixel p belongs to group p % 32), f32 sums, a fixed-order fold: integers make every order exact"""
+    x = E.small_ints((3, hw, 72), 61 + hw)
+    xn = x.numpy()
+    parts = np.stack([xn[:, g::32].sum(1, dtype=F32) if g < hw else np.zeros((3, 72), F32) for g in range(32)])
+    s = np.zeros((3, 72), F32)
+    for g in range(32):
+        s = s + parts[g]
+    got = s * (F32(1) / F32(hw))
+    for dt in (torch.float32, torch.bfloat16):
+        assert E.check_exact(torch.from_numpy(got).to(dt), E.avgpool_exact(x, dt)).ok
+    bad = (s - parts[min(hw, 32) - 1]) * (F32(1) / F32(hw))
+    assert not E.check_exact(bad, E.avgpool_exact(x, torch.float32)).ok or not parts[min(hw, 32) - 1].any()
+
+
+def test_reduction_constants_are_the_derived_ones():
+    assert E.bn_chain(25088, 64) == 8 + 32 and E.bn_chain(4099, 2048) == 9 + 1 and E.bn_chain(8200, 2048) == 17 + 1
+    assert E.bn_chain(257, 1024) == 8 + 2 and E.bn_chain(2, 8) == 1 + 256
+    assert list(E.ulp32(np.array([1.0, 0.75, 3.0, 0.0, 1e-45]))) == [2.0 ** -23, 2.0 ** -24, 2.0 ** -22, 2.0 ** -149, 2.0 ** -149]

@@ -12,9 +12,9 @@ say WHICH element is wrong: no element is excluded, there is no percentile and n
                  itself.  Their relative error against float64 IS delta_w (envelope.DELTA_W = 2 x the maximum measured here).
 
 Left on rel-L2, on purpose: the LSTM sequences (test_gpu_lstm_*.py) — the recurrence is nonlinear, no per-element bound follows
-from first principles, and btx_lstm_bwd cannot be fed integers end to end (its gates are transcendental); mc_accumulate — a
-softmax, so integer logits do not make it exact (its lanes are pinned bit for bit against sequential launches in
-test_gpu_lanes.py).  The stem + max-pool launch cannot be read back by an impulse (BN, ReLU and the pool sit between the weights
+from first principles, and btx_lstm_bwd cannot be fed integers end to end (its gates are transcendental).  The reducing kernels
+— training BatchNorm, mc_accumulate, the KL gradients, the global average pool — have their own file, test_gpu_reductions.py.
+The stem + max-pool launch cannot be read back by an impulse (BN, ReLU and the pool sit between the weights
 and the store): its envelope runs through BN + ReLU + store + pool at batch 64 instead.
 
 Each check prints one line `name prec: worst err/bound R at (n, c, h, w)`; profiles/elementwise_envelope.txt holds the lines of
