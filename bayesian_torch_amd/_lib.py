@@ -83,6 +83,11 @@ class KlItem(ctypes.Structure):
                 ("prior_mu", ctypes.c_float), ("prior_sigma", ctypes.c_float), ("n", ctypes.c_size_t)]
 
 
+class Q8Chain(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("s_sigma", "s_mu", "s_eps", "inv_s_eps", "s_d", "inv_s_d", "inv_s_w")] + \
+               [("bias_div", ctypes.c_double)]
+
+
 EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_gauss", "btx_kl_model_workspace_bytes",
            "btx_kl_gauss_model", "btx_kl_gauss_model_bwd", "btx_contract_wgrad",
            "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_contract_plan_info", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
@@ -91,7 +96,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_wgrad_workspace_bytes", "btx_contract_wgrad_ws", "btx_maxpool2d_cl_train", "btx_maxpool2d_cl_bwd",
            "btx_lstm_workspace_bytes", "btx_lstm_fwd", "btx_lstm_train_saved_bytes", "btx_lstm_train_workspace_bytes",
            "btx_lstm_fwd_train", "btx_lstm_bwd",
-           "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd")
+           "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd",
+           "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract")
 
 
 def lib_path():
@@ -213,6 +219,15 @@ def lib():
     L.btx_eau_fwd.argtypes = [vp, vp, i32, i32, f32, vp, f32, vp, f32, vp, vp, sz, vp]
     L.btx_eau_bwd.restype = i32
     L.btx_eau_bwd.argtypes = [vp, vp, i32, i32, vp, vp, sz, vp, vp, vp]
+    L.btx_q8_weight_row_bytes.restype = sz
+    L.btx_q8_weight_row_bytes.argtypes = [i32, i32]
+    L.btx_q8_quantize_act.restype = i32
+    L.btx_q8_quantize_act.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int64), vp, i32, i32, i32, i32, f32, i32, vp]
+    L.btx_q8_sample_weights.restype = i32
+    L.btx_q8_sample_weights.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(Q8Chain), ctypes.POINTER(Rng), vp, vp,
+                                        vp, vp, vp, vp]
+    L.btx_q8_contract.restype = i32
+    L.btx_q8_contract.argtypes = [ctypes.POINTER(Geom), vp, i32, vp, vp, vp, f32, i32, i32, i32, f32, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

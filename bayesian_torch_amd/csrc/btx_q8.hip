@@ -1,0 +1,388 @@
+// K10: INT8 inference (BTX-Q8 v1) for Linear / Conv2d Reparameterization layers.
+// Reference op chain (CPU quantized engines): layers/variational_layers/quantize_linear_variational.py:134-224 and
+// quantize_conv_variational.py:457-552 — quantize eps, quantized.mul, quantized.add, quantized linear / conv2d.
+//
+// Three kernels:
+//   q8_quantize_act_kernel   f32 / bf16 activations of any 4-D strides -> uint8 channels-last
+//   q8_sample_kernel         one launch per layer: eps -> eps_i -> d_i -> W_i (int8, [N][Kp], k = tap * Cp + c, Cp = C rounded up
+//                            to 16, Kp = taps * Cp rounded up to 64, padding zero), the row sums S_n and the int32 bias b_i
+//   q8_contract_kernel       implicit GEMM on v_mfma_i32_16x16x64_i8.  Activations stay uint8 in memory and become x - 128 (int8)
+//                            with one xor on the way into LDS; the epilogue adds (128 - z_x) * S_n, which makes every input zero
+//                            point exact on the signed x signed instruction; out-of-image taps and the K tail hold the byte z_x
+//                            (value 0 after the correction; the tail meets zero weights).
+//
+// Numerics: every floating step is ONE f32 operation, round to nearest even, never contracted (__fmul_rn / __fadd_rn, and this unit is
+// built with -ffp-contract=off); rintf is half-to-even.  The integer sums are exact, so their order does not matter.
+//
+// The MFMA computes D^T = W * X^T: the weight tile is the A operand (row = output channel), the activation tile the B operand
+// (column = output pixel).  A lane then owns 4 CONSECUTIVE output channels of one pixel (C/D map: col = lane & 15,
+// row = 4 * (lane >> 4) + reg), i.e. one 4-byte (uint8) or 16-byte (f32) store.  Both operands are read with the same
+// (lane >> 4, byte) -> k map (16 consecutive k per lane), so the product does not depend on how the instruction orders k inside a step.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/btx.h"
+#include "btx_rng.h"
+
+namespace {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int Q8_BM = 64;     // output pixels per workgroup
+constexpr int Q8_BN = 64;     // output channels per workgroup
+constexpr int Q8_BK = 64;     // one MFMA K step
+constexpr int Q8_LDS_ROW = 80;  // 64 bytes of k + 16 of padding: 16-byte aligned rows that do not all start in one bank
+
+__device__ __forceinline__ float q8_round_clamp(float v, float inv_s, float z, float lo, float hi) {
+  return fminf(fmaxf(__fadd_rn(rintf(__fmul_rn(v, inv_s)), z), lo), hi);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// activation quantize
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ float q8_ldf(const T* p);
+template <> __device__ __forceinline__ float q8_ldf<float>(const float* p) { return *p; }
+template <> __device__ __forceinline__ float q8_ldf<uint16_t>(const uint16_t* p) { return __uint_as_float((uint32_t)(*p) << 16); }
+
+template <typename T>
+__global__ __launch_bounds__(256) void q8_quantize_act_kernel(const T* __restrict__ x, uint8_t* __restrict__ out, int C, int H, int W,
+                                                              long long sn, long long sc, long long sh, long long sw, size_t total,
+                                                              float inv_s, float zp) {
+  // one thread per 4 consecutive output bytes (channels-last order); total is the element count
+  const size_t ngrp = (total + 3) >> 2;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < ngrp; g += (size_t)gridDim.x * 256) {
+    uint32_t pack = 0;
+    const size_t base = g << 2;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const size_t i = base + e;
+      if (i < total) {
+        const int c = (int)(i % (size_t)C);
+        size_t p = i / (size_t)C;
+        const int w = (int)(p % (size_t)W); p /= (size_t)W;
+        const int h = (int)(p % (size_t)H);
+        const size_t n = p / (size_t)H;
+        const float v = q8_ldf<T>(x + (long long)n * sn + (long long)c * sc + (long long)h * sh + (long long)w * sw);
+        pack |= (uint32_t)(int)q8_round_clamp(v, inv_s, zp, 0.0f, 255.0f) << (8 * e);
+      }
+    }
+    if (base + 4 <= total) {
+      *reinterpret_cast<uint32_t*>(out + base) = pack;
+    } else {
+      for (int e = 0; base + e < total; ++e) out[base + e] = (uint8_t)(pack >> (8 * e));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// weight sampling pre-pass: one workgroup per output channel
+// ---------------------------------------------------------------------------------------------------------------------
+struct Q8SampleArgs {
+  const int8_t* mu_i; const int8_t* sigma_i;   // [N][taps][C]
+  const float* mu_b; const float* sigma_b;     // [N] or NULL
+  const float* eps_w; const float* eps_b;      // explicit noise ([N][taps][C] / [N]) or NULL -> BTX-RNG v1
+  int8_t* W; int32_t* S; int32_t* b_i;
+  int N, taps, C, eps_C, Cp, Kp;
+  BtxQ8Chain ch;
+  uint32_t k0, k1, sample, layer;
+  const uint32_t* sample_ptr;
+};
+
+__global__ __launch_bounds__(256) void q8_sample_kernel(const Q8SampleArgs a) {
+  __shared__ int red[256];
+  uint32_t sample = a.sample;
+  if (a.sample_ptr) sample = __builtin_amdgcn_readfirstlane(*a.sample_ptr);  // BtxRng.sample_idx_dev (captured graphs)
+  const int n = blockIdx.x;
+  const int8_t* mu = a.mu_i + (size_t)n * a.taps * a.C;
+  const int8_t* sg = a.sigma_i + (size_t)n * a.taps * a.C;
+  int8_t* wrow = a.W + (size_t)n * a.Kp;
+  int sum = 0;
+  for (int p = threadIdx.x * 4; p < a.Kp; p += 256 * 4) {  // 4 consecutive k per thread: one Philox block, one 4-byte store
+    const int tap = p / a.Cp, c0 = p - tap * a.Cp;
+    uint32_t pack = 0;
+    if (tap < a.taps && c0 < a.C) {
+      float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (!a.eps_w)  // the float layer's index space: [N][taps][eps_C], eps_C a multiple of 8 -> c0 .. c0+3 share a block
+        btx_normal4((uint32_t)((((size_t)n * a.taps + tap) * a.eps_C + c0) >> 2), sample, a.layer, BTX_STREAM_EPS_W, a.k0, a.k1, z);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = c0 + e;
+        if (c < a.C) {
+          const size_t src = (size_t)tap * a.C + c;
+          const float eps = a.eps_w ? a.eps_w[(size_t)n * a.taps * a.C + src] : z[e];
+          const float eps_i = q8_round_clamp(eps, a.ch.inv_s_eps, 0.0f, -128.0f, 127.0f);
+          const float t = __fmul_rn(__fmul_rn((float)sg[src], a.ch.s_sigma), __fmul_rn(eps_i, a.ch.s_eps));
+          const float d_i = q8_round_clamp(t, a.ch.inv_s_d, 0.0f, -128.0f, 127.0f);
+          const float u = __fadd_rn(__fmul_rn(d_i, a.ch.s_d), __fmul_rn((float)mu[src], a.ch.s_mu));
+          const int w = (int)q8_round_clamp(u, a.ch.inv_s_w, 0.0f, -128.0f, 127.0f);
+          sum += w;
+          pack |= ((uint32_t)w & 0xffu) << (8 * e);
+        }
+      }
+    }
+    *reinterpret_cast<uint32_t*>(wrow + p) = pack;  // padding (c >= C, k >= taps * Cp) is written as zero
+  }
+  red[threadIdx.x] = sum;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    a.S[n] = red[0];
+    int bi = 0;
+    if (a.mu_b) {
+      float b = a.mu_b[n];
+      if (a.sigma_b) {
+        const float eb = a.eps_b ? a.eps_b[n] : btx_normal1((uint64_t)n, sample, a.layer, BTX_STREAM_EPS_B, a.k0, a.k1);
+        b = __fadd_rn(b, __fmul_rn(a.sigma_b[n], eb));
+      }
+      bi = (int)rint((double)b / a.ch.bias_div);
+    }
+    a.b_i[n] = bi;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// i8 implicit GEMM
+// ---------------------------------------------------------------------------------------------------------------------
+struct Q8ContractArgs {
+  const uint8_t* x; const int8_t* W; const int32_t* S; const int32_t* b_i; void* out;
+  int NB, H, Wd, C, N, KH, KW, sh, sw, ph, pw, dh, dw, OH, OW;
+  int Cp, Kp, taps;
+  long long M;        // NB * OH * OW
+  int z_x, z_o, lo;   // lo: lower clamp (z_o with ReLU, else 0)
+  float mult, s_o;
+  int out_f32, x_vec, out_vec;
+};
+
+__global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a) {
+  // two stages of each tile: step i + 1 is written while slower waves still read step i, so one barrier per step is enough (the
+  // write of step i + 2 into this stage comes after barrier i + 1, which every wave reaches only after its reads of step i)
+  __shared__ __attribute__((aligned(16))) uint8_t lds_w[2][Q8_BN * Q8_LDS_ROW];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_x[2][Q8_BM * Q8_LDS_ROW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * Q8_BM;
+  const int n0 = blockIdx.y * Q8_BN;
+
+  // the 16-byte chunk of each tile this thread stages: row = tid / 4, bytes [16 * (tid & 3), +16)
+  const int lrow = tid >> 2, lq = tid & 3;
+  const long long lm = m0 + lrow;
+  const bool m_ok = lm < a.M;
+  int img = 0, ih0 = 0, iw0 = 0;
+  if (m_ok) {
+    const int ow = (int)(lm % a.OW);
+    const long long t = lm / a.OW;
+    const int oh = (int)(t % a.OH);
+    img = (int)(t / a.OH);
+    ih0 = oh * a.sh - a.ph;
+    iw0 = ow * a.sw - a.pw;
+  }
+  const int ln = n0 + lrow;
+  const uint32_t zfill = (uint32_t)(a.z_x & 0xff) * 0x01010101u;
+
+  v4i acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = (v4i){0, 0, 0, 0};
+
+  // one K step's 16-byte chunks of this thread: the weight chunk (rows of W are Kp bytes, 16-byte aligned; rows >= N read as zero) and
+  // the activation chunk (k = tap * Cp + c; a chunk lies inside one tap because Cp is a multiple of 16), already xor-ed to int8
+  auto load_chunks = [&](int k0, uint4& wv, uint4& xv) {
+    wv = make_uint4(0u, 0u, 0u, 0u);
+    if (ln < a.N) wv = *reinterpret_cast<const uint4*>(a.W + (size_t)ln * a.Kp + k0 + 16 * lq);
+    xv = make_uint4(zfill, zfill, zfill, zfill);
+    const int k = k0 + 16 * lq;
+    const int tap = k / a.Cp, c0 = k - tap * a.Cp;
+    if (m_ok && tap < a.taps && c0 < a.C) {
+      const int kh = tap / a.KW, kw = tap - kh * a.KW;
+      const int ih = ih0 + kh * a.dh, iw = iw0 + kw * a.dw;
+      if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.Wd) {
+        const uint8_t* src = a.x + (((size_t)img * a.H + ih) * a.Wd + iw) * a.C + c0;
+        if (a.x_vec) {  // C % 16 == 0 and a 16-byte aligned base: the whole chunk is in range and aligned
+          xv = *reinterpret_cast<const uint4*>(src);
+        } else {
+          uint32_t wds[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            uint32_t wd = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int c = c0 + 4 * q + e;
+              const uint32_t byte = (c < a.C) ? (uint32_t)src[4 * q + e] : (uint32_t)(a.z_x & 0xff);
+              wd |= byte << (8 * e);
+            }
+            wds[q] = wd;
+          }
+          xv = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+        }
+      }
+    }
+    xv.x ^= 0x80808080u; xv.y ^= 0x80808080u; xv.z ^= 0x80808080u; xv.w ^= 0x80808080u;  // uint8 x -> int8 (x - 128)
+  };
+
+  uint4 wv, xv;
+  load_chunks(0, wv, xv);
+  int stage = 0;
+  for (int k0 = 0; k0 < a.Kp; k0 += Q8_BK, stage ^= 1) {
+    const uint8_t* sw = lds_w[stage];
+    const uint8_t* sx = lds_x[stage];
+    *reinterpret_cast<uint4*>(lds_w[stage] + lrow * Q8_LDS_ROW + 16 * lq) = wv;
+    *reinterpret_cast<uint4*>(lds_x[stage] + lrow * Q8_LDS_ROW + 16 * lq) = xv;
+    __syncthreads();
+    if (k0 + Q8_BK < a.Kp) load_chunks(k0 + Q8_BK, wv, xv);  // the next step's global loads fly under this step's MFMAs
+    // ---- wave `wave` owns pixels [16 * wave, +16) and all 64 channels: 4 MFMAs per step
+    const v4i xf = *reinterpret_cast<const v4i*>(sx + (16 * wave + (lane & 15)) * Q8_LDS_ROW + 16 * (lane >> 4));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const v4i wf = *reinterpret_cast<const v4i*>(sw + (16 * j + (lane & 15)) * Q8_LDS_ROW + 16 * (lane >> 4));
+      acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, xf, acc[j], 0, 0, 0);
+    }
+  }
+
+  // ---- epilogue: lane holds channels n = n0 + 16 j + 4 (lane >> 4) + r of pixel m = m0 + 16 wave + (lane & 15)
+  const long long m = m0 + 16 * wave + (lane & 15);
+  if (m >= a.M) return;
+  const int zc = 128 - a.z_x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int nb = n0 + 16 * j + 4 * (lane >> 4);
+    if (nb >= a.N) continue;
+    float of[4];
+    uint32_t pack = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = nb + r;
+      float o = 0.0f;
+      if (n < a.N) {
+        const int v = acc[j][r] + zc * a.S[n] + a.b_i[n];
+        o = fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)v, a.mult)), (float)a.z_o), (float)a.lo), 255.0f);
+      }
+      pack |= (uint32_t)(int)o << (8 * r);
+      of[r] = __fmul_rn(o - (float)a.z_o, a.s_o);  // o and z_o are small integers: the difference is exact
+    }
+    const size_t off = (size_t)m * a.N + nb;
+    if (a.out_f32) {
+      float* o = reinterpret_cast<float*>(a.out) + off;
+      if (a.out_vec && nb + 4 <= a.N) {
+        *reinterpret_cast<float4*>(o) = make_float4(of[0], of[1], of[2], of[3]);
+      } else {
+        for (int r = 0; r < 4 && nb + r < a.N; ++r) o[r] = of[r];
+      }
+    } else {
+      uint8_t* o = reinterpret_cast<uint8_t*>(a.out) + off;
+      if (a.out_vec && nb + 4 <= a.N) {
+        *reinterpret_cast<uint32_t*>(o) = pack;
+      } else {
+        for (int r = 0; r < 4 && nb + r < a.N; ++r) o[r] = (uint8_t)(pack >> (8 * r));
+      }
+    }
+  }
+}
+
+inline int q8_out_extent(int in, int k, int s, int p, int d) { return (in + 2 * p - d * (k - 1) - 1) / s + 1; }
+
+// geometry checks shared by the size query and the launch: 0 or a BTX_E_* code
+inline int q8_check_geom(const BtxGeom* g) {
+  if (g->NB <= 0 || g->H <= 0 || g->W <= 0 || g->C <= 0 || g->N <= 0 || g->KH <= 0 || g->KW <= 0) return BTX_E_SHAPE;
+  if (g->sh <= 0 || g->sw <= 0 || g->dh <= 0 || g->dw <= 0 || g->ph < 0 || g->pw < 0) return BTX_E_SHAPE;
+  if (g->D != 1 || g->KD != 1) return BTX_E_UNSUPPORTED;   // Linear and Conv2d only
+  if (g->groups != 1) return BTX_E_UNSUPPORTED;
+  if (q8_out_extent(g->H, g->KH, g->sh, g->ph, g->dh) <= 0 || q8_out_extent(g->W, g->KW, g->sw, g->pw, g->dw) <= 0) return BTX_E_SHAPE;
+  return 0;
+}
+
+inline int q8_cp(int C) { return (C + 15) / 16 * 16; }
+inline long long q8_kp(int taps, int C) { return ((long long)taps * q8_cp(C) + 63) / 64 * 64; }
+
+}  // namespace
+
+extern "C" {
+
+size_t btx_q8_weight_row_bytes(int taps, int C) {
+  if (taps <= 0 || C <= 0) return 0;
+  const long long kp = q8_kp(taps, C);
+  return kp > 0x7fffffc0LL ? 0 : (size_t)kp;
+}
+
+int btx_q8_quantize_act(const void* x, int act_dtype, const int64_t* strides_host, uint8_t* out, int NB, int C, int H, int W,
+                        float scale, int zero_point, void* stream) {
+  if (!x || !strides_host || !out) return BTX_E_NULL;
+  if (NB <= 0 || C <= 0 || H <= 0 || W <= 0 || !(scale > 0.0f) || zero_point < 0 || zero_point > 255) return BTX_E_SHAPE;
+  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  if ((uintptr_t)out & 3u) return BTX_E_ALIGN;
+  const size_t total = (size_t)NB * C * H * W;
+  size_t blocks = ((total + 3) / 4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  const float inv_s = 1.0f / scale;
+  const long long sn = strides_host[0], sc = strides_host[1], sh = strides_host[2], sw = strides_host[3];
+  if (act_dtype == BTX_ACT_F32)
+    hipLaunchKernelGGL(q8_quantize_act_kernel<float>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const float*)x, out, C, H, W,
+                       sn, sc, sh, sw, total, inv_s, (float)zero_point);
+  else
+    hipLaunchKernelGGL(q8_quantize_act_kernel<uint16_t>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, out, C,
+                       H, W, sn, sc, sh, sw, total, inv_s, (float)zero_point);
+  return (int)hipGetLastError();
+}
+
+int btx_q8_sample_weights(const int8_t* mu_i, const int8_t* sigma_i, const float* mu_b, const float* sigma_b, int N, int taps, int C,
+                          int eps_C, const BtxQ8Chain* chain_host, const BtxRng* rng, const float* eps_w, const float* eps_b,
+                          int8_t* W, int32_t* S, int32_t* b_i, void* stream) {
+  if (!mu_i || !sigma_i || !chain_host || !W || !S || !b_i) return BTX_E_NULL;
+  if (!rng && !eps_w) return BTX_E_NULL;                       // the noise comes from somewhere
+  if (sigma_b && !mu_b) return BTX_E_NULL;
+  if (mu_b && sigma_b && !rng && !eps_b) return BTX_E_NULL;
+  if (N <= 0 || taps <= 0 || C <= 0) return BTX_E_SHAPE;
+  if (eps_C < C || (eps_C & 7)) {
+    if (!eps_w || eps_C != C) return BTX_E_SHAPE;              // the RNG index space has rows of a multiple of 8 channels
+  }
+  const long long kp = q8_kp(taps, C);
+  if (kp > 0x7fffffc0LL || (long long)N * taps * (long long)eps_C > 0xfffffffcLL) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)W & 15u) || ((uintptr_t)S & 3u) || ((uintptr_t)b_i & 3u)) return BTX_E_ALIGN;
+  const BtxQ8Chain& ch = *chain_host;
+  if (!(ch.s_sigma > 0.0f) || !(ch.s_mu > 0.0f) || !(ch.s_eps > 0.0f) || !(ch.s_d > 0.0f) || !(ch.inv_s_eps > 0.0f) ||
+      !(ch.inv_s_d > 0.0f) || !(ch.inv_s_w > 0.0f) || !(ch.bias_div > 0.0))
+    return BTX_E_SHAPE;
+  Q8SampleArgs a;
+  a.mu_i = mu_i; a.sigma_i = sigma_i; a.mu_b = mu_b; a.sigma_b = sigma_b; a.eps_w = eps_w; a.eps_b = eps_b;
+  a.W = W; a.S = S; a.b_i = b_i;
+  a.N = N; a.taps = taps; a.C = C; a.eps_C = eps_C; a.Cp = q8_cp(C); a.Kp = (int)kp;
+  a.ch = ch;
+  a.k0 = rng ? (uint32_t)rng->seed : 0u;
+  a.k1 = rng ? (uint32_t)(rng->seed >> 32) : 0u;
+  a.sample = rng ? rng->sample_idx : 0u;
+  a.layer = rng ? rng->layer_id : 0u;
+  a.sample_ptr = rng ? (const uint32_t*)rng->sample_idx_dev : nullptr;
+  hipLaunchKernelGGL(q8_sample_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int btx_q8_contract(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
+                    float multiplier, int out_zero_point, int relu, int out_f32, float out_scale, void* out, void* stream) {
+  if (!g || !x || !W || !S || !b_i || !out) return BTX_E_NULL;
+  const int rc = q8_check_geom(g);
+  if (rc) return rc;
+  if (x_zero_point < 0 || x_zero_point > 255 || out_zero_point < 0 || out_zero_point > 255 || !(multiplier > 0.0f)) return BTX_E_SHAPE;
+  if (out_f32 && !(out_scale > 0.0f)) return BTX_E_SHAPE;
+  const long long kp = q8_kp(g->KH * g->KW, g->C);
+  if (kp > 0x7fffffc0LL) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)W & 15u) || ((uintptr_t)S & 3u) || ((uintptr_t)b_i & 3u)) return BTX_E_ALIGN;
+  Q8ContractArgs a;
+  a.x = x; a.W = W; a.S = S; a.b_i = b_i; a.out = out;
+  a.NB = g->NB; a.H = g->H; a.Wd = g->W; a.C = g->C; a.N = g->N; a.KH = g->KH; a.KW = g->KW;
+  a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw; a.dh = g->dh; a.dw = g->dw;
+  a.OH = q8_out_extent(g->H, g->KH, g->sh, g->ph, g->dh);
+  a.OW = q8_out_extent(g->W, g->KW, g->sw, g->pw, g->dw);
+  a.taps = g->KH * g->KW; a.Cp = q8_cp(g->C); a.Kp = (int)kp;
+  a.M = (long long)g->NB * a.OH * a.OW;
+  const long long mblocks = (a.M + Q8_BM - 1) / Q8_BM;
+  if (mblocks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+  a.z_x = x_zero_point; a.z_o = out_zero_point; a.lo = relu ? out_zero_point : 0;
+  a.mult = multiplier; a.s_o = out_scale;
+  a.out_f32 = out_f32 ? 1 : 0;
+  a.x_vec = (g->C % 16 == 0 && ((uintptr_t)x & 15u) == 0) ? 1 : 0;
+  a.out_vec = out_f32 ? ((g->N % 4 == 0 && ((uintptr_t)out & 15u) == 0) ? 1 : 0) : ((g->N % 4 == 0 && ((uintptr_t)out & 3u) == 0) ? 1 : 0);
+  hipLaunchKernelGGL(q8_contract_kernel, dim3((unsigned)mblocks, (unsigned)((g->N + Q8_BN - 1) / Q8_BN)), dim3(256), 0,
+                     (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -216,9 +216,51 @@ class _VariationalNd(BaseVariationalLayer_):
         from .. import autograd as _ag
         return _ag.kl_of_layers([self])
 
+    def _prepare_stubs(self):
+        """the reference's prepare() (layers/variational_layers/linear_variational.py:123-129, conv_variational.py:326-332): five
+        symmetric qint8 stubs (sigma, mu, eps, sigma * eps, the sampled weight) and two affine quint8 stubs (input, output) for
+        torch.quantization.prepare / convert to calibrate; models.bnn_to_qbnn reads their (scale, zero point) pairs"""
+        from torch.ao.quantization import DeQuantStub, MinMaxObserver, QConfig, QuantStub
+        sym = MinMaxObserver.with_args(dtype=torch.qint8, qscheme=torch.per_tensor_symmetric)
+        aff = MinMaxObserver.with_args(dtype=torch.quint8)
+        self.qint_quant = nn.ModuleList([QuantStub(QConfig(weight=sym, activation=sym)) for _ in range(5)])
+        self.quint_quant = nn.ModuleList([QuantStub(QConfig(weight=aff, activation=aff)) for _ in range(2)])
+        self.dequant = DeQuantStub()
+        self.quant_prepare = True
+
+    def _forward_calibrate(self, x, return_kl):
+        """the calibration run (quant_prepare): the ATen chain of the reference forward, then every intermediate through its stub in
+        the reference's order (linear_variational.py:180-190) — observers record ranges; no HIP involved"""
+        mu, rho = self._w()
+        mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
+        sigma_w = BF.softplus_naive(rho)
+        eps_w = getattr(self, "eps_" + self._wn).data.normal_()
+        tmp = sigma_w * eps_w
+        weight = mu + tmp
+        kl = self.kl_div(mu, sigma_w, self.prior_weight_mu, self.prior_weight_sigma) if return_kl else None
+        b = None
+        if self.mu_bias is not None:
+            sigma_b = BF.softplus_naive(self.rho_bias)
+            b = self.mu_bias + (sigma_b * self.eps_bias.data.normal_())
+            if return_kl:
+                kl = kl + self.kl_div(self.mu_bias, sigma_b, self.prior_bias_mu, self.prior_bias_sigma)
+        out = BF.contract_aten(x, weight, b, self._op)
+        self.quint_quant[0](x)
+        self.quint_quant[1](out)
+        self.qint_quant[0](sigma_w)
+        self.qint_quant[1](mu)
+        self.qint_quant[2](eps_w)
+        self.qint_quant[3](tmp)
+        self.qint_quant[4](weight)
+        if return_kl:
+            return out, kl
+        return out
+
     def forward(self, input, return_kl=True):
         if self.dnn_to_bnn_flag:
             return_kl = False
+        if self.quant_prepare:
+            return self._forward_calibrate(input, return_kl)
         if self._use_hip(input):
             if self._needs_grad(input):
                 if self.__dict__.get("_btx_lanes", 1) > 1:

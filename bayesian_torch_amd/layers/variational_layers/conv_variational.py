@@ -33,6 +33,10 @@ class Conv2dReparameterization(_VariationalNd):
                     prior_mean, prior_variance, posterior_mu_init, posterior_rho_init, bias,
                     check_groups=True)
 
+    def prepare(self):
+        """add the reference's seven QuantStubs (conv_variational.py:326-332); forwards then calibrate (quant_prepare)"""
+        self._prepare_stubs()
+
 
 class Conv3dReparameterization(_VariationalNd):
     """Conv3d with the reparameterization trick — reference layers/variational_layers/conv_variational.py:405-574."""

@@ -19,3 +19,7 @@ class LinearReparameterization(_VariationalNd):
         self.posterior_rho_init = posterior_rho_init,
         self._setup(in_features, out_features, 1, 1, 0, 1, 1, 0, prior_mean, prior_variance,
                     posterior_mu_init, posterior_rho_init, bias, check_groups=False)
+
+    def prepare(self):
+        """add the reference's seven QuantStubs (linear_variational.py:123-129); forwards then calibrate (quant_prepare)"""
+        self._prepare_stubs()

@@ -206,6 +206,8 @@ class GraphedMC:
             raise ValueError("GraphedMC needs CUDA (ROCm) tensors")
         if lane_mode not in ("launch", "streams"):
             raise ValueError("lane_mode must be 'launch' or 'streams'")
+        if int(lanes) > 1 and any(getattr(m, "_btx_q8", False) for m in model.modules()):
+            raise _lib.BtxError("MC sample lanes > 1 are not supported on a model that holds a quantized (INT8) layer: use lanes=1")
         self.model, self.x, self.kl, self.lanes = model, x, float(kl), int(lanes)
         self.lane_mode = lane_mode
         self._capture_stream = capture_stream  # graphs that will be replayed concurrently must not share a capture stream:

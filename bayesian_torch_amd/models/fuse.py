@@ -29,6 +29,12 @@ def _is_var(m):
     return hasattr(m, "forward_fused")
 
 
+def _is_q8(m):
+    """a quantized (INT8) twin: a leaf of the trace and never an epilogue site — its BatchNorm folding happens in
+    models.bnn_to_qbnn(fuse_conv_bn=True), its ReLU is the layer's own `relu` attribute"""
+    return getattr(m, "_btx_q8", False)
+
+
 def _is_lstm(m):
     """a Bayesian LSTM: a leaf of the trace (its forward loops over the time steps), never an epilogue site; fuse_model switches
     it to its fused sequence path (fused_sequence)"""
@@ -533,7 +539,7 @@ class _Tracer(torch.fx.Tracer):
     """variational layers and torch.nn modules (not containers) are leaves: their calls stay single nodes"""
 
     def is_leaf_module(self, m, qualname):
-        return _is_var(m) or _is_lstm(m) or super().is_leaf_module(m, qualname)
+        return _is_var(m) or _is_lstm(m) or _is_q8(m) or super().is_leaf_module(m, qualname)
 
 
 def _inlined(module):

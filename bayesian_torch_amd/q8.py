@@ -1,0 +1,157 @@
+"""INT8 inference plumbing (BTX-Q8 v1): the carrier of quantized GPU activations and the ctypes wrappers of the
+btx_q8_* entry points (include/btx.h K10).
+
+torch has no quantized tensors on ROCm devices, so a quantized activation travels between layers as a `QTensor`: a uint8
+tensor (channels-last for 4-D), a scale and a zero point, with the handful of methods of a torch.quint8 tensor that model code
+calls between layers."""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+class QTensor:
+    """uint8 values + (scale, zero_point): value = (q - zero_point) * scale.  4-D tensors are kept channels-last (what the i8
+    contraction reads and writes); the logical shape is NCHW as everywhere in torch."""
+
+    is_quantized = True
+    dtype = torch.quint8
+
+    def __init__(self, q, scale, zero_point):
+        if q.dtype != torch.uint8:
+            raise _lib.BtxError("QTensor holds uint8 values (got %s)" % q.dtype)
+        if q.dim() == 4:
+            q = q.contiguous(memory_format=torch.channels_last)
+        self.q, self.scale, self.zero_point = q, float(scale), int(zero_point)
+
+    shape = property(lambda self: self.q.shape)
+    device = property(lambda self: self.q.device)
+    is_cuda = property(lambda self: self.q.is_cuda)
+
+    def dim(self):
+        return self.q.dim()
+
+    def size(self, *a):
+        return self.q.size(*a)
+
+    def int_repr(self):
+        return self.q
+
+    def q_scale(self):
+        return self.scale
+
+    def q_zero_point(self):
+        return self.zero_point
+
+    def dequantize(self):
+        return (self.q.to(torch.float32) - float(self.zero_point)) * np.float32(self.scale).item()
+
+    def relu(self):
+        return QTensor(self.q.clamp(min=self.zero_point), self.scale, self.zero_point)
+
+    def flatten(self, start_dim=0, end_dim=-1):
+        return QTensor(self.q.flatten(start_dim, end_dim), self.scale, self.zero_point)
+
+    def reshape(self, *shape):
+        return QTensor(self.q.reshape(*shape), self.scale, self.zero_point)
+
+    def to(self, *a, **kw):
+        return QTensor(self.q.to(*a, **kw), self.scale, self.zero_point)
+
+    def cpu(self):
+        return self.to("cpu")
+
+    def as_torch_quint8(self):
+        """a real torch.quint8 tensor (CPU only: torch's quantized backends live there)"""
+        return torch._make_per_tensor_quantized_tensor(self.q.cpu().contiguous(), self.scale, self.zero_point)
+
+    def __repr__(self):
+        return "QTensor(shape=%s, scale=%g, zero_point=%d, device=%s)" % (tuple(self.q.shape), self.scale, self.zero_point, self.q.device)
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def quantize_act(x, scale, zero_point):
+    """f32 / bf16 CUDA tensor [B, K] or [B, C, H, W] (any memory format) -> QTensor, one launch (btx_q8_quantize_act)"""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BtxError("quantized layers take float32 or bfloat16 activations (got %s)" % x.dtype)
+    if x.dim() == 2:
+        nb, c, h, w = x.shape[0], x.shape[1], 1, 1
+        st = (x.stride(0), x.stride(1), 0, 0)
+        out = torch.empty((nb, c), dtype=torch.uint8, device=x.device)
+    elif x.dim() == 4:
+        nb, c, h, w = x.shape
+        st = tuple(x.stride())
+        out = torch.empty((nb, c, h, w), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    else:
+        raise _lib.BtxError("quantized layers take [B, K] or [B, C, H, W] activations (got %d-D)" % x.dim())
+    strides = (ctypes.c_int64 * 4)(*[int(s) for s in st])
+    _lib.check(_lib.lib().btx_q8_quantize_act(x.data_ptr(), _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32, strides,
+                                              out.data_ptr(), nb, c, h, w, float(scale), int(zero_point), _stream(x.device)))
+    return QTensor(out, scale, zero_point)
+
+
+def make_chain(s_sigma, s_mu, s_eps, s_d, s_w, s_x):
+    """BtxQ8Chain: the f32 scales, their f32 reciprocals (computed here, once, in f32) and the double bias divisor"""
+    f = np.float32
+    one = f(1.0)
+    return _lib.Q8Chain(float(f(s_sigma)), float(f(s_mu)), float(f(s_eps)), float(one / f(s_eps)), float(f(s_d)), float(one / f(s_d)),
+                        float(one / f(s_w)), float(s_x) * float(s_w))
+
+
+def weight_row_bytes(taps, c):
+    n = int(_lib.lib().btx_q8_weight_row_bytes(int(taps), int(c)))
+    if n == 0:
+        raise _lib.BtxError("quantized layer too large for the int8 weight image (taps=%d, C=%d)" % (taps, c))
+    return n
+
+
+def sample_weights(mu_p, sigma_p, mu_b, sigma_b, n, taps, c, eps_c, chain, seed, sample_idx, layer_id, sample_dev=None, eps_w=None,
+                   eps_b=None):
+    """btx_q8_sample_weights: int8 GEMM-major [n][taps][c] mu_i / sigma_i -> (W [n][Kp] int8, S [n] int32, b_i [n] int32).
+    eps_w: f32 GEMM-major [n][taps][c] explicit noise (eps_b: [n]) instead of BTX-RNG v1."""
+    dev = mu_p.device
+    kp = weight_row_bytes(taps, c)
+    W = torch.empty((n, kp), dtype=torch.int8, device=dev)
+    S = torch.empty(n, dtype=torch.int32, device=dev)
+    b_i = torch.empty(n, dtype=torch.int32, device=dev)
+    r = _lib.Rng(int(seed), int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(_lib.lib().btx_q8_sample_weights(mu_p.data_ptr(), sigma_p.data_ptr(), ptr(mu_b), ptr(sigma_b), int(n), int(taps), int(c),
+                                                int(eps_c), ctypes.byref(chain), ctypes.byref(r), ptr(eps_w), ptr(eps_b),
+                                                W.data_ptr(), S.data_ptr(), b_i.data_ptr(), _stream(dev)))
+    return W, S, b_i
+
+
+def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplier, z_o, relu, out_f32, s_o):
+    """btx_q8_contract.  xq: uint8 [B, K] (Linear, kernel (1, 1)) or channels-last [B, C, H, W]."""
+    g = _lib.Geom()
+    if xq.dim() == 2:
+        g.NB, g.C, g.H, g.W = xq.shape[0], xq.shape[1], 1, 1
+    else:
+        g.NB, g.C, g.H, g.W = xq.shape
+    g.D = g.KD = 1
+    g.N = int(n)
+    g.KH, g.KW = kernel
+    g.sd, g.sh, g.sw = 1, stride[0], stride[1]
+    g.pd, g.ph, g.pw = 0, padding[0], padding[1]
+    g.dd, g.dh, g.dw = 1, dilation[0], dilation[1]
+    g.groups = 1
+    oh = (g.H + 2 * g.ph - g.dh * (g.KH - 1) - 1) // g.sh + 1
+    ow = (g.W + 2 * g.pw - g.dw * (g.KW - 1) - 1) // g.sw + 1
+    if oh <= 0 or ow <= 0:
+        raise _lib.BtxError("quantized conv: the kernel does not fit the input")
+    dt = torch.float32 if out_f32 else torch.uint8
+    if xq.dim() == 2:
+        out = torch.empty((g.NB, g.N), dtype=dt, device=xq.device)
+    else:
+        out = torch.empty((g.NB, g.N, oh, ow), dtype=dt, device=xq.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().btx_q8_contract(ctypes.byref(g), xq.data_ptr(), int(z_x), W.data_ptr(), S.data_ptr(), b_i.data_ptr(),
+                                          float(multiplier), int(z_o), 1 if relu else 0, 1 if out_f32 else 0, float(np.float32(s_o)),
+                                          out.data_ptr(), _stream(xq.device)))
+    return out

@@ -89,6 +89,9 @@ def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=Non
         if indices:
             set_sample_index(model, indices[0], presample=presample)
         return None
+    if any(getattr(m, "_btx_q8", False) for m in layers):
+        from ._lib import BtxError
+        raise BtxError("MC sample lanes > 1 are not supported on a model that holds a quantized (INT8) layer: use lanes=1")
     if batch is None:
         raise ValueError("set_sample_lanes needs the number of images per lane (batch)")
     n = len(indices)

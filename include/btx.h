@@ -549,6 +549,42 @@ int btx_eau_fwd(const float* error, const float* other, int B, int conf_form, fl
 int btx_eau_bwd(const float* error, const float* other, int B, int conf_form, const float* g_loss, const void* ws,
                 size_t ws_bytes, float* derror, float* dother, void* stream);
 
+/* K10. INT8 inference, arithmetic BTX-Q8 v1, for Linear and Conv2d Reparameterization layers with groups = 1
+ * (reference layers/variational_layers/quantize_linear_variational.py:134-224, quantize_conv_variational.py:457-552: quantize eps,
+ * quantized.mul, quantized.add, quantized linear / conv2d on the CPU engines).  Every floating step is one f32 operation, round to
+ * nearest even, never contracted;  q(v, s, z, lo, hi) = clamp(rint(v * (1 / s)) + z, lo, hi).
+ * BtxQ8Chain (HOST struct): the scales of the weight chain, each with the f32 reciprocal the quantize steps multiply by, and
+ *   bias_div = (double)s_x * (double)s_w, the divisor of the int32 bias.
+ * Weight image W: int8 [N][Kp], k = tap * Cp + c, tap = kh * KW + kw, Cp = C rounded up to 16, Kp = the row size
+ *   btx_q8_weight_row_bytes(taps, C) = taps * Cp rounded up to 64; padding bytes are zero.  0 = invalid or too large.
+ * btx_q8_quantize_act: x [NB][C][H][W] LOGICAL, element strides strides_host[4] (any memory format), f32 or bf16 ->
+ *   out uint8 channels-last [NB][H][W][C] = q(x, scale, zero_point, 0, 255).  One launch.
+ * btx_q8_sample_weights: one launch per layer.  mu_i / sigma_i: int8 GEMM-major [N][taps][C].  eps = BTX-RNG v1 stream EPS_W at
+ *   index (n * taps + tap) * eps_C + c — the float layer's index space, eps_C = its channel count rounded up to 8 — or, when eps_w
+ *   is non-NULL, eps_w[N][taps][C] f32 (then eps_C may equal C).  eps_i = q(eps, s_eps, 0, -128, 127);
+ *   d_i = q((sigma_i * s_sigma) * (eps_i * s_eps), s_d, ..);  W_i = q((d_i * s_d) + (mu_i * s_mu), s_w, ..).
+ *   S[n] = sum_k W_i[n][k] (int32).  b_i[n] = (int32) rint((double)(mu_b + sigma_b * eps_b) / bias_div), eps_b = stream EPS_B at
+ *   index n or eps_b[n]; sigma_b NULL: the bias is mu_b; mu_b NULL: b_i = 0.  rng may be NULL when all the noise is explicit;
+ *   rng->sample_idx_dev is honoured.
+ * btx_q8_contract: implicit GEMM on v_mfma_i32_16x16x64_i8.  g: Linear (D = H = W = 1, taps = 1) or Conv2d (D = KD = 1), groups 1.
+ *   acc = sum_k (x - x_zero_point) * W_i, padded taps contribute 0;  o = clamp(rint(f32(acc + b_i) * multiplier) + out_zero_point,
+ *   relu ? out_zero_point : 0, 255).  out: uint8 channels-last [NB][OH][OW][N], or with out_f32 the dequantized
+ *   f32 (o - out_zero_point) * out_scale.
+ * Errors: BTX_E_NULL, BTX_E_SHAPE (extents, scales <= 0, zero points outside [0, 255]), BTX_E_UNSUPPORTED (groups != 1, D or KD != 1,
+ *   index spaces beyond 32 bits), BTX_E_DTYPE, BTX_E_ALIGN (W 16 bytes; S, b_i, the quantize output 4 bytes). */
+typedef struct BtxQ8Chain {
+  float s_sigma, s_mu, s_eps, inv_s_eps, s_d, inv_s_d, inv_s_w;
+  double bias_div;
+} BtxQ8Chain;
+size_t btx_q8_weight_row_bytes(int taps, int C);
+int btx_q8_quantize_act(const void* x, int act_dtype, const int64_t* strides_host, uint8_t* out, int NB, int C, int H, int W,
+                        float scale, int zero_point, void* stream);
+int btx_q8_sample_weights(const int8_t* mu_i, const int8_t* sigma_i, const float* mu_b, const float* sigma_b, int N, int taps, int C,
+                          int eps_C, const BtxQ8Chain* chain_host, const BtxRng* rng, const float* eps_w, const float* eps_b,
+                          int8_t* W, int32_t* S, int32_t* b_i, void* stream);
+int btx_q8_contract(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
+                    float multiplier, int out_zero_point, int relu, int out_f32, float out_scale, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
