@@ -63,6 +63,10 @@ roundoff of f32.  Every constant below is a count of roundings, written out wher
               cancel near sig = ps, so the bound is on magnitudes: (c1 u32 + DELTA_W) g (sig / ps^2 + 1 / sig) sig' with
               c1 = 12 + 2 c0 (ten roundings and the expf inside sig'; DELTA_W is the softplus, as for the sampled weights).
   avg-pool    small integers: f32(sum) * f32(1 / HW), one rounding, then the store's: exact, zero tolerance.
+
+FUSED LSTM (third part of this file, derivations in its header): per-step float64 references fed with the GPU's own sampled
+weights, previous state and saved buffers — gates (accumulation only), cell / hidden state (transcendentals only) and a backward
+through time whose bound is propagated operation by operation (Err).
 """
 import numpy as np
 import torch
@@ -479,3 +483,263 @@ def avgpool_exact(x, dtype):
     s = _np(x).sum(1).astype(np.float32)
     inv = np.float32(1.0) / np.float32(hw)
     return torch.from_numpy((s * inv).astype(np.float32)).to(dtype)
+
+
+# =============================================================================================================================
+# fused Bayesian LSTM (btx_lstm.hip, btx_lstm_bwd.hip): every step judged alone
+# =============================================================================================================================
+# The whole-sequence references of test_gpu_lstm_fused.py / test_gpu_lstm_train_fused.py re-derive the chain, so a bf16 rounding
+# of h that flips feeds back and only a loose rel-L2 bar survives.  Here the reference of step t is fed with the GPU's OWN
+# operands — the weights it sampled (read back by identity-impulse probes: x = I makes every gate pre-activation one product),
+# its own h_{t-1} (hidden_seq[:, t-1]) and its own saved f32 cell state — so no operand term is left, in f32 and bf16 alike:
+#
+#   sampled weights   |w_gpu - (mu + sigma64 eps)| <= DELTA_W_LSTM (|mu| + |sigma eps|), eps / signs from materialize_noise(s + t)
+#   gates             |got - ref| <= (K_i + K_h + 8) 2^-23 A,   A = the same sum on absolute values (accumulation only)
+#   cell / hidden     c = f c' + i g,  h = o tanh c  from the saved gates and the saved c': with es = SIGM_ULP 2^-23 (the relative
+#                     error of 1 / (1 + expf(-v))), et = TANH_ULP 2^-23 (tanhf), u = 2^-24 and three roundings per line
+#                         b_c = (es + 3u) |f c'| + (es + et + 3u) |i g|
+#                         b_h = (es + et + 3u) |o tanh c| + |o| b_c              (tanh' <= 1 carries the error of c into h)
+#                     bf16 activations: store_rounding on top
+#   backward          the same first-order calculus, carried by Err below: every product, sum and contraction adds its own
+#                     roundings to the error it inherits; nothing is fitted.  Contractions: (len + 8) 2^-23 A plus the incoming
+#                     error through |W|; len = 4H (recurrent term, dx, dh0), B (one step of a weight gradient), T (the sum over
+#                     the steps).  drho multiplies by sigmoid(rho): one more sigm.  The eps the weight-gradient kernel
+#                     regenerates is the hardware Box-Muller value, the reference's is materialize_noise's: DELTA_W_LSTM on eps_w,
+#                     DELTA_B_LSTM on eps_b (the measured error of sigma eps bounds that of its factor eps).
+#
+# SIGM_ULP / TANH_ULP: twice the maximum error, in ulps of the result, of the device's 1 / (1 + expf(-v)) and tanhf against
+# float64 (torch.sigmoid / torch.tanh on the GPU, the same math library; measured over the gate range of the test cases, never
+# on the outputs of the kernels under test): profiles/lstm_envelope.txt
+SIGM_ULP = 5.09  # measured 2.544 ulp (torch.sigmoid and the spelled-out expression alike), 5 M points on [-40, 40]
+TANH_ULP = 2.72  # measured 1.359 ulp
+# The LSTM's own sampled-weight constants, twice the maxima its probes measured.  DELTA_W is not widened: the Reparameterization
+# probes (fl(mu + sigma eps) relative to |mu| + |sigma eps|) measured 3.73e-7, inside DELTA_W / 2.  The Flipout probes pass a
+# zero mu and return Delta = sigma eps ALONE, so nothing dilutes the error of the hardware softplus times the hardware
+# Box-Muller against float64 softplus times the materialised eps: 6.55e-7 relative to |sigma eps|, above DELTA_W / 2.  The
+# bias (btx_softplus_fast / btx_normal1) measured 3.08e-7 (Reparameterization) and 5.59e-7 (Flipout, sigma_b eps_b alone).
+DELTA_W_LSTM = 1.31e-6
+DELTA_B_LSTM = 1.12e-6
+LSTM_USEFUL = 1e-4  # a backward bound above this fraction of A (before any bf16 store) says nothing about the element
+
+
+def rbf16(a):
+    """float64 numpy of the values rounded to bf16 (the bits the kernels' own rounding gives)"""
+    return torch.as_tensor(_np(a), dtype=torch.float32).to(torch.bfloat16).to(torch.float64).numpy()
+
+
+def lstm_layer_step(mu, D=None, bm=None, bd=None, s_in=None, s_out=None):
+    """one layer at one step as the kernel contracts it.  Reparameterization: mu = the sampled W = fl(mu + sigma eps), bm =
+    fl(mu_b + sigma_b eps_b).  Flipout: mu, D = Delta, bm = mu_b, bd = sigma_b eps_b, s_in [B, K], s_out [B, 4H] (+-1)."""
+    f = lambda t: None if t is None else _np(t)  # noqa: E731
+    return dict(mu=f(mu), D=f(D), bm=f(bm), bd=f(bd), s_in=f(s_in), s_out=f(s_out))
+
+
+def _lstm_round(L, bf16):
+    if not bf16:
+        return L
+    return dict(L, mu=rbf16(L["mu"]), D=None if L["D"] is None else rbf16(L["D"]))
+
+
+def lstm_linear64(inp, L, bf16):
+    """inp [B, K] (or None: zeros) through one layer step -> (value, A) [B, 4H] float64"""
+    L = _lstm_round(L, bf16)
+    N = L["mu"].shape[0]
+    if inp is None:
+        v = a = 0.0
+        B = None
+    else:
+        inp = rbf16(inp) if bf16 else _np(inp)
+        B = inp.shape[0]
+        v, a = inp @ L["mu"].T, np.abs(inp) @ np.abs(L["mu"]).T
+    if L["D"] is not None and inp is not None:
+        p, a = (inp * L["s_in"][:B]) @ L["D"].T, a + np.abs(inp) @ np.abs(L["D"]).T
+    else:
+        p = 0.0
+    if L["bm"] is not None:
+        v, a = v + L["bm"], a + np.abs(L["bm"])
+    if L["bd"] is not None:
+        p, a = p + L["bd"], a + np.abs(L["bd"])
+    if L["D"] is not None or L["bd"] is not None:
+        so = L["s_out"]
+        v = v + p * (so if B is None else so[:B])
+    return v, a
+
+
+def lstm_gates64(x_t, h_prev, Li, Lh, bf16):
+    """gate pre-activations of one step in float64 and their accumulation bound -> (ref, bound) [B, 4H]"""
+    vi, ai = lstm_linear64(x_t, Li, bf16)
+    vh, ah = lstm_linear64(h_prev, Lh, bf16)
+    K = Li["mu"].shape[1] + Lh["mu"].shape[1]
+    B = _np(x_t).shape[0]
+    shape = (B, Li["mu"].shape[0])
+    return np.broadcast_to(vi + vh, shape), np.broadcast_to((K + 8) * ACC_UNIT * (ai + ah), shape)
+
+
+def _sig(v):
+    return 1.0 / (1.0 + np.exp(-v))
+
+
+def lstm_cell64(gates, c_prev):
+    """c_t, h_t in float64 from the (saved, f32) gate pre-activations [B, 4H] and c_{t-1} [B, H] -> (c, b_c, h, b_h)"""
+    g4 = _np(gates)
+    H = g4.shape[1] // 4
+    cp = np.zeros((g4.shape[0], H)) if c_prev is None else _np(c_prev)
+    with np.errstate(over="ignore"):
+        i, f, g, o = _sig(g4[:, :H]), _sig(g4[:, H:2 * H]), np.tanh(g4[:, 2 * H:3 * H]), _sig(g4[:, 3 * H:])
+    es, et, u = SIGM_ULP * ACC_UNIT, TANH_ULP * ACC_UNIT, REF32_UNIT
+    c = f * cp + i * g
+    b_c = (es + 3 * u) * np.abs(f * cp) + (es + et + 3 * u) * np.abs(i * g)
+    h = o * np.tanh(c)
+    b_h = (es + et + 3 * u) * np.abs(h) + np.abs(o) * b_c
+    return c, b_c, h, b_h
+
+
+class Err:
+    """a float64 value with a bound on the error of its f32 counterpart; every operation adds one f32 rounding of its result
+    (a fused multiply-add rounds less often: still inside)"""
+    __slots__ = ("v", "e")
+
+    def __init__(self, v, e=None):
+        self.v = _np(v)
+        self.e = np.zeros_like(self.v) if e is None else np.broadcast_to(_np(e), self.v.shape)
+
+    @staticmethod
+    def of(x):
+        return x if isinstance(x, Err) else Err(x)
+
+    def __mul__(self, o):
+        o = Err.of(o)
+        v = self.v * o.v
+        e = np.abs(self.v) * o.e + np.abs(o.v) * self.e + self.e * o.e
+        return Err(v, e + REF32_UNIT * (np.abs(v) + e))
+
+    def __add__(self, o):
+        o = Err.of(o)
+        e = self.e + o.e
+        return Err(self.v + o.v, e + REF32_UNIT * (np.abs(self.v) + np.abs(o.v) + e))
+
+    def __sub__(self, o):
+        o = Err.of(o)
+        return self + Err(-o.v, o.e)
+
+    def abs(self):
+        return Err(np.abs(self.v))
+
+    @property
+    def T(self):
+        return Err(self.v.T, self.e.T)
+
+
+def _err_sigm(v):
+    with np.errstate(over="ignore"):
+        s = _sig(_np(v))
+    return Err(s, SIGM_ULP * ACC_UNIT * s)
+
+
+def _err_tanh(v):
+    t = np.tanh(_np(v))
+    return Err(t, TANH_ULP * ACC_UNIT * np.abs(t))
+
+
+def _err_matmul(a, b, length):
+    """a [m, k] (Err) @ b [k, n] (exact): the incoming error through |b| and (length + 8) 2^-23 of the magnitudes"""
+    ab = np.abs(b)
+    return Err(a.v @ b, a.e @ ab + (length + 8) * ACC_UNIT * ((np.abs(a.v) + a.e) @ ab))
+
+
+def _lstm_contract_T(dG, L, length):
+    """dgates [B, 4H] . W -> [B, K]; Flipout: dG mu + s_in o ((dG o s_out) Delta)"""
+    out = _err_matmul(dG, L["mu"], length)
+    if L["D"] is not None:
+        B = dG.v.shape[0]
+        p = _err_matmul(Err(dG.v * L["s_out"][:B], dG.e), L["D"], length)
+        out = out + Err(p.v * L["s_in"][:B], p.e)
+    return out
+
+
+def _chain_sum(terms, length):
+    """sum of Err terms along one f32 chain of `length` additions"""
+    v = sum(t.v for t in terms)
+    e = sum(t.e for t in terms)
+    return Err(v, e + (length + 8) * ACC_UNIT * sum(np.abs(t.v) + t.e for t in terms))
+
+
+def lstm_bptt64(gates, cells, c0, Li, Lh, x, hs, h0, d_hs, d_cs, noise, rho, bf16, want_state=False, absolute=False):
+    """backward through time in float64 from what the GPU saved (gates [T, B, 4H], cells [T, B, H]), the layer steps Li[t] /
+    Lh[t] it sampled, its own hidden_seq [B, T, H] as the input of the hh weight gradient, and the given d_hs / d_cs [B, T, H]
+    (or None).  noise = dict(ih=[(eps_w, eps_b | None)] per step, hh=...), rho = dict(ih=(rho_w, rho_b | None), hh=...).
+    -> dict name -> Err: dx [B, T, I], dh0, dc0 (want_state), ih.dmu_w, ih.drho_w, ih.dmu_b, ih.drho_b, hh.* .
+    absolute=True: the same chain on absolute values — the magnitudes A of every output (errors meaningless)."""
+    gates, cells = _np(gates), _np(cells)
+    T, B, N = gates.shape
+    H = N // 4
+    ab = (lambda a: np.abs(a)) if absolute else (lambda a: a)
+    Li = [_lstm_round(L, bf16) for L in Li]
+    Lh = [_lstm_round(L, bf16) for L in Lh]
+    if absolute:
+        def absL(L):
+            one = lambda s: None if s is None else np.ones_like(s)  # noqa: E731
+            return dict(mu=np.abs(L["mu"]), D=None if L["D"] is None else np.abs(L["D"]), s_in=one(L["s_in"]), s_out=one(L["s_out"]))
+        Li, Lh = [absL(L) for L in Li], [absL(L) for L in Lh]
+    x, hs = _np(x), _np(hs)
+    xin = rbf16(x) if bf16 else x
+    hin = rbf16(hs) if bf16 else hs
+    h0in = None if h0 is None else (rbf16(h0) if bf16 else _np(h0))
+    fx = (lambda e: e.abs()) if absolute else (lambda e: e)
+    one = Err(1.0)
+    dG, dcc = [None] * T, None
+    for t in range(T - 1, -1, -1):
+        g4 = gates[t]
+        i, f, o = _err_sigm(g4[:, :H]), _err_sigm(g4[:, H:2 * H]), _err_sigm(g4[:, 3 * H:])
+        g, th = _err_tanh(g4[:, 2 * H:3 * H]), _err_tanh(cells[t])
+        cp = cells[t - 1] if t > 0 else (np.zeros((B, H)) if c0 is None else _np(c0))
+        dth, di, df, dg, do = one - th * th, i * (one - i), f * (one - f), one - g * g, o * (one - o)
+        g, th, cp = fx(g), fx(th), ab(cp)
+        dh = Err(ab(_np(d_hs)[:, t])) if d_hs is not None else Err(np.zeros((B, H)))
+        if t + 1 < T:
+            dh = dh + _lstm_contract_T(dG[t + 1], Lh[t + 1], N)
+        dc = dh * o * dth
+        if d_cs is not None:
+            dc = dc + Err(ab(_np(d_cs)[:, t]))
+        if dcc is not None:
+            dc = dc + dcc
+        parts = [dc * g * di, dc * Err(cp) * df, dc * i * dg, dh * th * do]
+        dG[t] = Err(np.concatenate([p.v for p in parts], 1), np.concatenate([p.e for p in parts], 1))
+        dcc = dc * f
+    out = {}
+    dx = [_lstm_contract_T(dG[t], Li[t], N) for t in range(T)]
+    out["dx"] = Err(np.stack([d.v for d in dx], 1), np.stack([d.e for d in dx], 1))
+    if want_state:
+        out["dh0"], out["dc0"] = _lstm_contract_T(dG[0], Lh[0], N), dcc
+    for name, Ls in (("ih", Li), ("hh", Lh)):
+        rho_w, rho_b = rho[name]
+        dmu, se, bmu, bse = [], [], [], []
+        for t in range(T):
+            if name == "ih":
+                inp = xin[:, t]
+            else:
+                inp = hin[:, t - 1] if t > 0 else (h0in if h0in is not None else np.zeros((B, H)))
+            inp = ab(inp)
+            L = Ls[t]
+            eps_w, eps_b = noise[name][t]
+            dW = _err_matmul(dG[t].T, inp, B)
+            dmu.append(dW)
+            dD = dW
+            sg = dG[t]
+            if L["D"] is not None or L["s_out"] is not None:
+                sg = Err(dG[t].v * L["s_out"][:B], dG[t].e)
+                dD = _err_matmul(sg.T, inp * L["s_in"][:B], B)
+            ew = ab(_np(eps_w))
+            se.append(dD * Err(ew, DELTA_W_LSTM * np.abs(ew)))
+            if rho_b is not None:
+                ones = np.ones((B, 1))
+                bm, bd = _err_matmul(dG[t].T, ones, B), _err_matmul(sg.T, ones, B)
+                eb = ab(_np(eps_b))
+                bmu.append(Err(bm.v[:, 0], bm.e[:, 0]))
+                bse.append(Err(bd.v[:, 0], bd.e[:, 0]) * Err(eb, DELTA_B_LSTM * np.abs(eb)))
+        out[name + ".dmu_w"] = _chain_sum(dmu, T)
+        out[name + ".drho_w"] = _chain_sum(se, T) * _err_sigm(rho_w)
+        if rho_b is not None:
+            out[name + ".dmu_b"] = _chain_sum(bmu, T)
+            out[name + ".drho_b"] = _chain_sum(bse, T) * _err_sigm(rho_b)
+    return out
