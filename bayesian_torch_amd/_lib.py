@@ -88,6 +88,11 @@ class Q8Chain(ctypes.Structure):
                [("bias_div", ctypes.c_double)]
 
 
+class Q8Add(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("s_a", "pre_a", "s_b", "pre_b", "inv_s")] + \
+               [("zero_point", ctypes.c_int32), ("relu", ctypes.c_int32)]
+
+
 EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_gauss", "btx_kl_model_workspace_bytes",
            "btx_kl_gauss_model", "btx_kl_gauss_model_bwd", "btx_contract_wgrad",
            "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_contract_plan_info", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
@@ -97,7 +102,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_lstm_workspace_bytes", "btx_lstm_fwd", "btx_lstm_train_saved_bytes", "btx_lstm_train_workspace_bytes",
            "btx_lstm_fwd_train", "btx_lstm_bwd",
            "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd",
-           "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract")
+           "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract",
+           "btx_q8_add", "btx_q8_contract_res", "btx_q8_maxpool2d_cl", "btx_q8_avgpool2d_cl")
 
 
 def lib_path():
@@ -228,6 +234,14 @@ def lib():
                                         vp, vp, vp, vp]
     L.btx_q8_contract.restype = i32
     L.btx_q8_contract.argtypes = [ctypes.POINTER(Geom), vp, i32, vp, vp, vp, f32, i32, i32, i32, f32, vp, vp]
+    L.btx_q8_add.restype = i32
+    L.btx_q8_add.argtypes = [vp, vp, vp, sz, ctypes.POINTER(Q8Add), vp]
+    L.btx_q8_contract_res.restype = i32
+    L.btx_q8_contract_res.argtypes = [ctypes.POINTER(Geom), vp, i32, vp, vp, vp, f32, i32, i32, i32, vp, ctypes.POINTER(Q8Add), vp, vp]
+    L.btx_q8_maxpool2d_cl.restype = i32
+    L.btx_q8_maxpool2d_cl.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.btx_q8_avgpool2d_cl.restype = i32
+    L.btx_q8_avgpool2d_cl.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -11,6 +11,9 @@
 //                            point exact on the signed x signed instruction; out-of-image taps and the K tail hold the byte z_x
 //                            (value 0 after the correction; the tail meets zero weights).
 //
+// Network ops (§13 "between the layers"): q8_add_kernel (two uint8 tensors -> one, requantized), the same add as the residual
+// epilogue of the contraction (q8_contract_kernel<true>), q8_maxpool_cl_kernel and q8_avgpool_cl_kernel on uint8 channels-last.
+//
 // Numerics: every floating step is ONE f32 operation, round to nearest even, never contracted (__fmul_rn / __fadd_rn, and this unit is
 // built with -ffp-contract=off); rintf is half-to-even.  The integer sums are exact, so their order does not matter.
 //
@@ -155,7 +158,29 @@ struct Q8ContractArgs {
   int out_f32, x_vec, out_vec;
 };
 
-__global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a) {
+// the add of two quantized tensors: da = fma(s_a, a, pre_a), pre_a = f32(s_a * f32(-z_a)) (torch's vector kernel dequantizes with one
+// fused multiply-add), db alike, o = clamp(rint((da + db) * inv_s) + z, lo, 255)
+struct Q8AddArgs {
+  float s_a, pre_a, s_b, pre_b, inv_s, z, lo;
+};
+
+__device__ __forceinline__ float q8_add1(float a, float b, const Q8AddArgs& p) {
+  const float da = __fmaf_rn(p.s_a, a, p.pre_a);
+  const float db = __fmaf_rn(p.s_b, b, p.pre_b);
+  return fminf(fmaxf(__fadd_rn(rintf(__fmul_rn(__fadd_rn(da, db), p.inv_s)), p.z), p.lo), 255.0f);
+}
+
+// the residual operand of q8_contract_kernel<true>: uint8 [M][N] like the output; res_vec: 4-byte loads are in range and aligned
+struct Q8ResArgs {
+  const uint8_t* res;
+  Q8AddArgs add;
+  int res_vec;
+};
+
+// RES: the epilogue adds a residual tensor to the requantized output (a = the conv's output at (s_o, z_o), b = the residual) and
+// stores the sum's uint8.  RES = false never touches `ra`.
+template <bool RES>
+__global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a, const Q8ResArgs ra) {
   // two stages of each tile: step i + 1 is written while slower waves still read step i, so one barrier per step is enough (the
   // write of step i + 2 into this stage comes after barrier i + 1, which every wave reaches only after its reads of step i)
   __shared__ __attribute__((aligned(16))) uint8_t lds_w[2][Q8_BN * Q8_LDS_ROW];
@@ -248,6 +273,16 @@ __global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a
     if (nb >= a.N) continue;
     float of[4];
     uint32_t pack = 0;
+    const size_t off = (size_t)m * a.N + nb;
+    uint32_t rpack = 0;
+    if (RES) {  // the residual's four bytes of this lane, at the offset of its own four outputs
+      const uint8_t* rp = ra.res + off;
+      if (ra.res_vec && nb + 4 <= a.N) {
+        rpack = *reinterpret_cast<const uint32_t*>(rp);
+      } else {
+        for (int r = 0; r < 4 && nb + r < a.N; ++r) rpack |= (uint32_t)rp[r] << (8 * r);
+      }
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int n = nb + r;
@@ -255,11 +290,11 @@ __global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a
       if (n < a.N) {
         const int v = acc[j][r] + zc * a.S[n] + a.b_i[n];
         o = fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)v, a.mult)), (float)a.z_o), (float)a.lo), 255.0f);
+        if (RES) o = q8_add1(o, (float)((rpack >> (8 * r)) & 0xffu), ra.add);
       }
       pack |= (uint32_t)(int)o << (8 * r);
       of[r] = __fmul_rn(o - (float)a.z_o, a.s_o);  // o and z_o are small integers: the difference is exact
     }
-    const size_t off = (size_t)m * a.N + nb;
     if (a.out_f32) {
       float* o = reinterpret_cast<float*>(a.out) + off;
       if (a.out_vec && nb + 4 <= a.N) {
@@ -278,6 +313,92 @@ __global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// between the layers: add, max-pool, avg-pool on uint8
+// ---------------------------------------------------------------------------------------------------------------------
+// one thread per 16 consecutive bytes; vec: the three bases are 16-byte aligned.  The last group (n % 16 bytes) and every group of
+// an unaligned call go byte by byte.
+__global__ __launch_bounds__(256) void q8_add_kernel(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b,
+                                                     uint8_t* __restrict__ out, size_t n, const Q8AddArgs p, int vec) {
+  const size_t ngrp = (n + 15) >> 4;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < ngrp; g += (size_t)gridDim.x * 256) {
+    const size_t base = g << 4;
+    if (vec && base + 16 <= n) {
+      const uint4 va = *reinterpret_cast<const uint4*>(a + base);
+      const uint4 vb = *reinterpret_cast<const uint4*>(b + base);
+      const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+      uint32_t wo[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        uint32_t pack = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          pack |= (uint32_t)(int)q8_add1((float)((wa[q] >> (8 * e)) & 0xffu), (float)((wb[q] >> (8 * e)) & 0xffu), p) << (8 * e);
+        wo[q] = pack;
+      }
+      *reinterpret_cast<uint4*>(out + base) = make_uint4(wo[0], wo[1], wo[2], wo[3]);
+    } else {
+      for (size_t i = base; i < base + 16 && i < n; ++i) out[i] = (uint8_t)(int)q8_add1((float)a[i], (float)b[i], p);
+    }
+  }
+}
+
+// Channels-last pooling, window and grid conventions of maxpool2d_cl_kernel (btx_small.hip): one thread per VEC channels of one
+// output pixel, grid-stride over `total` = NB * Ho * Wo * (C / VEC).  VEC = 16: one 16-byte load per window element (C % 16 == 0,
+// aligned bases); VEC = 1: bytewise.  AVG: no padding, the window is always whole (cnt = k * k).
+template <int VEC, bool AVG>
+__global__ __launch_bounds__(256) void q8_pool_cl_kernel(const uint8_t* __restrict__ x, uint8_t* __restrict__ out, int NB, int H, int W,
+                                                         int C, int Ho, int Wo, int k, int s, int pad, long long total, int zcnt,
+                                                         float rcp, float z) {
+  const int cgs = C / VEC;
+  for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
+    const int cg = (int)(t % cgs);
+    long long r = t / cgs;
+    const int wo = (int)(r % Wo);
+    r /= Wo;
+    const int ho = (int)(r % Ho);
+    const int n = (int)(r / Ho);
+    int m[VEC];
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) m[j] = 0;
+    for (int kh = 0; kh < k; ++kh) {
+      const int h = ho * s - pad + kh;
+      if ((unsigned)h >= (unsigned)H) continue;
+      for (int kw = 0; kw < k; ++kw) {
+        const int w = wo * s - pad + kw;
+        if ((unsigned)w >= (unsigned)W) continue;
+        const uint8_t* src = x + (((long long)n * H + h) * W + w) * C + (long long)cg * VEC;
+        if (VEC == 16) {
+          const uint4 v = *reinterpret_cast<const uint4*>(src);
+          const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) {
+            const int e = (int)((wd[j >> 2] >> (8 * (j & 3))) & 0xffu);
+            m[j] = AVG ? m[j] + e : max(m[j], e);
+          }
+        } else {
+          const int e = (int)src[0];
+          m[0] = AVG ? m[0] + e : max(m[0], e);
+        }
+      }
+    }
+    if (AVG) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j)
+        m[j] = (int)fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)(m[j] - zcnt), rcp)), z), 0.0f), 255.0f);
+    }
+    uint8_t* dst = out + (((long long)n * Ho + ho) * Wo + wo) * C + (long long)cg * VEC;
+    if (VEC == 16) {
+      uint32_t wd[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) wd[j >> 2] |= (uint32_t)m[j] << (8 * (j & 3));
+      *reinterpret_cast<uint4*>(dst) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+    } else {
+      dst[0] = (uint8_t)m[0];
+    }
+  }
+}
+
 inline int q8_out_extent(int in, int k, int s, int p, int d) { return (in + 2 * p - d * (k - 1) - 1) / s + 1; }
 
 // geometry checks shared by the size query and the launch: 0 or a BTX_E_* code
@@ -292,6 +413,70 @@ inline int q8_check_geom(const BtxGeom* g) {
 
 inline int q8_cp(int C) { return (C + 15) / 16 * 16; }
 inline long long q8_kp(int taps, int C) { return ((long long)taps * q8_cp(C) + 63) / 64 * 64; }
+
+// BtxQ8Add (host) -> the kernels' constants; 0 or BTX_E_SHAPE
+inline int q8_add_args(const BtxQ8Add* h, Q8AddArgs* p) {
+  if (!(h->s_a > 0.0f) || !(h->s_b > 0.0f) || !(h->inv_s > 0.0f) || h->zero_point < 0 || h->zero_point > 255) return BTX_E_SHAPE;
+  p->s_a = h->s_a; p->pre_a = h->pre_a; p->s_b = h->s_b; p->pre_b = h->pre_b; p->inv_s = h->inv_s;
+  p->z = (float)h->zero_point;
+  p->lo = h->relu ? (float)h->zero_point : 0.0f;
+  return 0;
+}
+
+// what btx_q8_contract and btx_q8_contract_res share: the checks in their order of precedence, the kernel's arguments, the grid
+inline int q8_contract_setup(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
+                             float multiplier, int out_zero_point, int relu, int out_f32, float out_scale, void* out, Q8ContractArgs* pa,
+                             dim3* grid) {
+  if (!g || !x || !W || !S || !b_i || !out) return BTX_E_NULL;
+  const int rc = q8_check_geom(g);
+  if (rc) return rc;
+  if (x_zero_point < 0 || x_zero_point > 255 || out_zero_point < 0 || out_zero_point > 255 || !(multiplier > 0.0f)) return BTX_E_SHAPE;
+  if (out_f32 && !(out_scale > 0.0f)) return BTX_E_SHAPE;
+  const long long kp = q8_kp(g->KH * g->KW, g->C);
+  if (kp > 0x7fffffc0LL) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)W & 15u) || ((uintptr_t)S & 3u) || ((uintptr_t)b_i & 3u)) return BTX_E_ALIGN;
+  Q8ContractArgs& a = *pa;
+  a.x = x; a.W = W; a.S = S; a.b_i = b_i; a.out = out;
+  a.NB = g->NB; a.H = g->H; a.Wd = g->W; a.C = g->C; a.N = g->N; a.KH = g->KH; a.KW = g->KW;
+  a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw; a.dh = g->dh; a.dw = g->dw;
+  a.OH = q8_out_extent(g->H, g->KH, g->sh, g->ph, g->dh);
+  a.OW = q8_out_extent(g->W, g->KW, g->sw, g->pw, g->dw);
+  a.taps = g->KH * g->KW; a.Cp = q8_cp(g->C); a.Kp = (int)kp;
+  a.M = (long long)g->NB * a.OH * a.OW;
+  const long long mblocks = (a.M + Q8_BM - 1) / Q8_BM;
+  if (mblocks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+  a.z_x = x_zero_point; a.z_o = out_zero_point; a.lo = relu ? out_zero_point : 0;
+  a.mult = multiplier; a.s_o = out_scale;
+  a.out_f32 = out_f32 ? 1 : 0;
+  a.x_vec = (g->C % 16 == 0 && ((uintptr_t)x & 15u) == 0) ? 1 : 0;
+  a.out_vec = out_f32 ? ((g->N % 4 == 0 && ((uintptr_t)out & 15u) == 0) ? 1 : 0) : ((g->N % 4 == 0 && ((uintptr_t)out & 3u) == 0) ? 1 : 0);
+  *grid = dim3((unsigned)mblocks, (unsigned)((g->N + Q8_BN - 1) / Q8_BN));
+  return 0;
+}
+
+// the two pooling entry points: checks, output extent, grid (the conventions of maxpool_grid in btx_small.hip)
+template <bool AVG>
+int q8_pool_launch(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, int zero_point, void* stream) {
+  if (!x || !out) return BTX_E_NULL;
+  if (NB <= 0 || H <= 0 || W <= 0 || C <= 0 || k <= 0 || stride <= 0 || pad < 0 || 2 * pad > k) return BTX_E_SHAPE;
+  if (zero_point < 0 || zero_point > 255) return BTX_E_SHAPE;
+  const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
+  if (H + 2 * pad < k || W + 2 * pad < k || Ho <= 0 || Wo <= 0) return BTX_E_SHAPE;
+  if (AVG && (long long)k * k > 8000000LL) return BTX_E_UNSUPPORTED;   // the int32 window sum: 255 * k * k
+  const bool vec = C % 16 == 0 && ((((uintptr_t)x | (uintptr_t)out) & 15u) == 0);
+  const long long total = (long long)NB * Ho * Wo * (vec ? C / 16 : C);
+  long long blocks = (total + 255) / 256;
+  if (blocks > 262144) blocks = 262144;
+  const int cnt = k * k;
+  const float rcp = (float)(1.0 / (double)cnt);   // double reciprocal, rounded once
+  if (vec)
+    hipLaunchKernelGGL((q8_pool_cl_kernel<16, AVG>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, out, NB, H, W, C, Ho, Wo,
+                       k, stride, pad, total, cnt * zero_point, rcp, (float)zero_point);
+  else
+    hipLaunchKernelGGL((q8_pool_cl_kernel<1, AVG>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, out, NB, H, W, C, Ho, Wo,
+                       k, stride, pad, total, cnt * zero_point, rcp, (float)zero_point);
+  return (int)hipGetLastError();
+}
 
 }  // namespace
 
@@ -357,32 +542,56 @@ int btx_q8_sample_weights(const int8_t* mu_i, const int8_t* sigma_i, const float
 
 int btx_q8_contract(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
                     float multiplier, int out_zero_point, int relu, int out_f32, float out_scale, void* out, void* stream) {
-  if (!g || !x || !W || !S || !b_i || !out) return BTX_E_NULL;
-  const int rc = q8_check_geom(g);
-  if (rc) return rc;
-  if (x_zero_point < 0 || x_zero_point > 255 || out_zero_point < 0 || out_zero_point > 255 || !(multiplier > 0.0f)) return BTX_E_SHAPE;
-  if (out_f32 && !(out_scale > 0.0f)) return BTX_E_SHAPE;
-  const long long kp = q8_kp(g->KH * g->KW, g->C);
-  if (kp > 0x7fffffc0LL) return BTX_E_UNSUPPORTED;
-  if (((uintptr_t)W & 15u) || ((uintptr_t)S & 3u) || ((uintptr_t)b_i & 3u)) return BTX_E_ALIGN;
   Q8ContractArgs a;
-  a.x = x; a.W = W; a.S = S; a.b_i = b_i; a.out = out;
-  a.NB = g->NB; a.H = g->H; a.Wd = g->W; a.C = g->C; a.N = g->N; a.KH = g->KH; a.KW = g->KW;
-  a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw; a.dh = g->dh; a.dw = g->dw;
-  a.OH = q8_out_extent(g->H, g->KH, g->sh, g->ph, g->dh);
-  a.OW = q8_out_extent(g->W, g->KW, g->sw, g->pw, g->dw);
-  a.taps = g->KH * g->KW; a.Cp = q8_cp(g->C); a.Kp = (int)kp;
-  a.M = (long long)g->NB * a.OH * a.OW;
-  const long long mblocks = (a.M + Q8_BM - 1) / Q8_BM;
-  if (mblocks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
-  a.z_x = x_zero_point; a.z_o = out_zero_point; a.lo = relu ? out_zero_point : 0;
-  a.mult = multiplier; a.s_o = out_scale;
-  a.out_f32 = out_f32 ? 1 : 0;
-  a.x_vec = (g->C % 16 == 0 && ((uintptr_t)x & 15u) == 0) ? 1 : 0;
-  a.out_vec = out_f32 ? ((g->N % 4 == 0 && ((uintptr_t)out & 15u) == 0) ? 1 : 0) : ((g->N % 4 == 0 && ((uintptr_t)out & 3u) == 0) ? 1 : 0);
-  hipLaunchKernelGGL(q8_contract_kernel, dim3((unsigned)mblocks, (unsigned)((g->N + Q8_BN - 1) / Q8_BN)), dim3(256), 0,
-                     (hipStream_t)stream, a);
+  dim3 grid;
+  const int rc = q8_contract_setup(g, x, x_zero_point, W, S, b_i, multiplier, out_zero_point, relu, out_f32, out_scale, out, &a, &grid);
+  if (rc) return rc;
+  Q8ResArgs ra = {};
+  hipLaunchKernelGGL(q8_contract_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a, ra);
   return (int)hipGetLastError();
+}
+
+int btx_q8_contract_res(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
+                        float multiplier, int out_zero_point, int relu, int out_f32, const uint8_t* residual, const BtxQ8Add* add_host,
+                        void* out, void* stream) {
+  if (!residual || !add_host) return BTX_E_NULL;
+  Q8ContractArgs a;
+  dim3 grid;
+  const int rc = q8_contract_setup(g, x, x_zero_point, W, S, b_i, multiplier, out_zero_point, relu, 0, add_host->s_a, out, &a, &grid);
+  if (rc) return rc;
+  if (out_f32) return BTX_E_UNSUPPORTED;   // the sum leaves as uint8 at the add's (s, z)
+  Q8ResArgs ra;
+  const int rc2 = q8_add_args(add_host, &ra.add);
+  if (rc2) return rc2;
+  ra.res = residual;
+  ra.res_vec = (g->N % 4 == 0 && ((uintptr_t)residual & 3u) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(q8_contract_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a, ra);
+  return (int)hipGetLastError();
+}
+
+int btx_q8_add(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, const BtxQ8Add* add_host, void* stream) {
+  if (!a || !b || !out || !add_host) return BTX_E_NULL;
+  if (n == 0) return BTX_E_SHAPE;
+  Q8AddArgs p;
+  const int rc = q8_add_args(add_host, &p);
+  if (rc) return rc;
+  size_t blocks = ((n + 15) / 16 + 255) / 256;
+  if (blocks > 262144) blocks = 262144;
+  const int vec = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 15u) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(q8_add_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, b, out, n, p, vec);
+  return (int)hipGetLastError();
+}
+
+int btx_q8_maxpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, void* stream) {
+  return q8_pool_launch<false>(x, out, NB, H, W, C, k, stride, pad, 0, stream);
+}
+
+int btx_q8_avgpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, int ceil_mode,
+                        int zero_point, void* stream) {
+  if (!x || !out) return BTX_E_NULL;
+  if (pad < 0) return BTX_E_SHAPE;
+  if (pad != 0 || ceil_mode) return BTX_E_UNSUPPORTED;
+  return q8_pool_launch<true>(x, out, NB, H, W, C, k, stride, 0, zero_point, stream);
 }
 
 }  // extern "C"

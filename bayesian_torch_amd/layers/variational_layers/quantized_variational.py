@@ -252,9 +252,10 @@ class _QuantizedReparameterization(_base.BaseVariationalLayer_):
         c = self.in_features if self._nd == 0 else self.in_channels
         return c if c % 8 == 0 else (c + 7) // 8 * 8
 
-    def _forward_hip(self, x, sc, noise=None, sample_idx=None, parts=False):
+    def _forward_hip(self, x, sc, noise=None, sample_idx=None, parts=False, residual=None, add=None):
         """noise: dict(eps_w[, eps_b]) in the logical layouts (what the float layer's materialize_noise returns) instead of BTX-RNG;
-        parts=True: also return (W, S, b_i) of the sampling pre-pass."""
+        parts=True: also return (W, S, b_i) of the sampling pre-pass; residual (a QTensor of the output's shape) with
+        add = (scale or None, zero point, relu): the residual add in the contraction's store (btx_q8_contract_res)."""
         s_eps, s_d, s_w, (s_x, z_x), (s_o, z_o) = sc
         if self.__dict__.get("_btx_lanes", 1) > 1:
             raise _lib.BtxError("MC sample lanes > 1 are not supported by quantized (INT8) layers: use lanes=1")
@@ -292,7 +293,18 @@ class _QuantizedReparameterization(_base.BaseVariationalLayer_):
                                        _rng.seed(), sample_idx, self._btx_layer_id, getattr(self, "_btx_sample_dev", None), eps_w, eps_b)
         f = np.float32
         mult = float(f(f(s_x) * f(s_w)) / f(s_o))
-        if self._nd == 0:
+        if residual is not None:
+            if self._nd == 0:
+                raise _lib.BtxError("the residual add is an epilogue of the quantized Conv2d only")
+            if not isinstance(residual, _q8.QTensor):
+                raise _lib.BtxError("quantized conv: on the GPU the residual is a q8.QTensor (got %s)" % type(residual).__name__)
+            s_add, z_add, relu_add = add
+            s_add = max(float(s_o), residual.scale) if s_add is None else float(s_add)
+            p = _q8.make_add(s_o, z_o, residual.scale, residual.zero_point, s_add, z_add, relu_add)
+            o = _q8.contract(xq.q, z_x, W, S, b_i, n, kernel, _pair(self.stride), _pair(self.padding), _pair(self.dilation), mult, z_o,
+                             bool(self.relu), False, s_o, residual=residual.q, add=p)
+            out = _q8.QTensor(o, s_add, z_add)
+        elif self._nd == 0:
             out = _q8.contract(xq.q, z_x, W, S, b_i, n, (1, 1), (1, 1), (0, 0), (1, 1), mult, z_o, False, True, s_o)
         else:
             o = _q8.contract(xq.q, z_x, W, S, b_i, n, kernel, _pair(self.stride), _pair(self.padding), _pair(self.dilation), mult, z_o,
@@ -302,11 +314,14 @@ class _QuantizedReparameterization(_base.BaseVariationalLayer_):
             return out, W, S, b_i
         return out
 
-    def forward_int8(self, x, noise=None, sample_idx=None, parts=False, normal_scale=6 / 255, default_scale=None, default_zero_point=128):
-        """the GPU forward with explicit noise and / or a pinned sample index (tests, parity runs)"""
+    def forward_int8(self, x, noise=None, sample_idx=None, parts=False, normal_scale=6 / 255, default_scale=None, default_zero_point=128,
+                     residual=None, add_relu=True, add_scale=None, add_zero_point=0):
+        """the GPU forward with explicit noise and / or a pinned sample index (tests, parity runs); with `residual` the fused
+        residual add of forward_add"""
         if default_scale is None:
             default_scale = 0.2 if self._nd == 0 else 0.1
-        return self._forward_hip(x, self._scales(normal_scale, default_scale, default_zero_point), noise, sample_idx, parts)
+        return self._forward_hip(x, self._scales(normal_scale, default_scale, default_zero_point), noise, sample_idx, parts, residual,
+                                 (add_scale, int(add_zero_point), bool(add_relu)))
 
 
 class QuantizedLinearReparameterization(_QuantizedReparameterization):
@@ -333,3 +348,18 @@ class QuantizedConv2dReparameterization(_QuantizedReparameterization):
     def forward(self, input, enable_int8_compute=True, normal_scale=6 / 255, default_scale=0.1, default_zero_point=128, return_kl=True):
         """returns the quantized output (a q8.QTensor on the GPU, a torch.quint8 tensor on the CPU) and 0 for the KL"""
         return self._forward(input, enable_int8_compute, normal_scale, default_scale, default_zero_point, return_kl)
+
+    def forward_add(self, input, residual, relu=True, scale=None, zero_point=0, normal_scale=6 / 255, default_scale=0.1,
+                    default_zero_point=128):
+        """conv, then the quantized add of `residual` (and a ReLU): quantized.add[_relu](conv(input), residual, scale, zero_point),
+        scale=None -> the reference's max(conv output scale, residual scale).  GPU: ONE btx_q8_contract_res launch behind the
+        sampling pre-pass; CPU: the conv, then torch's quantized add.  Returns the quantized sum."""
+        sc = self._scales(normal_scale, default_scale, default_zero_point)
+        if _base._BACKEND == "hip" and not input.is_cuda:
+            raise _lib.BtxError("backend 'hip' needs CUDA (ROCm) tensors")
+        if input.is_cuda and _base._BACKEND != "torch":
+            return self._forward_hip(input, sc, residual=residual, add=(scale, int(zero_point), bool(relu)))
+        out = self._forward_cpu(input, sc)
+        if isinstance(residual, _q8.QTensor):
+            residual = residual.as_torch_quint8()
+        return _q8.add(out, residual, max(out.q_scale(), residual.q_scale()) if scale is None else scale, zero_point, relu)

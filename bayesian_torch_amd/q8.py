@@ -57,6 +57,17 @@ class QTensor:
     def reshape(self, *shape):
         return QTensor(self.q.reshape(*shape), self.scale, self.zero_point)
 
+    def view(self, *shape):
+        """torch's view of the logical NCHW tensor.  A channels-last 4-D carrier is viewable as it is when H = W = 1 (the tensor
+        behind the average pool of a ResNet); any other 4-D carrier is put in NCHW order first, like reshape()."""
+        q = self.q
+        if q.dim() == 4 and not q.is_contiguous():
+            q = q.contiguous()
+        return QTensor(q.view(*shape), self.scale, self.zero_point)
+
+    def contiguous(self):
+        return self
+
     def to(self, *a, **kw):
         return QTensor(self.q.to(*a, **kw), self.scale, self.zero_point)
 
@@ -128,8 +139,16 @@ def sample_weights(mu_p, sigma_p, mu_b, sigma_b, n, taps, c, eps_c, chain, seed,
     return W, S, b_i
 
 
-def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplier, z_o, relu, out_f32, s_o):
-    """btx_q8_contract.  xq: uint8 [B, K] (Linear, kernel (1, 1)) or channels-last [B, C, H, W]."""
+def make_add(s_a, z_a, s_b, z_b, scale, zero_point, relu=False):
+    """BtxQ8Add: the three f32 constants of the add (pre_a, pre_b, 1 / s), computed here, once, in f32"""
+    f = np.float32
+    return _lib.Q8Add(float(f(s_a)), float(f(s_a) * f(-int(z_a))), float(f(s_b)), float(f(s_b) * f(-int(z_b))),
+                      float(f(1.0) / f(scale)), int(zero_point), 1 if relu else 0)
+
+
+def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplier, z_o, relu, out_f32, s_o, residual=None, add=None):
+    """btx_q8_contract, or with `residual` (uint8, the output's shape and layout) and `add` (make_add) btx_q8_contract_res.
+    xq: uint8 [B, K] (Linear, kernel (1, 1)) or channels-last [B, C, H, W]."""
     g = _lib.Geom()
     if xq.dim() == 2:
         g.NB, g.C, g.H, g.W = xq.shape[0], xq.shape[1], 1, 1
@@ -151,7 +170,102 @@ def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplie
         out = torch.empty((g.NB, g.N), dtype=dt, device=xq.device)
     else:
         out = torch.empty((g.NB, g.N, oh, ow), dtype=dt, device=xq.device, memory_format=torch.channels_last)
+    if residual is not None:
+        if residual.dtype != torch.uint8 or residual.shape != out.shape or residual.device != out.device:
+            raise _lib.BtxError("quantized conv: the residual must be uint8 of the output's shape %s on its device (got %s %s)"
+                                % (tuple(out.shape), residual.dtype, tuple(residual.shape)))
+        if residual.dim() == 4:
+            residual = residual.contiguous(memory_format=torch.channels_last)
+        _lib.check(_lib.lib().btx_q8_contract_res(ctypes.byref(g), xq.data_ptr(), int(z_x), W.data_ptr(), S.data_ptr(), b_i.data_ptr(),
+                                                  float(multiplier), int(z_o), 1 if relu else 0, 1 if out_f32 else 0,
+                                                  residual.data_ptr(), ctypes.byref(add), out.data_ptr(), _stream(xq.device)))
+        return out
     _lib.check(_lib.lib().btx_q8_contract(ctypes.byref(g), xq.data_ptr(), int(z_x), W.data_ptr(), S.data_ptr(), b_i.data_ptr(),
                                           float(multiplier), int(z_o), 1 if relu else 0, 1 if out_f32 else 0, float(np.float32(s_o)),
                                           out.data_ptr(), _stream(xq.device)))
     return out
+
+
+# ---- between the layers: one `forward` for both devices -------------------------------------------------------------------
+def _is_quint8(x):
+    return isinstance(x, torch.Tensor) and x.dtype == torch.quint8
+
+
+def _gpu_q(x, what):
+    if isinstance(x, QTensor):
+        if not x.is_cuda:
+            raise _lib.BtxError("q8.%s: a QTensor runs on the GPU; on the CPU pass a torch.quint8 tensor (QTensor.as_torch_quint8())" % what)
+        return x
+    raise _lib.BtxError("q8.%s takes a q8.QTensor (GPU) or a torch.quint8 tensor (CPU), got %s" % (what, type(x).__name__))
+
+
+def add(a, b, scale, zero_point, relu=False):
+    """torch.ops.quantized.add / add_relu (CPU, torch.quint8), or btx_q8_add (GPU, QTensor): one launch"""
+    if _is_quint8(a) and _is_quint8(b):
+        op = torch.ops.quantized.add_relu if relu else torch.ops.quantized.add
+        return op(a, b, float(scale), int(zero_point))
+    a, b = _gpu_q(a, "add"), _gpu_q(b, "add")
+    if a.shape != b.shape or a.device != b.device:
+        raise _lib.BtxError("q8.add: operands differ in shape or device (%s, %s)" % (tuple(a.shape), tuple(b.shape)))
+    out = torch.empty_like(a.q)
+    bq = b.q if b.q.stride() == a.q.stride() else b.q.contiguous(memory_format=torch.channels_last if a.q.dim() == 4 else torch.contiguous_format)
+    if not out.is_contiguous() and not (out.dim() == 4 and out.is_contiguous(memory_format=torch.channels_last)):
+        raise _lib.BtxError("q8.add: operands must be dense")
+    p = make_add(a.scale, a.zero_point, b.scale, b.zero_point, scale, zero_point, relu)
+    _lib.check(_lib.lib().btx_q8_add(a.q.data_ptr(), bq.data_ptr(), out.data_ptr(), out.numel(), ctypes.byref(p), _stream(out.device)))
+    return QTensor(out, scale, zero_point)
+
+
+def _pool_args(x, what):
+    x = _gpu_q(x, what)
+    if x.q.dim() != 4:
+        raise _lib.BtxError("q8.%s takes a [B, C, H, W] tensor (got %d-D)" % (what, x.q.dim()))
+    return x
+
+
+def _one(v, what):
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2 or v[0] != v[1]:
+            raise _lib.BtxError("q8 pooling: %s must be square (got %s)" % (what, (v,)))
+        v = v[0]
+    return int(v)
+
+
+def max_pool2d(x, k, stride=None, padding=0):
+    """F.max_pool2d on quint8 (CPU), btx_q8_maxpool2d_cl (GPU).  Scale and zero point pass through."""
+    stride = k if stride is None else stride
+    if _is_quint8(x):
+        return torch.nn.functional.max_pool2d(x, k, stride, padding)
+    x = _pool_args(x, "max_pool2d")
+    k, s, p = _one(k, "kernel"), _one(stride, "stride"), _one(padding, "padding")
+    nb, c, h, w = x.q.shape
+    ho, wo = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+    if ho <= 0 or wo <= 0:
+        raise _lib.BtxError("q8.max_pool2d: the window does not fit the input")
+    out = torch.empty((nb, c, ho, wo), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().btx_q8_maxpool2d_cl(x.q.data_ptr(), out.data_ptr(), nb, h, w, c, k, s, p, _stream(x.device)))
+    return QTensor(out, x.scale, x.zero_point)
+
+
+def avg_pool2d(x, k, stride=None, padding=0, ceil_mode=False):
+    """F.avg_pool2d on quint8 (CPU), btx_q8_avgpool2d_cl (GPU: no padding, floor mode).  Scale and zero point pass through."""
+    stride = k if stride is None else stride
+    if _is_quint8(x):
+        return torch.nn.functional.avg_pool2d(x, k, stride, padding, ceil_mode)
+    x = _pool_args(x, "avg_pool2d")
+    k, s, p = _one(k, "kernel"), _one(stride, "stride"), _one(padding, "padding")
+    nb, c, h, w = x.q.shape
+    ho, wo = (h - k) // s + 1, (w - k) // s + 1
+    if ho <= 0 or wo <= 0:
+        raise _lib.BtxError("q8.avg_pool2d: the window does not fit the input")
+    out = torch.empty((nb, c, ho, wo), dtype=torch.uint8, device=x.device, memory_format=torch.channels_last)
+    _lib.check(_lib.lib().btx_q8_avgpool2d_cl(x.q.data_ptr(), out.data_ptr(), nb, h, w, c, k, s, p, 1 if ceil_mode else 0,
+                                              x.zero_point, _stream(x.device)))
+    return QTensor(out, x.scale, x.zero_point)
+
+
+def relu(x):
+    """max(q, z): torch.relu on quint8, QTensor.relu() on the GPU"""
+    if _is_quint8(x):
+        return torch.relu(x)
+    return _gpu_q(x, "relu").relu()

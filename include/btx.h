@@ -571,7 +571,25 @@ int btx_eau_bwd(const float* error, const float* other, int B, int conf_form, co
  *   relu ? out_zero_point : 0, 255).  out: uint8 channels-last [NB][OH][OW][N], or with out_f32 the dequantized
  *   f32 (o - out_zero_point) * out_scale.
  * Errors: BTX_E_NULL, BTX_E_SHAPE (extents, scales <= 0, zero points outside [0, 255]), BTX_E_UNSUPPORTED (groups != 1, D or KD != 1,
- *   index spaces beyond 32 bits), BTX_E_DTYPE, BTX_E_ALIGN (W 16 bytes; S, b_i, the quantize output 4 bytes). */
+ *   index spaces beyond 32 bits), BTX_E_DTYPE, BTX_E_ALIGN (W 16 bytes; S, b_i, the quantize output 4 bytes).
+ *
+ * Between the layers (ABI 9, additive; the ops of the reference's models/bayesian/quantized_resnet_variational_large.py on quint8:
+ * torch.ops.quantized.add, nn.MaxPool2d, nn.AvgPool2d).  All are one launch, capturable: no allocation, no sync, no host read.
+ * BtxQ8Add (HOST struct): the add of a (uint8, s_a, z_a) and b (uint8, s_b, z_b) into (s, zero_point):
+ *   da = fma(s_a, a, pre_a), pre_a = f32(s_a * f32(-z_a)), ONE rounding (what torch's vector kernel computes, not (a - z_a) * s_a);
+ *   db alike;  o = clamp(rint((da + db) * inv_s) + zero_point, relu ? zero_point : 0, 255), inv_s = f32(1) / f32(s).  The caller
+ *   computes pre_a, pre_b, inv_s once in f32.
+ * btx_q8_add: out[i] = add(a[i], b[i]) over n bytes; 16 bytes per thread when the three bases are 16-byte aligned, bytewise else.
+ * btx_q8_contract_res: btx_q8_contract with a residual operand in its store: the lane's four uint8 outputs o (formed exactly as
+ *   btx_q8_contract forms them, the conv's own ReLU clamp included) become add(o, residual[m][n]) with add_host->s_a / pre_a
+ *   describing the conv's (out scale, out_zero_point).  residual: uint8 channels-last [NB][OH][OW][N].  Bit-identical to
+ *   btx_q8_contract followed by btx_q8_add.  out_f32 != 0 -> BTX_E_UNSUPPORTED.
+ * btx_q8_maxpool2d_cl / btx_q8_avgpool2d_cl: uint8 channels-last [NB][H][W][C] -> [NB][Ho][Wo][C], floor mode, Ho = (H + 2 pad - k)
+ *   / stride + 1; scale and zero point pass through.  16 channels per thread when C % 16 == 0 and both bases are 16-byte aligned,
+ *   bytewise otherwise.  max: the maximum over the in-image window elements, 2 * pad <= k.  avg: o = clamp(rint(f32(sum - k*k *
+ *   zero_point) * f32(1.0 / (k*k))) + zero_point, 0, 255), int32 sum, the reciprocal computed in double and rounded once;
+ *   pad != 0 or ceil_mode != 0 -> BTX_E_UNSUPPORTED.
+ * Errors as above: BTX_E_NULL, BTX_E_SHAPE (extents, n == 0, s_a / s_b / inv_s <= 0, zero points outside [0, 255]). */
 typedef struct BtxQ8Chain {
   float s_sigma, s_mu, s_eps, inv_s_eps, s_d, inv_s_d, inv_s_w;
   double bias_div;
@@ -584,6 +602,17 @@ int btx_q8_sample_weights(const int8_t* mu_i, const int8_t* sigma_i, const float
                           int8_t* W, int32_t* S, int32_t* b_i, void* stream);
 int btx_q8_contract(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
                     float multiplier, int out_zero_point, int relu, int out_f32, float out_scale, void* out, void* stream);
+typedef struct BtxQ8Add {
+  float s_a, pre_a, s_b, pre_b, inv_s;
+  int zero_point, relu;
+} BtxQ8Add;
+int btx_q8_add(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, const BtxQ8Add* add_host, void* stream);
+int btx_q8_contract_res(const BtxGeom* g, const uint8_t* x, int x_zero_point, const int8_t* W, const int32_t* S, const int32_t* b_i,
+                        float multiplier, int out_zero_point, int relu, int out_f32, const uint8_t* residual, const BtxQ8Add* add_host,
+                        void* out, void* stream);
+int btx_q8_maxpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, void* stream);
+int btx_q8_avgpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, int ceil_mode,
+                        int zero_point, void* stream);
 
 #ifdef __cplusplus
 }
