@@ -93,6 +93,18 @@ class Q8Add(ctypes.Structure):
                [("zero_point", ctypes.c_int32), ("relu", ctypes.c_int32)]
 
 
+class Q8Delta(ctypes.Structure):
+    _fields_ = [("inv_s_eps", ctypes.c_float), ("mult", ctypes.c_float), ("mean_bias", ctypes.c_int32), ("pert_bias", ctypes.c_int32),
+                ("div_mean", ctypes.c_double), ("div_pert", ctypes.c_double)]
+
+
+class Q8Flipout(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("z_x", "z_xp", "z_mean", "z_pert", "z_p2", "sin_pos", "sin_neg", "sout_pos", "sout_neg")] + \
+               [(n, ctypes.c_float) for n in ("mult_xp", "mult_mean", "mult_pert", "mult_p2", "out_scale")]
+
+
+Q8_BIAS_NONE, Q8_BIAS_MU, Q8_BIAS_SIGMA_EPS = 0, 1, 2
+
 EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_gauss", "btx_kl_model_workspace_bytes",
            "btx_kl_gauss_model", "btx_kl_gauss_model_bwd", "btx_contract_wgrad",
            "btx_contract_workspace_bytes", "btx_contract_fwd", "btx_contract_fwd_ex", "btx_contract_fwd_lanes", "btx_contract_pool_shape", "btx_contract_plan_info", "btx_out_shape", "btx_fill_eps", "btx_fill_sign", "btx_rho_grad",
@@ -103,7 +115,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_lstm_fwd_train", "btx_lstm_bwd",
            "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd",
            "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract",
-           "btx_q8_add", "btx_q8_contract_res", "btx_q8_maxpool2d_cl", "btx_q8_avgpool2d_cl")
+           "btx_q8_add", "btx_q8_contract_res", "btx_q8_maxpool2d_cl", "btx_q8_avgpool2d_cl",
+           "btx_q8_sample_delta", "btx_q8_contract_flipout")
 
 
 def lib_path():
@@ -242,6 +255,12 @@ def lib():
     L.btx_q8_maxpool2d_cl.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.btx_q8_avgpool2d_cl.restype = i32
     L.btx_q8_avgpool2d_cl.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.btx_q8_sample_delta.restype = i32
+    L.btx_q8_sample_delta.argtypes = [vp, vp, vp, i32, i32, i32, i32, ctypes.POINTER(Q8Delta), ctypes.POINTER(Rng), vp, vp, vp, vp, vp,
+                                      vp, vp]
+    L.btx_q8_contract_flipout.restype = i32
+    L.btx_q8_contract_flipout.argtypes = [ctypes.POINTER(Geom), vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Q8Flipout),
+                                          ctypes.POINTER(Q8Add), ctypes.POINTER(Rng), i32, vp, vp, i32, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -314,6 +314,293 @@ __global__ __launch_bounds__(256) void q8_contract_kernel(const Q8ContractArgs a
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Flipout (DESIGN.md §13 "Flipout"): the delta pre-pass and the two-GEMM contraction
+// ---------------------------------------------------------------------------------------------------------------------
+// quantized.mul of two quantized values: c = (a - z_a) * (b - z_b) in int32 (formed by the caller),
+// o = clamp(rint(f32(c) * m) + z_o, lo, hi), m = f32(f32(s_a) * f32(s_b)) * (f32(1) / f32(s_o)) computed once on the host
+__device__ __forceinline__ float q8_mul1(int c, float m, float z, float lo, float hi) {
+  return fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)c, m)), z), lo), hi);
+}
+
+struct Q8DeltaArgs {
+  const int8_t* sigma_i;                       // [N][taps][C]
+  const float* mu_b; const float* sigma_b;     // [N] or NULL
+  const float* eps_w; const float* eps_b;      // explicit noise or NULL -> BTX-RNG v1
+  int8_t* D; int32_t* S; int32_t* bm_i; int32_t* bp_i;
+  int N, taps, C, eps_C, Cp, Kp;
+  int mean_bias, pert_bias;                    // BTX_Q8_BIAS_*
+  float inv_s_eps, mult;
+  double div_mean, div_pert;
+  uint32_t k0, k1, sample, layer;
+  const uint32_t* sample_ptr;
+};
+
+__global__ __launch_bounds__(256) void q8_delta_kernel(const Q8DeltaArgs a) {
+  __shared__ int red[256];
+  uint32_t sample = a.sample;
+  if (a.sample_ptr) sample = __builtin_amdgcn_readfirstlane(*a.sample_ptr);
+  const int n = blockIdx.x;
+  const int8_t* sg = a.sigma_i + (size_t)n * a.taps * a.C;
+  int8_t* drow = a.D + (size_t)n * a.Kp;
+  int sum = 0;
+  for (int p = threadIdx.x * 4; p < a.Kp; p += 256 * 4) {
+    const int tap = p / a.Cp, c0 = p - tap * a.Cp;
+    uint32_t pack = 0;
+    if (tap < a.taps && c0 < a.C) {
+      float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (!a.eps_w)
+        btx_normal4((uint32_t)((((size_t)n * a.taps + tap) * a.eps_C + c0) >> 2), sample, a.layer, BTX_STREAM_EPS_W, a.k0, a.k1, z);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = c0 + e;
+        if (c < a.C) {
+          const size_t src = (size_t)tap * a.C + c;
+          const float eps = a.eps_w ? a.eps_w[(size_t)n * a.taps * a.C + src] : z[e];
+          const int eps_i = (int)q8_round_clamp(eps, a.inv_s_eps, 0.0f, -128.0f, 127.0f);
+          const int d = (int)q8_mul1((int)sg[src] * eps_i, a.mult, 0.0f, -128.0f, 127.0f);
+          sum += d;
+          pack |= ((uint32_t)d & 0xffu) << (8 * e);
+        }
+      }
+    }
+    *reinterpret_cast<uint32_t*>(drow + p) = pack;
+  }
+  red[threadIdx.x] = sum;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    a.S[n] = red[0];
+    float bs = 0.0f;
+    if (a.mean_bias == BTX_Q8_BIAS_SIGMA_EPS || a.pert_bias == BTX_Q8_BIAS_SIGMA_EPS) {
+      const float eb = a.eps_b ? a.eps_b[n] : btx_normal1((uint64_t)n, sample, a.layer, BTX_STREAM_EPS_B, a.k0, a.k1);
+      bs = __fmul_rn(a.sigma_b[n], eb);
+    }
+    const float bm = a.mean_bias == BTX_Q8_BIAS_MU ? a.mu_b[n] : bs, bp = a.pert_bias == BTX_Q8_BIAS_MU ? a.mu_b[n] : bs;
+    a.bm_i[n] = a.mean_bias == BTX_Q8_BIAS_NONE ? 0 : (int)rint((double)bm / a.div_mean);
+    a.bp_i[n] = a.pert_bias == BTX_Q8_BIAS_NONE ? 0 : (int)rint((double)bp / a.div_pert);
+  }
+}
+
+struct Q8FlipArgs {
+  const uint8_t* x; const int8_t* Wm; const int8_t* D;
+  const int32_t* Sm; const int32_t* Sd; const int32_t* bm_i; const int32_t* bp_i;
+  const int8_t* sign_in; const int8_t* sign_out;   // explicit +1 / -1 (channels-last like x / out) or NULL -> BTX-RNG v1
+  void* out;
+  int NB, H, Wd, C, N, KH, KW, sh, sw, ph, pw, dh, dw, OH, OW;
+  int Cp, Kp, taps, sign_C;
+  long long M;
+  BtxQ8Flipout f;
+  Q8AddArgs add;
+  int out_f32, x_vec, out_vec;
+  uint32_t k0, k1, sample, layer;
+  const uint32_t* sample_ptr;
+};
+
+__global__ __launch_bounds__(256) void q8_flipout_kernel(const Q8FlipArgs a) {
+  // q8_contract_kernel's tiling and staging with four tiles per step: W_mu, D, x, x'
+  __shared__ __attribute__((aligned(16))) uint8_t lds_w[2][Q8_BN * Q8_LDS_ROW];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_d[2][Q8_BN * Q8_LDS_ROW];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_x[2][Q8_BM * Q8_LDS_ROW];
+  __shared__ __attribute__((aligned(16))) uint8_t lds_p[2][Q8_BM * Q8_LDS_ROW];
+  // x' (as int8: xor 0x80) for every (sign, x byte): 512 entries kept in the 16 padding bytes of the first 32 rows of lds_w[0], which
+  // the staging never writes (a 513th LDS KB would cost the fourth workgroup per CU)
+  auto lut = [&](uint32_t i) -> uint8_t& { return lds_w[0][(i >> 4) * Q8_LDS_ROW + 64 + (i & 15u)]; };
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long m0 = (long long)blockIdx.x * Q8_BM;
+  const int n0 = blockIdx.y * Q8_BN;
+
+  uint32_t kin_a = 0, kin_b = 0, kout_a = 0, kout_b = 0;
+  if (!a.sign_in || !a.sign_out) {  // the sign keys of this sample (BtxRng.sample_idx_dev: resolved here, at run time)
+    uint32_t sample = a.sample;
+    if (a.sample_ptr) sample = __builtin_amdgcn_readfirstlane(*a.sample_ptr);
+    const BtxPhilox4 ki = btx_philox4x32_10(0u, sample, a.layer, BTX_STREAM_SIGN_IN, a.k0, a.k1);
+    const BtxPhilox4 ko = btx_philox4x32_10(0u, sample, a.layer, BTX_STREAM_SIGN_OUT, a.k0, a.k1);
+    kin_a = __builtin_amdgcn_readfirstlane(ki.x[0]); kin_b = __builtin_amdgcn_readfirstlane(ki.x[1]);
+    kout_a = __builtin_amdgcn_readfirstlane(ko.x[0]); kout_b = __builtin_amdgcn_readfirstlane(ko.x[1]);
+  }
+
+  const int lrow = tid >> 2, lq = tid & 3;
+  const long long lm = m0 + lrow;
+  const bool m_ok = lm < a.M;
+  int img = 0, ih0 = 0, iw0 = 0;
+  if (m_ok) {
+    const int ow = (int)(lm % a.OW);
+    const long long t = lm / a.OW;
+    const int oh = (int)(t % a.OH);
+    img = (int)(t / a.OH);
+    ih0 = oh * a.sh - a.ph;
+    iw0 = ow * a.sw - a.pw;
+  }
+  const int ln = n0 + lrow;
+  const uint32_t zfill = (uint32_t)(a.f.z_x & 0xff) * 0x01010101u;
+  const uint32_t pfill = ((uint32_t)(a.f.z_xp & 0xff) * 0x01010101u) ^ 0x80808080u;   // the x' tile is staged as int8
+  const float zp6 = (float)a.f.z_xp;
+  lut((uint32_t)tid) = (uint8_t)((int)q8_mul1((tid - a.f.z_x) * a.f.sin_pos, a.f.mult_xp, zp6, 0.0f, 255.0f) ^ 0x80);
+  lut(256u + (uint32_t)tid) = (uint8_t)((int)q8_mul1((tid - a.f.z_x) * a.f.sin_neg, a.f.mult_xp, zp6, 0.0f, 255.0f) ^ 0x80);
+  __syncthreads();
+
+  v4i acc[4], accd[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { acc[j] = (v4i){0, 0, 0, 0}; accd[j] = (v4i){0, 0, 0, 0}; }
+
+  // one K step's four 16-byte chunks of this thread.  x' is formed here from the loaded x bytes and the element's sign: the sign of
+  // element (pixel, c) does not depend on the tap that reads it, so every tap sees the same x' as a materialised tensor would give
+  auto load_chunks = [&](int k0, uint4& wv, uint4& dv, uint4& xv, uint4& pv) {
+    wv = make_uint4(0u, 0u, 0u, 0u);
+    dv = make_uint4(0u, 0u, 0u, 0u);
+    if (ln < a.N) {
+      wv = *reinterpret_cast<const uint4*>(a.Wm + (size_t)ln * a.Kp + k0 + 16 * lq);
+      dv = *reinterpret_cast<const uint4*>(a.D + (size_t)ln * a.Kp + k0 + 16 * lq);
+    }
+    xv = make_uint4(zfill, zfill, zfill, zfill);
+    pv = make_uint4(pfill, pfill, pfill, pfill);
+    const int k = k0 + 16 * lq;
+    const int tap = k / a.Cp, c0 = k - tap * a.Cp;
+    if (m_ok && tap < a.taps && c0 < a.C) {
+      const int kh = tap / a.KW, kw = tap - kh * a.KW;
+      const int ih = ih0 + kh * a.dh, iw = iw0 + kw * a.dw;
+      if (ih >= 0 && ih < a.H && iw >= 0 && iw < a.Wd) {
+        const size_t pix = ((size_t)img * a.H + ih) * a.Wd + iw;
+        const uint8_t* src = a.x + pix * a.C + c0;
+        uint32_t xs[4];
+        if (a.x_vec) {
+          const uint4 v = *reinterpret_cast<const uint4*>(src);
+          xs[0] = v.x; xs[1] = v.y; xs[2] = v.z; xs[3] = v.w;
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            uint32_t wd = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int c = c0 + 4 * q + e;
+              const uint32_t byte = (c < a.C) ? (uint32_t)src[4 * q + e] : (uint32_t)(a.f.z_x & 0xff);
+              wd |= byte << (8 * e);
+            }
+            xs[q] = wd;
+          }
+        }
+        xv = make_uint4(xs[0], xs[1], xs[2], xs[3]);
+        // 16 sign bits, bit e = 1 for a negative sign of channel c0 + e
+        uint32_t neg = 0;
+        if (a.sign_in) {
+          const int8_t* sp = a.sign_in + pix * a.C + c0;
+#pragma unroll
+          for (int e = 0; e < 16; ++e)
+            if (c0 + e < a.C && sp[e] < 0) neg |= 1u << e;
+        } else {
+          // the float layer's index space: rows of sign_C channels.  sign_C and c0 are multiples of 8, so the chunk is two aligned
+          // groups of 8 signs; group g of a 32-sign word keeps its even elements in bits 15 - 4g .. 12 - 4g and its odd ones in
+          // bits 31 - 4g .. 28 - 4g, first element highest (btx_sign_bitpos)
+          const unsigned long long i0 = (unsigned long long)pix * (unsigned)a.sign_C + (unsigned)c0;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const unsigned long long i = i0 + 8u * h;
+            const uint32_t w = btx_sign_word((uint32_t)(i >> 5), kin_a, kin_b);
+            const int g4 = 4 * (int)(((uint32_t)i & 31u) >> 3);
+            const uint32_t ev = (w >> (12 - g4)) & 0xfu, od = (w >> (28 - g4)) & 0xfu;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) neg |= ((((j & 1) ? od : ev) >> (3 - (j >> 1))) & 1u) << (8 * h + j);
+          }
+        }
+        // x' = mul(x, sign byte) depends on the x byte and the sign only: one of 512 table entries (already xor-ed to int8).
+        // Channels >= C of a chunk meet zero weights in D, so whatever byte they get contributes nothing.
+        uint32_t ps[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          uint32_t wd = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const uint32_t idx = ((xs[q] >> (8 * e)) & 0xffu) | (((neg >> (4 * q + e)) & 1u) << 8);
+            wd |= (uint32_t)lut(idx) << (8 * e);
+          }
+          ps[q] = wd;
+        }
+        pv = make_uint4(ps[0], ps[1], ps[2], ps[3]);
+      }
+    }
+    xv.x ^= 0x80808080u; xv.y ^= 0x80808080u; xv.z ^= 0x80808080u; xv.w ^= 0x80808080u;   // pv is int8 already
+  };
+
+  uint4 wv, dv, xv, pv;
+  load_chunks(0, wv, dv, xv, pv);
+  int stage = 0;
+  for (int k0 = 0; k0 < a.Kp; k0 += Q8_BK, stage ^= 1) {
+    const int so = lrow * Q8_LDS_ROW + 16 * lq;
+    *reinterpret_cast<uint4*>(lds_w[stage] + so) = wv;
+    *reinterpret_cast<uint4*>(lds_d[stage] + so) = dv;
+    *reinterpret_cast<uint4*>(lds_x[stage] + so) = xv;
+    *reinterpret_cast<uint4*>(lds_p[stage] + so) = pv;
+    __syncthreads();
+    if (k0 + Q8_BK < a.Kp) load_chunks(k0 + Q8_BK, wv, dv, xv, pv);
+    const int xo = (16 * wave + (lane & 15)) * Q8_LDS_ROW + 16 * (lane >> 4);
+    const v4i xf = *reinterpret_cast<const v4i*>(lds_x[stage] + xo);
+    const v4i pf = *reinterpret_cast<const v4i*>(lds_p[stage] + xo);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int wo = (16 * j + (lane & 15)) * Q8_LDS_ROW + 16 * (lane >> 4);
+      const v4i wf = *reinterpret_cast<const v4i*>(lds_w[stage] + wo);
+      const v4i df = *reinterpret_cast<const v4i*>(lds_d[stage] + wo);
+      acc[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wf, xf, acc[j], 0, 0, 0);
+      accd[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(df, pf, accd[j], 0, 0, 0);
+    }
+  }
+
+  // ---- store: requantize both accumulators, sign-multiply the perturbation, add, clamp
+  const long long m = m0 + 16 * wave + (lane & 15);
+  if (m >= a.M) return;
+  const int zc = 128 - a.f.z_x, zcp = 128 - a.f.z_xp;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int nb = n0 + 16 * j + 4 * (lane >> 4);
+    if (nb >= a.N) continue;
+    float of[4];
+    uint32_t pack = 0;
+    const size_t off = (size_t)m * a.N + nb;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = nb + r;
+      float o = 0.0f;
+      if (n < a.N) {
+        const int v1 = acc[j][r] + zc * a.Sm[n] + a.bm_i[n];
+        const float o1 = fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)v1, a.f.mult_mean)), (float)a.f.z_mean), 0.0f), 255.0f);
+        const int v2 = accd[j][r] + zcp * a.Sd[n] + a.bp_i[n];
+        const float p = fminf(fmaxf(__fadd_rn(rintf(__fmul_rn((float)v2, a.f.mult_pert)), (float)a.f.z_pert), 0.0f), 255.0f);
+        bool negs;
+        if (a.sign_out) {
+          negs = a.sign_out[off + r] < 0;
+        } else {
+          const unsigned long long io = (unsigned long long)(off + r);
+          const uint32_t w = btx_sign_word((uint32_t)(io >> 5), kout_a, kout_b);
+          negs = ((w >> btx_sign_bitpos((uint32_t)io & 31u)) & 1u) != 0;
+        }
+        const float p2 = q8_mul1(((int)p - a.f.z_pert) * (negs ? a.f.sout_neg : a.f.sout_pos), a.f.mult_p2, (float)a.f.z_p2, 0.0f, 255.0f);
+        o = q8_add1(o1, p2, a.add);
+      }
+      pack |= (uint32_t)(int)o << (8 * r);
+      of[r] = __fmul_rn(o - a.add.z, a.f.out_scale);
+    }
+    if (a.out_f32) {
+      float* o = reinterpret_cast<float*>(a.out) + off;
+      if (a.out_vec && nb + 4 <= a.N) {
+        *reinterpret_cast<float4*>(o) = make_float4(of[0], of[1], of[2], of[3]);
+      } else {
+        for (int r = 0; r < 4 && nb + r < a.N; ++r) o[r] = of[r];
+      }
+    } else {
+      uint8_t* o = reinterpret_cast<uint8_t*>(a.out) + off;
+      if (a.out_vec && nb + 4 <= a.N) {
+        *reinterpret_cast<uint32_t*>(o) = pack;
+      } else {
+        for (int r = 0; r < 4 && nb + r < a.N; ++r) o[r] = (uint8_t)(pack >> (8 * r));
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // between the layers: add, max-pool, avg-pool on uint8
 // ---------------------------------------------------------------------------------------------------------------------
 // one thread per 16 consecutive bytes; vec: the three bases are 16-byte aligned.  The last group (n % 16 bytes) and every group of
@@ -592,6 +879,93 @@ int btx_q8_avgpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, in
   if (pad < 0) return BTX_E_SHAPE;
   if (pad != 0 || ceil_mode) return BTX_E_UNSUPPORTED;
   return q8_pool_launch<true>(x, out, NB, H, W, C, k, stride, 0, zero_point, stream);
+}
+
+int btx_q8_sample_delta(const int8_t* sigma_i, const float* mu_b, const float* sigma_b, int N, int taps, int C, int eps_C,
+                        const BtxQ8Delta* delta_host, const BtxRng* rng, const float* eps_w, const float* eps_b, int8_t* D, int32_t* S_d,
+                        int32_t* b_mean_i, int32_t* b_pert_i, void* stream) {
+  if (!sigma_i || !delta_host || !D || !S_d || !b_mean_i || !b_pert_i) return BTX_E_NULL;
+  if (!rng && !eps_w) return BTX_E_NULL;
+  const BtxQ8Delta& d = *delta_host;
+  if (d.mean_bias < BTX_Q8_BIAS_NONE || d.mean_bias > BTX_Q8_BIAS_SIGMA_EPS || d.pert_bias < BTX_Q8_BIAS_NONE ||
+      d.pert_bias > BTX_Q8_BIAS_SIGMA_EPS)
+    return BTX_E_SHAPE;
+  const bool need_mu = d.mean_bias == BTX_Q8_BIAS_MU || d.pert_bias == BTX_Q8_BIAS_MU;
+  const bool need_sigma = d.mean_bias == BTX_Q8_BIAS_SIGMA_EPS || d.pert_bias == BTX_Q8_BIAS_SIGMA_EPS;
+  if ((need_mu && !mu_b) || (need_sigma && !sigma_b)) return BTX_E_NULL;
+  if (need_sigma && !rng && !eps_b) return BTX_E_NULL;
+  if (N <= 0 || taps <= 0 || C <= 0) return BTX_E_SHAPE;
+  if (eps_C < C || (eps_C & 7)) {
+    if (!eps_w || eps_C != C) return BTX_E_SHAPE;
+  }
+  if (!(d.inv_s_eps > 0.0f) || !(d.mult > 0.0f) || !(d.div_mean > 0.0) || !(d.div_pert > 0.0)) return BTX_E_SHAPE;
+  const long long kp = q8_kp(taps, C);
+  if (kp > 0x7fffffc0LL || (long long)N * taps * (long long)eps_C > 0xfffffffcLL) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)D & 15u) || ((uintptr_t)S_d & 3u) || ((uintptr_t)b_mean_i & 3u) || ((uintptr_t)b_pert_i & 3u)) return BTX_E_ALIGN;
+  Q8DeltaArgs a;
+  a.sigma_i = sigma_i; a.mu_b = mu_b; a.sigma_b = sigma_b; a.eps_w = eps_w; a.eps_b = eps_b;
+  a.D = D; a.S = S_d; a.bm_i = b_mean_i; a.bp_i = b_pert_i;
+  a.N = N; a.taps = taps; a.C = C; a.eps_C = eps_C; a.Cp = q8_cp(C); a.Kp = (int)kp;
+  a.mean_bias = d.mean_bias; a.pert_bias = d.pert_bias;
+  a.inv_s_eps = d.inv_s_eps; a.mult = d.mult; a.div_mean = d.div_mean; a.div_pert = d.div_pert;
+  a.k0 = rng ? (uint32_t)rng->seed : 0u;
+  a.k1 = rng ? (uint32_t)(rng->seed >> 32) : 0u;
+  a.sample = rng ? rng->sample_idx : 0u;
+  a.layer = rng ? rng->layer_id : 0u;
+  a.sample_ptr = rng ? (const uint32_t*)rng->sample_idx_dev : nullptr;
+  hipLaunchKernelGGL(q8_delta_kernel, dim3(N), dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int btx_q8_contract_flipout(const BtxGeom* g, const uint8_t* x, const int8_t* W_mu, const int32_t* S_mu, const int32_t* b_mean_i,
+                            const int8_t* D, const int32_t* S_d, const int32_t* b_pert_i, const BtxQ8Flipout* flip_host,
+                            const BtxQ8Add* add_host, const BtxRng* rng, int sign_C, const int8_t* sign_in, const int8_t* sign_out,
+                            int out_f32, void* out, void* stream) {
+  if (!g || !x || !W_mu || !S_mu || !b_mean_i || !D || !S_d || !b_pert_i || !flip_host || !add_host || !out) return BTX_E_NULL;
+  if (!rng && (!sign_in || !sign_out)) return BTX_E_NULL;   // the signs come from somewhere
+  const int rc = q8_check_geom(g);
+  if (rc) return rc;
+  const BtxQ8Flipout& f = *flip_host;
+  const int zs[5] = {f.z_x, f.z_xp, f.z_mean, f.z_pert, f.z_p2};
+  for (int i = 0; i < 5; ++i)
+    if (zs[i] < 0 || zs[i] > 255) return BTX_E_SHAPE;
+  if (!(f.mult_xp > 0.0f) || !(f.mult_mean > 0.0f) || !(f.mult_pert > 0.0f) || !(f.mult_p2 > 0.0f)) return BTX_E_SHAPE;
+  if (f.sin_pos < -255 || f.sin_pos > 255 || f.sin_neg < -255 || f.sin_neg > 255 || f.sout_pos < -255 || f.sout_pos > 255 ||
+      f.sout_neg < -255 || f.sout_neg > 255)
+    return BTX_E_SHAPE;
+  if (out_f32 && !(f.out_scale > 0.0f)) return BTX_E_SHAPE;
+  if (!sign_in && (sign_C < g->C || (sign_C & 7))) return BTX_E_SHAPE;   // the hash index space has rows of a multiple of 8 signs
+  Q8FlipArgs a;
+  const int rc2 = q8_add_args(add_host, &a.add);
+  if (rc2) return rc2;
+  const long long kp = q8_kp(g->KH * g->KW, g->C);
+  if (kp > 0x7fffffc0LL) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)W_mu & 15u) || ((uintptr_t)D & 15u) || ((uintptr_t)S_mu & 3u) || ((uintptr_t)S_d & 3u) || ((uintptr_t)b_mean_i & 3u) ||
+      ((uintptr_t)b_pert_i & 3u))
+    return BTX_E_ALIGN;
+  a.x = x; a.Wm = W_mu; a.D = D; a.Sm = S_mu; a.Sd = S_d; a.bm_i = b_mean_i; a.bp_i = b_pert_i;
+  a.sign_in = sign_in; a.sign_out = sign_out; a.out = out;
+  a.NB = g->NB; a.H = g->H; a.Wd = g->W; a.C = g->C; a.N = g->N; a.KH = g->KH; a.KW = g->KW;
+  a.sh = g->sh; a.sw = g->sw; a.ph = g->ph; a.pw = g->pw; a.dh = g->dh; a.dw = g->dw;
+  a.OH = q8_out_extent(g->H, g->KH, g->sh, g->ph, g->dh);
+  a.OW = q8_out_extent(g->W, g->KW, g->sw, g->pw, g->dw);
+  a.taps = g->KH * g->KW; a.Cp = q8_cp(g->C); a.Kp = (int)kp;
+  a.sign_C = sign_in ? g->C : sign_C;
+  a.M = (long long)g->NB * a.OH * a.OW;
+  const long long mblocks = (a.M + Q8_BM - 1) / Q8_BM;
+  if (mblocks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+  a.f = f;
+  a.out_f32 = out_f32 ? 1 : 0;
+  a.x_vec = (g->C % 16 == 0 && ((uintptr_t)x & 15u) == 0) ? 1 : 0;
+  a.out_vec = out_f32 ? ((g->N % 4 == 0 && ((uintptr_t)out & 15u) == 0) ? 1 : 0) : ((g->N % 4 == 0 && ((uintptr_t)out & 3u) == 0) ? 1 : 0);
+  a.k0 = rng ? (uint32_t)rng->seed : 0u;
+  a.k1 = rng ? (uint32_t)(rng->seed >> 32) : 0u;
+  a.sample = rng ? rng->sample_idx : 0u;
+  a.layer = rng ? rng->layer_id : 0u;
+  a.sample_ptr = rng ? (const uint32_t*)rng->sample_idx_dev : nullptr;
+  const dim3 grid((unsigned)mblocks, (unsigned)((g->N + Q8_BN - 1) / Q8_BN));
+  hipLaunchKernelGGL(q8_flipout_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

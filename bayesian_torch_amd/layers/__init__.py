@@ -1,6 +1,6 @@
 """bayesian_torch_amd.layers — same export surface as the reference `bayesian_torch/layers/__init__.py:1-6`
-(the variational-forward hot path, the LSTM wrappers over its Linear layers and the INT8 twins of Linear / Conv2d Reparameterization:
-no quantized Flipout / LSTM and no tuple-passing wrappers — SURVEY.md §2 scope)."""
+(the variational-forward hot path, the LSTM wrappers over its Linear layers and the INT8 twins of Linear / Conv2d Reparameterization
+and Linear / Conv2d Flipout: no quantized LSTM and no tuple-passing wrappers — SURVEY.md §2 scope)."""
 from . import variational_layers
 from . import flipout_layers
 from .variational_layers import *

@@ -223,14 +223,17 @@ class _VariationalNd(BaseVariationalLayer_):
         from torch.ao.quantization import DeQuantStub, MinMaxObserver, QConfig, QuantStub
         sym = MinMaxObserver.with_args(dtype=torch.qint8, qscheme=torch.per_tensor_symmetric)
         aff = MinMaxObserver.with_args(dtype=torch.quint8)
-        self.qint_quant = nn.ModuleList([QuantStub(QConfig(weight=sym, activation=sym)) for _ in range(5)])
-        self.quint_quant = nn.ModuleList([QuantStub(QConfig(weight=aff, activation=aff)) for _ in range(2)])
+        n_sym, n_aff = (4, 8) if self._family == "flipout" else (5, 2)   # Flipout: linear_flipout.py:114-120, conv_flipout.py:339-345
+        self.qint_quant = nn.ModuleList([QuantStub(QConfig(weight=sym, activation=sym)) for _ in range(n_sym)])
+        self.quint_quant = nn.ModuleList([QuantStub(QConfig(weight=aff, activation=aff)) for _ in range(n_aff)])
         self.dequant = DeQuantStub()
         self.quant_prepare = True
 
     def _forward_calibrate(self, x, return_kl):
         """the calibration run (quant_prepare): the ATen chain of the reference forward, then every intermediate through its stub in
         the reference's order (linear_variational.py:180-190) — observers record ranges; no HIP involved"""
+        if self._family == "flipout":
+            return self._forward_calibrate_flipout(x, return_kl)
         mu, rho = self._w()
         mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
         sigma_w = BF.softplus_naive(rho)
@@ -252,6 +255,37 @@ class _VariationalNd(BaseVariationalLayer_):
         self.qint_quant[2](eps_w)
         self.qint_quant[3](tmp)
         self.qint_quant[4](weight)
+        if return_kl:
+            return out, kl
+        return out
+
+    def _forward_calibrate_flipout(self, x, return_kl):
+        """the Flipout calibration run: the reference's forward (conv_flipout.py:370-417, linear_flipout.py:135-175) as ATen ops, then
+        its eight quint8 and four qint8 stubs in its order (conv_flipout.py:419-434)"""
+        mu, rho = self._w()
+        mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
+        op = self._op
+        outputs = BF.contract_aten(x, mu, self.mu_bias, op)
+        sign_in = x.clone().uniform_(-1, 1).sign()
+        sign_out = outputs.clone().uniform_(-1, 1).sign()
+        sigma_w = BF.softplus_naive(rho)
+        eps_w = getattr(self, "eps_" + self._wn).data.normal_()
+        delta = sigma_w * eps_w
+        kl = self.kl_div(mu, sigma_w, self.prior_weight_mu, self.prior_weight_sigma) if return_kl else None
+        b = None
+        if self.mu_bias is not None:
+            sigma_b = BF.softplus_naive(self.rho_bias)
+            b = sigma_b * self.eps_bias.data.normal_()
+            if return_kl:
+                kl = kl + self.kl_div(self.mu_bias, sigma_b, self.prior_bias_mu, self.prior_bias_sigma)
+        x_tmp = x * sign_in
+        pert_tmp = BF.contract_aten(x_tmp, delta, b, op)
+        pert = pert_tmp * sign_out
+        out = outputs + pert
+        for stub, t in zip(self.quint_quant, (x, outputs, sign_in, sign_out, x_tmp, pert_tmp, pert, out)):
+            stub(t)
+        for stub, t in zip(self.qint_quant, (sigma_w, mu, eps_w, delta)):
+            stub(t)
         if return_kl:
             return out, kl
         return out

@@ -35,6 +35,10 @@ class Conv2dFlipout(_VariationalNd):
                     prior_mean, prior_variance, posterior_mu_init, posterior_rho_init, bias,
                     check_groups=False)
 
+    def prepare(self):
+        """add the reference's twelve QuantStubs (conv_flipout.py:339-345); forwards then calibrate (quant_prepare)"""
+        self._prepare_stubs()
+
 
 class Conv3dFlipout(_VariationalNd):
     """Conv3d with Flipout — reference layers/flipout_layers/conv_flipout.py:443-637."""

@@ -19,3 +19,7 @@ class LinearFlipout(_VariationalNd):
         self.posterior_rho_init = posterior_rho_init
         self._setup(in_features, out_features, 1, 1, 0, 1, 1, 0, prior_mean, prior_variance,
                     posterior_mu_init, posterior_rho_init, bias, check_groups=False)
+
+    def prepare(self):
+        """add the reference's twelve QuantStubs (linear_flipout.py:114-120); forwards then calibrate (quant_prepare)"""
+        self._prepare_stubs()

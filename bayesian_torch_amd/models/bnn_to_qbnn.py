@@ -5,23 +5,30 @@ Kept from the reference: the in-place traversal; `Quantized<ClassName>` as the t
 (scale, zero point) pairs over as `quant_dict` = [eps, mul, add, input, output]; fuse_conv_bn=True folds `bn1` into `conv1`,
 `bn2` into `conv2`, `bn3` into `conv3` and `downsample[1]` into `downsample[0]` and leaves nn.Identity() where the BatchNorm was.
 
-Quantized here: LinearReparameterization and Conv2dReparameterization.  Every other layer kind (Flipout, Conv1d / 3d / Transpose,
-LSTM and the Linear layers inside one, BatchNorm) is left as it is.  The twin keeps its source layer's BTX-RNG layer id and
-sample counter: at the same seed and sample index it draws the eps its float source would."""
+Quantized here: LinearReparameterization and Conv2dReparameterization, and with `flipout=True` LinearFlipout and Conv2dFlipout
+(reference models/bnn_to_qbnn.py: the Flipout twins; their twelve stubs hand over ten entries, qint_quant[2:] + quint_quant).  The
+default flipout=False leaves a Flipout layer as it is.  Every other layer kind (Conv1d / 3d / Transpose, LSTM and the Linear layers
+inside one, BatchNorm) is left as it is.  The twin keeps its source layer's BTX-RNG layer id and sample counter: at the same seed
+and sample index it draws the eps (and a Flipout twin the signs) its float source would."""
 import torch
 import torch.nn as nn
 
 from .. import layers as bayesian_layers
 
-_KINDS = ("LinearReparameterization", "Conv2dReparameterization")
+_KINDS = {"LinearReparameterization": "reparam", "Conv2dReparameterization": "reparam", "LinearFlipout": "flipout",
+          "Conv2dFlipout": "flipout"}
 
 
-def _convertible(m):
-    return type(m).__name__ in _KINDS and hasattr(m, "_btx_layer_id") and getattr(m, "_family", None) == "reparam"
+def _convertible(m, flipout=False):
+    fam = _KINDS.get(type(m).__name__)
+    if fam is None or not hasattr(m, "_btx_layer_id") or getattr(m, "_family", None) != fam:
+        return False
+    return fam == "reparam" or flipout
 
 
 def _stub_entries(d):
-    """[eps, mul, add, input, output] from the layer's converted stubs, or None when there are none"""
+    """[eps, mul, add, input, output] (Flipout: the ten entries eps, delta and the eight quint8 stubs) from the layer's converted
+    stubs, or None when there are none"""
     if not getattr(d, "quant_prepare", False) or not hasattr(d, "qint_quant"):
         return None
     stubs = list(d.qint_quant)[2:] + list(d.quint_quant)
@@ -82,28 +89,28 @@ def batch_norm_folding(conv, bn):
     return _twin(conv, bn)
 
 
-def _foldable(conv, bn):
-    return _convertible(conv) and conv._nd == 2 and isinstance(bn, nn.BatchNorm2d) and bn.running_var is not None
+def _foldable(conv, bn, flipout=False):
+    return _convertible(conv, flipout) and conv._nd == 2 and isinstance(bn, nn.BatchNorm2d) and bn.running_var is not None
 
 
-def bnn_to_qbnn(m, fuse_conv_bn=False):
+def bnn_to_qbnn(m, fuse_conv_bn=False, flipout=False):
     mods = m._modules
     if fuse_conv_bn:
         for c, b in (("conv1", "bn1"), ("conv2", "bn2"), ("conv3", "bn3")):
-            if c in mods and b in mods and _foldable(mods[c], mods[b]):
+            if c in mods and b in mods and _foldable(mods[c], mods[b], flipout):
                 setattr(m, c, batch_norm_folding(mods[c], mods[b]))
                 setattr(m, b, nn.Identity())
         ds = mods.get("downsample")
-        if isinstance(ds, nn.Sequential) and len(ds) == 2 and _foldable(ds[0], ds[1]):
+        if isinstance(ds, nn.Sequential) and len(ds) == 2 and _foldable(ds[0], ds[1], flipout):
             ds[0] = batch_norm_folding(ds[0], ds[1])
             ds[1] = nn.Identity()
     for name, child in list(mods.items()):
         if child is None or getattr(child, "_btx_q8", False):
             continue
-        if _convertible(child):
+        if _convertible(child, flipout):
             setattr(m, name, qbnn_linear_layer(child) if child._nd == 0 else qbnn_conv_layer(child))
         elif hasattr(child, "ih") and hasattr(child, "hh") and hasattr(child, "fused_sequence"):
             continue  # a Bayesian LSTM stays whole: its inner Linear layers are part of its recurrence
         elif child._modules:
-            bnn_to_qbnn(child, fuse_conv_bn=fuse_conv_bn)
+            bnn_to_qbnn(child, fuse_conv_bn=fuse_conv_bn, flipout=flipout)
     return

@@ -9,7 +9,7 @@ One `forward` serves both devices through the q8.* functions: CUDA tensors trave
 btx_q8.hip (the residual add rides in the store of the block's last conv: btx_q8_contract_res), CPU tensors as torch.quint8
 through torch's quantized engine.  A QResNet is built from one of this repo's models.resnet ResNets:
 
-    m = resnet18(); dnn_to_bnn(m, {... "type": "Reparameterization" ...}); q = to_qresnet(m)
+    m = resnet18(); dnn_to_bnn(m, {... "type": "Reparameterization" or "Flipout" ...}); q = to_qresnet(m)
 
 A BatchNorm2d that was not folded into its conv (fuse_conv_bn=False) is refused: the reference swaps in torch's quantized
 BatchNorm there, which has no GPU form here."""
@@ -29,7 +29,7 @@ def _out(o):
 
 
 def _is_qconv(m):
-    return type(m).__name__ == "QuantizedConv2dReparameterization"
+    return type(m).__name__ in ("QuantizedConv2dReparameterization", "QuantizedConv2dFlipout")
 
 
 class _QBlock(nn.Module):
@@ -49,7 +49,7 @@ class _QBlock(nn.Module):
             conv = getattr(self, c)
             if not _is_qconv(conv):
                 raise _lib.BtxError("to_qresnet: %s.%s is a %s, not a quantized Conv2d (convert the model with "
-                                    "dnn_to_bnn(type='Reparameterization') first)" % (type(src).__name__, c, type(conv).__name__))
+                                    "dnn_to_bnn(type='Reparameterization' or 'Flipout') first)" % (type(src).__name__, c, type(conv).__name__))
         for c in self._convs[:-1]:
             getattr(self, c).relu = True   # a ReLU follows directly: clamp in the conv's store
 
@@ -122,8 +122,9 @@ class QResNet(nn.Module):
 
 
 def to_qresnet(model, fuse_conv_bn=True):
-    """models.resnet ResNet after dnn_to_bnn(type="Reparameterization") -> QResNet over the same modules (bnn_to_qbnn in place)"""
-    bnn_to_qbnn(model, fuse_conv_bn=fuse_conv_bn)
+    """models.resnet ResNet after dnn_to_bnn(type="Reparameterization" or "Flipout") -> QResNet over the same modules (bnn_to_qbnn
+    in place, Flipout layers included; a Flipout block's residual add is conv + q8.add)"""
+    bnn_to_qbnn(model, fuse_conv_bn=fuse_conv_bn, flipout=True)
     for name, m in model.named_modules():
         if isinstance(m, nn.BatchNorm2d):
             raise _lib.BtxError("to_qresnet: float BatchNorm2d '%s' is left between quantized layers; fold it with fuse_conv_bn=True "
@@ -137,7 +138,9 @@ _PRIOR = {"prior_mu": 0.0, "prior_sigma": 1.0, "posterior_mu_init": 0.0, "poster
 
 def _make(name, num_classes, bnn_prior_parameters):
     m = getattr(_resnet, name)(num_classes=num_classes).eval()
-    dnn_to_bnn(m, dict(_PRIOR, **(bnn_prior_parameters or {}), type="Reparameterization"))
+    # bnn_prior_parameters={"type": "Flipout"} builds the Flipout QResNet; any other (or no) type the Reparameterization one
+    kind = "Flipout" if (bnn_prior_parameters or {}).get("type") == "Flipout" else "Reparameterization"
+    dnn_to_bnn(m, dict(dict(_PRIOR, **(bnn_prior_parameters or {})), type=kind))
     return to_qresnet(m)
 
 

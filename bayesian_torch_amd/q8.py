@@ -186,6 +186,90 @@ def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplie
     return out
 
 
+# ---- Flipout (DESIGN.md §13 "Flipout") -----------------------------------------------------------------------------------
+def mul_multiplier(s_a, s_b, s_o):
+    """m of quantized.mul: f32(f32(s_a) * f32(s_b)) * (f32(1) / f32(s_o)), computed here, once, in f32"""
+    f = np.float32
+    return float(f(f(s_a) * f(s_b)) * (f(1.0) / f(s_o)))
+
+
+def sign_bytes(scale, zero_point):
+    """the bytes of q(+1) and q(-1) at (scale, zero_point): a quantized sign is not exactly +-1"""
+    f = np.float32
+    inv = f(1.0) / f(scale)
+    return tuple(int(np.clip(np.rint(f(v) * inv) + f(zero_point), f(0), f(255))) for v in (1.0, -1.0))
+
+
+_BIAS = {"none": _lib.Q8_BIAS_NONE, "mu": _lib.Q8_BIAS_MU, "sigma_eps": _lib.Q8_BIAS_SIGMA_EPS}
+
+
+def sample_delta(sigma_p, mu_b, sigma_b, n, taps, c, eps_c, s_sigma, s_mu, s_x, e, mean_bias, pert_bias, seed, sample_idx, layer_id,
+                 sample_dev=None, eps_w=None, eps_b=None):
+    """btx_q8_sample_delta: int8 GEMM-major [n][taps][c] sigma_i -> (D [n][Kp] int8, S_d, b_mean_i, b_pert_i [n] int32).
+    e: the ten (scale, zero point) entries; mean_bias / pert_bias: 'none' | 'mu' | 'sigma_eps'."""
+    dev = sigma_p.device
+    kp = weight_row_bytes(taps, c)
+    D = torch.empty((n, kp), dtype=torch.int8, device=dev)
+    S = torch.empty(n, dtype=torch.int32, device=dev)
+    bm = torch.empty(n, dtype=torch.int32, device=dev)
+    bp = torch.empty(n, dtype=torch.int32, device=dev)
+    f = np.float32
+    d = _lib.Q8Delta(float(f(1.0) / f(e[0][0])), mul_multiplier(s_sigma, e[0][0], e[1][0]), _BIAS[mean_bias], _BIAS[pert_bias],
+                     float(s_x) * float(s_mu), float(e[6][0]) * float(e[1][0]))
+    r = _lib.Rng(int(seed), int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(_lib.lib().btx_q8_sample_delta(sigma_p.data_ptr(), ptr(mu_b), ptr(sigma_b), int(n), int(taps), int(c), int(eps_c),
+                                              ctypes.byref(d), ctypes.byref(r), ptr(eps_w), ptr(eps_b), D.data_ptr(), S.data_ptr(),
+                                              bm.data_ptr(), bp.data_ptr(), _stream(dev)))
+    return D, S, bm, bp
+
+
+def make_flipout(s_x, z_x, s_mu, e):
+    """BtxQ8Flipout from the input's (scale, zero point), the mean weights' scale and the ten entries"""
+    f = np.float32
+    ip, ineg = sign_bytes(*e[4])
+    op, oneg = sign_bytes(*e[5])
+    return _lib.Q8Flipout(int(z_x), int(e[6][1]), int(e[3][1]), int(e[7][1]), int(e[8][1]), ip - e[4][1], ineg - e[4][1], op - e[5][1],
+                          oneg - e[5][1], mul_multiplier(s_x, e[4][0], e[6][0]), float(f(f(s_x) * f(s_mu)) / f(e[3][0])),
+                          float(f(f(e[6][0]) * f(e[1][0])) / f(e[7][0])), mul_multiplier(e[7][0], e[5][0], e[8][0]), float(f(e[9][0])))
+
+
+def contract_flipout(xq, W_mu, S_mu, bm_i, D, S_d, bp_i, n, kernel, stride, padding, dilation, flip, add, seed, sample_idx, layer_id,
+                     sign_c, sample_dev=None, sign_in=None, sign_out=None, out_f32=False):
+    """btx_q8_contract_flipout.  xq: uint8 [B, K] or channels-last [B, C, H, W]; sign_in / sign_out: int8 +1 / -1 in the physical
+    (channels-last) order of x / the output, or None -> BTX-RNG v1."""
+    g = _lib.Geom()
+    if xq.dim() == 2:
+        g.NB, g.C, g.H, g.W = xq.shape[0], xq.shape[1], 1, 1
+    else:
+        g.NB, g.C, g.H, g.W = xq.shape
+    g.D = g.KD = 1
+    g.N = int(n)
+    g.KH, g.KW = kernel
+    g.sd, g.sh, g.sw = 1, stride[0], stride[1]
+    g.pd, g.ph, g.pw = 0, padding[0], padding[1]
+    g.dd, g.dh, g.dw = 1, dilation[0], dilation[1]
+    g.groups = 1
+    oh = (g.H + 2 * g.ph - g.dh * (g.KH - 1) - 1) // g.sh + 1
+    ow = (g.W + 2 * g.pw - g.dw * (g.KW - 1) - 1) // g.sw + 1
+    if oh <= 0 or ow <= 0:
+        raise _lib.BtxError("quantized conv: the kernel does not fit the input")
+    dt = torch.float32 if out_f32 else torch.uint8
+    if xq.dim() == 2:
+        out = torch.empty((g.NB, g.N), dtype=dt, device=xq.device)
+    else:
+        out = torch.empty((g.NB, g.N, oh, ow), dtype=dt, device=xq.device, memory_format=torch.channels_last)
+    r = _lib.Rng(int(seed), int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(_lib.lib().btx_q8_contract_flipout(ctypes.byref(g), xq.data_ptr(), W_mu.data_ptr(), S_mu.data_ptr(), bm_i.data_ptr(),
+                                                  D.data_ptr(), S_d.data_ptr(), bp_i.data_ptr(), ctypes.byref(flip), ctypes.byref(add),
+                                                  ctypes.byref(r), int(sign_c), ptr(sign_in), ptr(sign_out), 1 if out_f32 else 0,
+                                                  out.data_ptr(), _stream(xq.device)))
+    return out
+
+
 # ---- between the layers: one `forward` for both devices -------------------------------------------------------------------
 def _is_quint8(x):
     return isinstance(x, torch.Tensor) and x.dtype == torch.quint8

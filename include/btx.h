@@ -614,6 +614,50 @@ int btx_q8_maxpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, in
 int btx_q8_avgpool2d_cl(const uint8_t* x, uint8_t* out, int NB, int H, int W, int C, int k, int stride, int pad, int ceil_mode,
                         int zero_point, void* stream);
 
+/* K10, Flipout (ABI 9, additive; DESIGN.md §13 "Flipout"): the INT8 forward of LinearFlipout / Conv2dFlipout, groups = 1 (reference
+ * layers/flipout_layers/quantized_linear_flipout.py:138-261, quantized_conv_flipout.py:398-514: two quantized convs, three
+ * quantized.mul and one quantized.add, entries e0 .. e9 of quant_dict).  One pre-pass launch and ONE contraction launch.
+ * quantized.mul(a, b -> (s_o, z_o)) = clamp(rint(f32((a - z_a) * (b - z_b)) * m) + z_o, lo, hi) with the int32 product exact and
+ *   m = f32(f32(s_a) * f32(s_b)) * (f32(1) / f32(s_o)), computed by the caller once.
+ * BtxQ8Delta (HOST struct): inv_s_eps = 1 / s_e0; mult = m of (s_sigma, s_e0 -> s_e1); mean_bias / pert_bias = BTX_Q8_BIAS_*: which
+ *   f32 vector becomes the int32 bias of the mean / the perturbed GEMM (none, mu_b, sigma_b * eps_b); div_mean = (double)s_x *
+ *   s_mu, div_pert = (double)s_e6 * s_e1.
+ * btx_q8_sample_delta: sigma_i int8 GEMM-major [N][taps][C]; eps as in btx_q8_sample_weights (stream EPS_W in the float layer's
+ *   index space, eps_C, or explicit eps_w).  eps_i = q(eps, s_e0, 0, -128, 127); D[n][k] = mul(sigma_i, eps_i) in [-128, 127], int8
+ *   [N][Kp] in the weight image layout, padding zero; S_d[n] = its row sum; b_mean_i / b_pert_i[n] = (int32) rint((double)b /
+ *   div), b = mu_b[n] or f32(sigma_b[n] * eps_b) (eps_b: stream EPS_B at index n, or eps_b[n]) or 0.
+ * BtxQ8Flipout (HOST struct): z_x, z_xp (e6), z_mean (e3), z_pert (e7), z_p2 (e8); sin_pos / sin_neg = the bytes q(+1, e4), q(-1, e4)
+ *   minus z_e4, sout_* alike with e5; mult_xp = m of (s_x, s_e4 -> s_e6), mult_mean = f32(f32(s_x) * f32(s_mu)) / f32(s_e3),
+ *   mult_pert = f32(f32(s_e6) * f32(s_e1)) / f32(s_e7), mult_p2 = m of (s_e7, s_e5 -> s_e8); out_scale = s_e9 (f32 output).
+ * btx_q8_contract_flipout: g as in btx_q8_contract.  W_mu / S_mu: the mean image and its row sums (btx_q8_sample_weights with a zero
+ *   sigma_i).  x' = mul(x, sign byte) is formed on the way into LDS; o1 = requantize(sum (x - z_x) W_mu + b_mean_i), p =
+ *   requantize(sum (x' - z_xp) D + b_pert_i), padded taps contribute 0 to both; p2 = mul(p, sign byte); out = add(o1, p2) with
+ *   add_host (a = (s_e3, z_mean), b = (s_e8, z_p2), its relu flag the ReLU clamp).  out: uint8 channels-last [NB][OH][OW][N], or
+ *   with out_f32 the dequantized f32 (o - z_e9) * out_scale.  Signs: BTX-RNG v1 stream SIGN_IN at index pixel * sign_C + c (pixel
+ *   = (img * H + ih) * W + iw; sign_C = the float layer's row length, >= C and a multiple of 8) and SIGN_OUT at m * N + n; sign_in / sign_out (int8
+ *   +1 / -1, channels-last like x / out), when non-NULL, override the hash.  rng may be NULL when both are given;
+ *   rng->sample_idx_dev is honoured.  Errors as above; capturable. */
+#define BTX_Q8_BIAS_NONE      0
+#define BTX_Q8_BIAS_MU        1
+#define BTX_Q8_BIAS_SIGMA_EPS 2
+typedef struct BtxQ8Delta {
+  float inv_s_eps, mult;
+  int mean_bias, pert_bias;
+  double div_mean, div_pert;
+} BtxQ8Delta;
+typedef struct BtxQ8Flipout {
+  int z_x, z_xp, z_mean, z_pert, z_p2;
+  int sin_pos, sin_neg, sout_pos, sout_neg;
+  float mult_xp, mult_mean, mult_pert, mult_p2, out_scale;
+} BtxQ8Flipout;
+int btx_q8_sample_delta(const int8_t* sigma_i, const float* mu_b, const float* sigma_b, int N, int taps, int C, int eps_C,
+                        const BtxQ8Delta* delta_host, const BtxRng* rng, const float* eps_w, const float* eps_b, int8_t* D, int32_t* S_d,
+                        int32_t* b_mean_i, int32_t* b_pert_i, void* stream);
+int btx_q8_contract_flipout(const BtxGeom* g, const uint8_t* x, const int8_t* W_mu, const int32_t* S_mu, const int32_t* b_mean_i,
+                            const int8_t* D, const int32_t* S_d, const int32_t* b_pert_i, const BtxQ8Flipout* flip_host,
+                            const BtxQ8Add* add_host, const BtxRng* rng, int sign_C, const int8_t* sign_in, const int8_t* sign_out,
+                            int out_f32, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
