@@ -103,6 +103,19 @@ class Q8Flipout(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("mult_xp", "mult_mean", "mult_pert", "mult_p2", "out_scale")]
 
 
+class OptimItem(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("state0", ctypes.c_void_p), ("state1", ctypes.c_void_p),
+                ("n", ctypes.c_int64)]
+
+
+class OptimHyper(ctypes.Structure):  # the DEVICE block of BTX-OPT v1: 16 words, filled on the host and copied
+    _fields_ = [(n, ctypes.c_float) for n in ("neg_lr", "wd", "decay_mul", "one_m_b1", "b2", "one_m_b2", "eps", "neg_step_size",
+                                              "bc2s", "momentum", "one_m_damp")] + \
+               [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+OPT_MAXIMIZE, OPT_NESTEROV, OPT_DECOUPLED, OPT_FIRST_STEP, OPT_COUPLED_WD = 1, 2, 4, 8, 16
+OPTIM_CHUNK, OPTIM_MAX_ITEMS = 4096, 65536
 Q8_BIAS_NONE, Q8_BIAS_MU, Q8_BIAS_SIGMA_EPS = 0, 1, 2
 
 EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_gauss", "btx_kl_model_workspace_bytes",
@@ -116,7 +129,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_calib_workspace_bytes", "btx_avu_fwd", "btx_avu_bwd", "btx_eau_fwd", "btx_eau_bwd",
            "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract",
            "btx_q8_add", "btx_q8_contract_res", "btx_q8_maxpool2d_cl", "btx_q8_avgpool2d_cl",
-           "btx_q8_sample_delta", "btx_q8_contract_flipout")
+           "btx_q8_sample_delta", "btx_q8_contract_flipout",
+           "btx_optim_sgd", "btx_optim_adam", "btx_optim_grad_norm_workspace_bytes", "btx_optim_grad_norm")
 
 
 def lib_path():
@@ -261,6 +275,14 @@ def lib():
     L.btx_q8_contract_flipout.restype = i32
     L.btx_q8_contract_flipout.argtypes = [ctypes.POINTER(Geom), vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Q8Flipout),
                                           ctypes.POINTER(Q8Add), ctypes.POINTER(Rng), i32, vp, vp, i32, vp, vp]
+    L.btx_optim_sgd.restype = i32
+    L.btx_optim_sgd.argtypes = [ctypes.POINTER(OptimItem), i32, vp, i32, vp, vp]
+    L.btx_optim_adam.restype = i32
+    L.btx_optim_adam.argtypes = [ctypes.POINTER(OptimItem), i32, vp, vp, vp]
+    L.btx_optim_grad_norm_workspace_bytes.restype = sz
+    L.btx_optim_grad_norm_workspace_bytes.argtypes = [i32, ctypes.c_int64]
+    L.btx_optim_grad_norm.restype = i32
+    L.btx_optim_grad_norm.argtypes = [ctypes.POINTER(OptimItem), i32, f32, vp, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

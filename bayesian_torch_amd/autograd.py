@@ -501,15 +501,30 @@ class GraphedTrainStep:
         step = GraphedTrainStep(model, x, target)            # grads live in p.grad (static tensors, rewritten by every replay)
         for it in range(n): loss = step.run(it); optimizer.step()
 
+    With `optimizer=` one of bayesian_torch_amd.optim.{SGD, Adam, AdamW}, the update is INSIDE the graph as well: the gradient norm
+    (max_grad_norm) and the update launches are captured after loss.backward(); run() advances the optimizer's step counts on the
+    host, rewrites its device blocks from the groups' current lr, replays, and bumps the parameters' versions:
+
+        step = GraphedTrainStep(model, x, target, optimizer=opt)
+        for it in range(n): loss = step.run(it); scheduler.step()
+
+    Constructing the step changes no parameter and no optimizer state (the warm-up runs forward + backward only; the update kernels
+    are warmed on scratch tensors).  Load an optimizer state_dict BEFORE constructing the step: the graph holds the state's pointers.
+
     In-place parameter updates between replays are seen (the kernels read mu / rho where they live); x / target are read from the
     tensors given here (copy new batches INTO them).  Layers on padded layouts that need their input gradient (sign tensors keyed
     on the host) cannot be captured and raise.  Drop every reference to the loss / outputs of earlier EAGER steps of this model
     before constructing one (torch: a live autograd graph pins its AccumulateGrad nodes to the stream it ran on)."""
 
-    def __init__(self, model, x, target, loss_fn=None, warmup=2):
+    def __init__(self, model, x, target, loss_fn=None, warmup=2, optimizer=None):
         from .models.dnn_to_bnn import get_kl_loss
+        from . import optim as _optim
         if not x.is_cuda:
             raise ValueError("GraphedTrainStep needs CUDA (ROCm) tensors")
+        if optimizer is not None and not isinstance(optimizer, _optim._BtxOptimizer):
+            raise TypeError("GraphedTrainStep(optimizer=) takes bayesian_torch_amd.optim.SGD / Adam / AdamW (got %s): a torch.optim "
+                            "step cannot be captured here; call it after run() instead" % type(optimizer).__name__)
+        self.optimizer, self._plan = optimizer, None
         self.model, self.x, self.target = model, x, target
         bs = x.shape[0]
         self.loss_fn = loss_fn or (lambda out, tgt: torch.nn.functional.cross_entropy(out.float(), tgt) + get_kl_loss(model) / bs)
@@ -526,13 +541,22 @@ class GraphedTrainStep:
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup) + 1):
                 self._step()
+            if optimizer is not None:
+                optimizer._warm(dev)   # every update kernel once, on scratch tensors: the model is not touched
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
+        if optimizer is not None:
+            with torch.no_grad():
+                optimizer._plan()      # state, staging buffers, device blocks and the norm workspace exist before the capture
         for p_ in model.parameters():
             p_.grad = None
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.loss = self._step()
+            if optimizer is not None:
+                with torch.no_grad():
+                    self._plan = optimizer._plan()   # the item tables of THIS capture's gradient tensors
+                    optimizer._launch(self._plan)
         # the graph writes its gradients into these pool tensors on every replay; `optimizer.zero_grad()` (set_to_none=True by
         # default) between replays detaches them from the parameters, so run() attaches them again
         self._grads = [(p_, p_.grad) for p_ in model.parameters() if p_.grad is not None]
@@ -550,10 +574,15 @@ class GraphedTrainStep:
 
     def run(self, sample_idx):
         self.sample_dev.fill_(int(sample_idx) & 0x7FFFFFFF)
+        if self._plan is not None:
+            with torch.no_grad():
+                self.optimizer._advance(self._plan)  # step counts, and lr & co. as the groups hold them NOW, into the device blocks
         self.graph.replay()
         for p_, g_ in self._grads:
             if p_.grad is not g_:
                 p_.grad = g_
+        if self._plan is not None:
+            self.optimizer._finish(self._plan)       # the replay wrote the parameters through raw pointers: bump their versions
         return self.loss
 
     def close(self):

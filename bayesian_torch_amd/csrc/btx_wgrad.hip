@@ -643,6 +643,17 @@ bool wgrad_taps3_geom(const WgradParams& p, int act_dtype) {
          (p.C % 64) == 0 && (p.N % 64) == 0;
 }
 
+// zero of the (at most two) bias-sum vectors the atomics accumulate into.  A kernel, not hipMemsetAsync: captured into a hipGraph, the
+// small memset nodes (40 bytes for a 10-class head) left the tail of the vector unset on replays after the first, and the sums then
+// started from whatever the graph's pool held there (inf / NaN bias gradients in GraphedTrainStep replays)
+__global__ __launch_bounds__(256) void wgrad_zero_kernel(float* __restrict__ a, float* __restrict__ b, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    a[i] = 0.f;
+    if (b) b[i] = 0.f;
+  }
+}
+
 int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float* dw_mu, float* dw_delta, float* db_mu, float* db_delta,
                const BtxRng* rng, const BtxNoise* noise, int act_dtype, uint32_t flags, void* ws, size_t ws_bytes, const float* rho_w,
                float* drho, void* stream) {
@@ -695,11 +706,9 @@ int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float*
     if (e != hipSuccess) return (int)e;
     if (kind == BTX_KIND_FLIPOUT) { e = hipMemsetAsync(dw_delta, 0, wbytes, st); if (e != hipSuccess) return (int)e; }
   }
-  if (db_mu) {
-    e = hipMemsetAsync(db_mu, 0, (size_t)g->N * sizeof(float), st);
-    if (e != hipSuccess) return (int)e;
-    if (kind == BTX_KIND_FLIPOUT) { e = hipMemsetAsync(db_delta, 0, (size_t)g->N * sizeof(float), st); if (e != hipSuccess) return (int)e; }
-  }
+  if (db_mu)
+    hipLaunchKernelGGL(wgrad_zero_kernel, dim3((g->N + 255) / 256), dim3(256), 0, st, db_mu,
+                       kind == BTX_KIND_FLIPOUT ? db_delta : (float*)nullptr, g->N);
   const int nwg = (int)(base * chunks);
   if (taps3) {
 #define BTX_LAUNCH_T3(KIND)                                                                                       \

@@ -658,6 +658,53 @@ int btx_q8_contract_flipout(const BtxGeom* g, const uint8_t* x, const int8_t* W_
                             const BtxQ8Add* add_host, const BtxRng* rng, int sign_C, const int8_t* sign_in, const int8_t* sign_out,
                             int out_f32, void* out, void* stream);
 
+/* K11 (ABI 9, additive; DESIGN.md §14 "BTX-OPT v1"): the parameter update of SGD / Adam / AdamW as ONE pass over every tensor of a
+ * param group (torch/optim/sgd.py, adam.py: _single_tensor_sgd / _single_tensor_adam), and the global gradient norm with its clip
+ * coefficient.  f32 only.  The unit is built with -ffp-contract=off: every operation of BTX-OPT v1 is rounded once.
+ * BtxOptimItem (HOST array): p, g and the state tensors of one parameter in the SAME storage order, n elements each, walked flat.
+ *   SGD: state0 = momentum_buffer (NULL when momentum == 0), state1 unused.  Adam: state0 = exp_avg, state1 = exp_avg_sq.
+ *   Items with n == 0 are skipped.  The library folds the items into by-value kernel-argument tables of at most 48 per launch; a
+ *   workgroup owns one chunk of BTX_OPTIM_CHUNK elements of one item.  16-byte accesses when all pointers of an item are 16-byte
+ *   aligned, scalar ones otherwise.
+ * BtxOptimHyper (DEVICE block, 16 words, 16-byte aligned): read by the kernel when it RUNS, never written by it; the host rewrites
+ *   it before each launch or replay, so a captured launch follows a changed lr and the advancing step count.  All floats are the
+ *   f32 roundings of values the host computes in double:
+ *   neg_lr = -lr (SGD); wd = weight_decay (coupled); decay_mul = 1 - lr * wd (BTX_OPT_DECOUPLED); one_m_b1 = 1 - beta1; b2 = beta2;
+ *   one_m_b2 = 1 - beta2; eps; neg_step_size = -lr / (1 - beta1^t); bc2s = sqrt(1 - beta2^t); momentum; one_m_damp = 1 - dampening.
+ * coef: optional DEVICE word (btx_optim_grad_norm's out[1]): g is multiplied by it first (after the negation of BTX_OPT_MAXIMIZE).
+ * btx_optim_grad_norm: out[0] = total_norm = f32(sqrt(sum g^2)) over all items, out[1] = coef = min(1, max_norm / (total_norm +
+ *   1e-6f)) in f32.  Per-chunk f32 lane sums, f64 partials in ws (btx_optim_grad_norm_workspace_bytes(n_items, total elements)), one
+ *   final block folds them in a fixed order: no atomics, two runs give the same bits.  state pointers of the items are ignored.
+ * Every launch is capturable (no allocation, no sync, no host read).  Errors, all before anything is launched: BTX_E_NULL (items,
+ *   hyper, out, ws, p, g, a required state pointer), BTX_E_SHAPE (n_items < 0, n < 0, max_norm not > 0), BTX_E_UNSUPPORTED (more than
+ *   BTX_OPTIM_MAX_ITEMS items), BTX_E_ALIGN (a tensor pointer not 4-byte, hyper not 16-byte, ws not 8-byte aligned),
+ *   BTX_E_WORKSPACE.  n_items == 0 (or only empty items) launches nothing and returns 0 (grad_norm still writes out). */
+#define BTX_OPTIM_CHUNK     4096
+#define BTX_OPTIM_MAX_ITEMS 65536
+#define BTX_OPT_MAXIMIZE   1u
+#define BTX_OPT_NESTEROV   2u
+#define BTX_OPT_DECOUPLED  4u   /* AdamW: p *= decay_mul */
+#define BTX_OPT_FIRST_STEP 8u   /* SGD: buf = g */
+#define BTX_OPT_COUPLED_WD 16u  /* g += wd * p */
+typedef struct BtxOptimItem {
+  float* p;
+  const float* g;
+  float* state0;
+  float* state1;
+  int64_t n;
+} BtxOptimItem;
+typedef struct BtxOptimHyper {
+  float neg_lr, wd, decay_mul, one_m_b1, b2, one_m_b2, eps, neg_step_size, bc2s, momentum, one_m_damp;
+  uint32_t flags;
+  uint32_t reserved[4];
+} BtxOptimHyper;
+int btx_optim_sgd(const BtxOptimItem* items, int n_items, const BtxOptimHyper* hyper_dev, int has_momentum, const float* coef_dev,
+                  void* stream);
+int btx_optim_adam(const BtxOptimItem* items, int n_items, const BtxOptimHyper* hyper_dev, const float* coef_dev, void* stream);
+size_t btx_optim_grad_norm_workspace_bytes(int n_items, int64_t total_elements);
+int btx_optim_grad_norm(const BtxOptimItem* items, int n_items, float max_norm, float* out_dev, void* ws, size_t ws_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
