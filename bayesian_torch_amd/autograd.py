@@ -359,6 +359,9 @@ class BatchNormTrainFn(torch.autograd.Function):
         C = x.shape[1]
         M = x.numel() // C
         dev = x.device
+        # the kernels move 8 channels per 16-byte access: a tensor off that grid (a dense view into a flat buffer) enters as one
+        # aligned copy with the same strides — the same launches, the same bits
+        x, residual = BF.on_grid(x), BF.on_grid(residual)
         y = torch.empty_like(x)  # preserves the channels-last strides
         save_mean = torch.empty(C, dtype=torch.float32, device=dev)
         save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
@@ -401,6 +404,7 @@ class BatchNormTrainFn(torch.autograd.Function):
             dy = dy.contiguous(memory_format=torch.channels_last_3d)
         else:
             dy = dy.contiguous()
+        dy = BF.on_grid(dy)
         dx = torch.empty_like(x)
         pd = w.dtype if w is not None else torch.float32  # the kernel writes the two [C] gradients in the parameters' dtype
         dgamma = torch.empty(C, dtype=pd, device=dev)

@@ -19,8 +19,11 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
   if (!g || !x || !mu_w || !rho_w || !out || !rng) return BTX_E_NULL;
   const int lanes = ln ? ln->n : 1;
   if ((mu_b == nullptr) != (rho_b == nullptr)) return BTX_E_NULL;
+  // every pointer some fast family reads or writes in 16-byte granules (the residual: btx_epilogue.h stage 2).  The bias, the
+  // scale / shift vectors, eps_b and the explicit sign arrays are read element by element in every family: no requirement.
   const uintptr_t al = (uintptr_t)x | (uintptr_t)mu_w | (uintptr_t)rho_w | (uintptr_t)out |
-                       (uintptr_t)(noise && noise->eps_w ? noise->eps_w : nullptr);
+                       (uintptr_t)(noise && noise->eps_w ? noise->eps_w : nullptr) |
+                       (uintptr_t)(ep && ep->residual ? ep->residual : nullptr);
   FwdSel sel;
   int rc = select_fwd(kind, g, act_dtype, prec, flags, (al & 15) != 0, noise, ep, &sel);
   if (rc) return rc;

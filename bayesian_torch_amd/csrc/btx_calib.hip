@@ -301,6 +301,7 @@ int btx_avu_fwd(const void* logits, const int64_t* labels, int B, int C, int act
   if (B <= 0 || C <= 0 || (area != 0 && area != 1)) return BTX_E_SHAPE;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
+  if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
   float* rows = (float*)ws + CALIB_HDR_FLOATS;
   const dim3 grid((B + 3) / 4);
@@ -320,6 +321,7 @@ int btx_avu_bwd(const void* logits, int B, int C, int act_dtype, const float* g_
   if (B <= 0 || C <= 0) return BTX_E_SHAPE;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
+  if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((B + 3) / 4);
   if (act_dtype == BTX_ACT_F32)
@@ -336,6 +338,7 @@ int btx_eau_fwd(const float* error, const float* other, int B, int conf_form, fl
   if (!error || !other || !out || !ws) return BTX_E_NULL;
   if (B <= 0 || (conf_form != 0 && conf_form != 1)) return BTX_E_SHAPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
+  if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
   if (conf_form)
     hipLaunchKernelGGL(calib_fold_kernel<2>, dim3(1), dim3(CALIB_FOLD_THREADS), 0, st, error, other, B, 1, error_th, error_th_dev,
@@ -350,6 +353,7 @@ int btx_eau_bwd(const float* error, const float* other, int B, int conf_form, co
   if (!error || !other || !g_loss || !ws || (!derror && !dother)) return BTX_E_NULL;
   if (B <= 0 || (conf_form != 0 && conf_form != 1)) return BTX_E_SHAPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
+  if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid(min((B + 255) / 256, 1024));
   if (conf_form)

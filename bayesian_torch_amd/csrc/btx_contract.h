@@ -751,6 +751,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
     __syncthreads();
   }
   const int colbase = ntile * BN + wv_n * 32;  // within the group
+  // GEN launches also serve calls whose `out` / residual are off the 16-byte grid (btx_api.hip: `unaligned`): a 4-channel run
+  // is then not aligned to its own width and goes element by element
+  bool io_al = true;
+  if constexpr (GEN) io_al = ((((uintptr_t)p.out) | ((uintptr_t)p.ep_res)) & (4 * sizeof(ACT) - 1)) == 0;
   if (colbase < p.Ng) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
@@ -793,7 +797,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
           }
           v[rr] = val;
         }
-        const bool vec = (c0 + 3 < p.Ng) && (((orow + c0) & 3) == 0);
+        const bool vec = (c0 + 3 < p.Ng) && (((orow + c0) & 3) == 0) && io_al;
         if (to_partial) {
           float* dst = p.partial + (long long)split * p.M * p.N + orow + c0;
           if (vec) {
@@ -835,6 +839,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   out = (ACT*)((unsigned char*)out + (long long)blockIdx.y * lane_out);
   if (res) res = (const ACT*)((const unsigned char*)res + (long long)blockIdx.y * lane_res);
   const long long stride = (long long)gridDim.x * blockDim.x * 4;
+  // (the gather kernel's split-K launches may come with `out` off the 16-byte grid: element stores then)
+  const bool out_vec = (((uintptr_t)out) & (4 * sizeof(ACT) - 1)) == 0;
   for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < total; i += stride) {
     const int nv = (int)((total - i) < 4 ? (total - i) : 4);
     float a[4] = {0.f, 0.f, 0.f, 0.f};
@@ -855,7 +861,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
       if (relu == 2) v = v < 6.f ? v : 6.f;  // ReLU6
       a[r] = v;
     }
-    if (nv == 4) {
+    if (nv == 4 && out_vec) {
       if constexpr (sizeof(ACT) == 4) *(f32x4*)(out + i) = (f32x4){a[0], a[1], a[2], a[3]};
       else *(bf16x4*)(out + i) = __builtin_convertvector((f32x4){a[0], a[1], a[2], a[3]}, bf16x4);
     } else {

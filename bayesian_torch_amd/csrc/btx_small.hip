@@ -336,6 +336,7 @@ int btx_rowfuse_pack(const void* x, int in_dtype, const int64_t* strides_ncHW, i
   if (!x || !out || !strides_ncHW) return BTX_E_NULL;
   if (NB <= 0 || C <= 0 || H <= 0 || W <= 0 || ph < 0 || pw < 0 || Hp < H + ph || Wp < W + pw) return BTX_E_SHAPE;
   if ((cp != 4 && cp != 8) || C > cp) return BTX_E_UNSUPPORTED;
+  if (((uintptr_t)out) & 15) return BTX_E_ALIGN;  // one store per padded pixel (8 / 16 / 32 bytes); x is read element by element
   hipStream_t st = (hipStream_t)stream;
   const bool ib = in_dtype == BTX_ACT_BF16, ob = out_dtype == BTX_ACT_BF16;
   if ((!ib && in_dtype != BTX_ACT_F32) || (!ob && out_dtype != BTX_ACT_F32)) return BTX_E_DTYPE;

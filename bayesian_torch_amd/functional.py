@@ -144,21 +144,34 @@ def gemm_major_param(shape, op):
     return torch.empty(shape)
 
 
+def on_grid(t):
+    """`t` itself when its first element lies on the 16-byte grid the vector kernels address (every tensor that comes straight from
+    torch's allocator does), else ONE copy in fresh storage with the same shape and strides — what the entry points that refuse an
+    off-grid pointer with BTX_E_ALIGN are handed instead (DESIGN.md "Alignment contract").  A dense view into a flat buffer
+    (`as_strided`, a dlpack / frombuffer import, parameters carved from one storage at 4-byte offsets) is the tensor this is for.
+    The copy is an ordinary stream-ordered launch: inside a captured region it is a node of the graph like any other."""
+    if t is None or t.data_ptr() % 16 == 0:
+        return t
+    return torch.empty_like(t, memory_format=torch.preserve_format).copy_(t)
+
+
 def gemm_major_view(w, op):
     """The [N][tap][Cg]-ordered tensor of a parameter: a zero-copy view when the parameter is stored GEMM-major
-    (the default, see gemm_major_param), else a packed copy made now."""
+    (the default, see gemm_major_param) on the 16-byte grid, else a packed copy made now.  (A parameter off the grid — a view of
+    a flat buffer at some 4-byte offset — is copied on every call: never stale, and the contraction, the pre-sampling and the
+    data gradient's weight pass keep their granule kernels, hence their bits.)"""
     nd = op.nd
     w = w.detach()
     if w.dtype != torch.float32:
         raise _lib.BtxError("variational parameters must be float32 (got %s)" % w.dtype)
     if nd == 0:
-        return w if w.is_contiguous() else w.contiguous()
+        return on_grid(w) if w.is_contiguous() else w.contiguous()
     if not op.transposed:
         v = w.permute((0,) + tuple(range(2, 2 + nd)) + (1,))
-        return v if v.is_contiguous() else v.contiguous()
+        return on_grid(v) if v.is_contiguous() else v.contiguous()
     if op.groups == 1:
         v = w.permute((1,) + tuple(range(2, 2 + nd)) + (0,))
-        return v if v.is_contiguous() else v.contiguous()
+        return on_grid(v) if v.is_contiguous() else v.contiguous()
     return pack_gemm_major(w, op)
 
 
@@ -477,6 +490,7 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
             if op.nd == 0:
                 res = res.reshape(-1, op.out_channels)
             rp, _, _, _ = _to_channels_last(res, OpDesc(op.nd, op.out_channels, op.out_channels))
+            rp = on_grid(rp)  # the store side adds it in 16-byte granules: an off-grid residual would cost the launch its kernel
             if rp.dtype != out.dtype or rp.numel() != out.numel():
                 raise ValueError("epilogue residual must match the output shape and dtype")
             keep.append(rp)
@@ -1037,7 +1051,7 @@ def maxpool2d_hip(x, kernel, stride, padding):
     """torch.nn.functional.max_pool2d for channels-last CUDA tensors through btx_maxpool2d_cl (C % 8 == 0)"""
     L = _lib.lib()
     n, c, h, w = x.shape
-    xp = x.contiguous(memory_format=torch.channels_last)
+    xp = on_grid(x.contiguous(memory_format=torch.channels_last))
     ho, wo = (h + 2 * padding - kernel) // stride + 1, (w + 2 * padding - kernel) // stride + 1
     out = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     _lib.check(L.btx_maxpool2d_cl(xp.data_ptr(), out.data_ptr(), _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32,
@@ -1050,6 +1064,7 @@ def maxpool2d_train_hip(x, kernel, stride, padding):
     its maximum (uint8 [N][Ho][Wo][C]) for maxpool2d_bwd_hip"""
     L = _lib.lib()
     n, c, h, w = x.shape
+    x = on_grid(x)
     ho, wo = (h + 2 * padding - kernel) // stride + 1, (w + 2 * padding - kernel) // stride + 1
     out = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     idx = torch.empty(n * ho * wo * c, dtype=torch.uint8, device=x.device)
@@ -1062,6 +1077,7 @@ def maxpool2d_bwd_hip(dy, idx, x_shape, kernel, stride, padding):
     """btx_maxpool2d_cl_bwd: the gradient of maxpool2d_train_hip's input (channels-last), dy channels-last"""
     L = _lib.lib()
     n, c, h, w = x_shape
+    dy = on_grid(dy)
     dx = torch.empty((n, c, h, w), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
     _lib.check(L.btx_maxpool2d_cl_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), _lib.ACT_BF16 if dy.dtype == torch.bfloat16 else _lib.ACT_F32,
                                       n, h, w, c, kernel, stride, padding, torch.cuda.current_stream(dy.device).cuda_stream))
@@ -1072,7 +1088,7 @@ def avgpool_global_hip(x):
     """adaptive_avg_pool2d(x, 1).flatten(1) for channels-last CUDA tensors through btx_avgpool_global_cl (C % 8 == 0)"""
     L = _lib.lib()
     n, c, h, w = x.shape
-    xp = x.contiguous(memory_format=torch.channels_last)
+    xp = on_grid(x.contiguous(memory_format=torch.channels_last))
     out = torch.empty((n, c), dtype=x.dtype, device=x.device)
     _lib.check(L.btx_avgpool_global_cl(xp.data_ptr(), out.data_ptr(), _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32,
                                        n, h * w, c, torch.cuda.current_stream(x.device).cuda_stream))

@@ -46,7 +46,7 @@ extern "C" {
 #define BTX_E_UNSUPPORTED (-3)   /* valid request this build does not implement */
 #define BTX_E_WORKSPACE   (-4)   /* workspace too small (see btx_*_workspace_bytes) */
 #define BTX_E_DTYPE       (-5)   /* unknown dtype / precision code */
-#define BTX_E_ALIGN       (-6)   /* pointer not 16-byte aligned */
+#define BTX_E_ALIGN       (-6)   /* pointer not 16-byte aligned (per pointer: DESIGN.md "Alignment contract") */
 
 /* kind */
 #define BTX_KIND_REPARAM 0
@@ -207,7 +207,9 @@ int btx_contract_fwd(int kind, const BtxGeom* g,
  *   relu = 0: none;  1: y = max(y, 0) (ReLU);  2: y = min(max(y, 0), 6) (ReLU6, MobileNetV2's ConvBNReLU).
  * The activation acts on the f32 value, in front of the one rounding to the output dtype; both bounds of ReLU6 are exact in
  * bf16, so relu = 2 gives exactly clamp(output of relu = 0, 0, 6).  relu = 2 with pool = 1 returns BTX_E_UNSUPPORTED.
- * scale/shift: f32 [N] (NULL => 1 / 0); residual: same layout and dtype as `out` (NULL => none).
+ * scale/shift: f32 [N] (NULL => 1 / 0), read element by element; residual: same layout and dtype as `out` (NULL => none) — like
+ * x, mu_w, rho_w, out and eps_w it is moved in 16-byte granules by the fast kernels: with any of them off the 16-byte grid the
+ * launch takes the element-wise gather kernel (BTX_E_UNSUPPORTED where none exists: BTX_FLAG_ROWFUSE, BTX_FLAG_OUT_*).
  * pool = 1: the ResNet stem's nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (resnet_large.py:118,145) is applied to y
  * inside the same launch and `out` is the POOLED tensor [NB][Hq][Wq][N] (btx_contract_pool_shape); the conv output never
  * reaches HBM.  Row-fused bf16 stems only (BTX_FLAG_ROWFUSE, generated noise, no residual): everything else returns
@@ -375,8 +377,9 @@ int btx_rho_grad(const float* dw, const float* rho, float* drho, size_t n, const
  * activations with the conv padding materialised and the channels zero-padded to cp (4 or 8), in the MFMA dtype.
  * btx_rowfuse_pack writes that tensor in ONE pass from the caller's logical [N,C,H,W] activations of any layout:
  * strides_ncHW = element strides of (n, c, h, w), host array of 4; element (n,c,h,w) lands at
- * out[n][h+ph][w+pw][c]; everything else is zero.  (The reference hands F.conv2d the NCHW tensor and a padding
- * argument: layers/flipout_layers/conv_flipout.py:376-383.) */
+ * out[n][h+ph][w+pw][c]; everything else is zero.  x is read element by element; out: 16-byte aligned (BTX_E_ALIGN), one
+ * store per padded pixel.  (The reference hands F.conv2d the NCHW tensor and a padding argument:
+ * layers/flipout_layers/conv_flipout.py:376-383.) */
 int btx_rowfuse_pack(const void* x, int in_dtype, const int64_t* strides_ncHW_host, int NB, int C, int H, int W,
                      void* out, int out_dtype, int Hp, int Wp, int cp, int ph, int pw, void* stream);
 
@@ -536,9 +539,9 @@ int btx_lstm_bwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint6
  *   weights (1 - tanh e | tanh e) x (conf | 1 - conf).  good = error <= error_th.  derror / dother: either nullable.
  * A threshold is the float argument, or — when its *_dev pointer is non-NULL — one f32 word in device memory that the kernel
  * reads when it runs (a captured graph follows an updated threshold).
- * ws: btx_calib_workspace_bytes(B) bytes, written by the forward and read by the backward.  Every sum has a fixed shape and
+ * ws: btx_calib_workspace_bytes(B) bytes, 8-byte aligned, written by the forward and read by the backward.  Every sum has a fixed shape and
  * no atomics: two runs give the same bits.  Three launches for forward + backward (AvU forms), two for EaU / EaC.
- * Errors: BTX_E_NULL, BTX_E_SHAPE (B, C <= 0, area / conf_form not 0 or 1), BTX_E_DTYPE, BTX_E_WORKSPACE. */
+ * Errors: BTX_E_NULL, BTX_E_SHAPE (B, C <= 0, area / conf_form not 0 or 1), BTX_E_DTYPE, BTX_E_WORKSPACE, BTX_E_ALIGN (ws). */
 size_t btx_calib_workspace_bytes(int B);
 int btx_avu_fwd(const void* logits, const int64_t* labels, int B, int C, int act_dtype, int area, float th, const float* th_dev,
                 float beta, float* out, void* ws, size_t ws_bytes, void* stream);
