@@ -130,7 +130,9 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_q8_weight_row_bytes", "btx_q8_quantize_act", "btx_q8_sample_weights", "btx_q8_contract",
            "btx_q8_add", "btx_q8_contract_res", "btx_q8_maxpool2d_cl", "btx_q8_avgpool2d_cl",
            "btx_q8_sample_delta", "btx_q8_contract_flipout",
-           "btx_optim_sgd", "btx_optim_adam", "btx_optim_grad_norm_workspace_bytes", "btx_optim_grad_norm")
+           "btx_optim_sgd", "btx_optim_adam", "btx_optim_grad_norm_workspace_bytes", "btx_optim_grad_norm",
+           "btx_mcloss_workspace_bytes", "btx_mc_ce_fwd", "btx_mc_ce_bwd", "btx_avu_mc_fwd", "btx_avu_mc_bwd",
+           "btx_bias_grad_workspace_bytes", "btx_bias_grad")
 
 
 def lib_path():
@@ -283,6 +285,20 @@ def lib():
     L.btx_optim_grad_norm_workspace_bytes.argtypes = [i32, ctypes.c_int64]
     L.btx_optim_grad_norm.restype = i32
     L.btx_optim_grad_norm.argtypes = [ctypes.POINTER(OptimItem), i32, f32, vp, vp, sz, vp]
+    L.btx_mcloss_workspace_bytes.restype = sz
+    L.btx_mcloss_workspace_bytes.argtypes = [i32, i32]
+    L.btx_mc_ce_fwd.restype = i32
+    L.btx_mc_ce_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, f32, vp, vp, sz, vp]
+    L.btx_mc_ce_bwd.restype = i32
+    L.btx_mc_ce_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, sz, vp, vp]
+    L.btx_avu_mc_fwd.restype = i32
+    L.btx_avu_mc_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, f32, vp, vp, sz, vp]
+    L.btx_avu_mc_bwd.restype = i32
+    L.btx_avu_mc_bwd.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, sz, vp, vp]
+    L.btx_bias_grad_workspace_bytes.restype = sz
+    L.btx_bias_grad_workspace_bytes.argtypes = [ctypes.c_int64, i32]
+    L.btx_bias_grad.restype = i32
+    L.btx_bias_grad.argtypes = [i32, vp, ctypes.c_int64, i32, i32, vp, vp, ctypes.POINTER(Rng), vp, ctypes.c_uint32, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

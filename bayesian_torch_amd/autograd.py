@@ -13,6 +13,11 @@ the backward: eps and the Flipout signs are regenerated.
   dmu, drho      btx_contract_wgrad: dW_mu = corr(x, dy) [and dW_delta = corr(x*s_in, dy*s_out) for Flipout] — a GEMM whose
                  reduction axis is the pixel axis, on the exact-f32 MFMA (csrc/btx_wgrad.hip); dmu = dW_mu and
                  drho = dW_delta * eps * sigmoid(rho) are elementwise follow-ups here.
+
+Steps with num_mc > 1 Monte-Carlo samples (reference examples/main_bayesian_cifar.py:363-372): mc_train_forward is
+the eager loop ([num_mc, B, C] logits, pass k on sample index step * num_mc + k), GraphedTrainStep(num_mc=n) the captured one (n
+device sample words, one per pass).  A layer's backward regenerates the noise of the word its FORWARD read (kept on ctx), so passes
+on different words can share one backward.  The loss head of the stack is utils.mc_loss (csrc/btx_mcloss.hip).
 """
 import ctypes
 
@@ -38,9 +43,9 @@ def fast_dgrad_ok(layer):
     return False
 
 
-def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho):
+def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho, sdev=None):
     """dx through libbtx: the contraction of dy with the (mu, sigma*eps) the FORWARD used (the tensors autograd saved) on
-    the transposed geometry"""
+    the transposed geometry.  sdev: the device sample word the forward read (None: the host index `sample_idx`)"""
     op = layer._op
     kind = _lib.KIND_FLIPOUT if layer._family == "flipout" else _lib.KIND_REPARAM
     nd = op.nd
@@ -59,7 +64,6 @@ def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho):
             opT = BF.OpDesc(2, op.out_channels, op.in_channels, op.kernel[1:], op.stride[1:], op.padding[1:], op.dilation[1:], 1,
                             transposed=True, output_padding=outpad)
             taps, flip = op.kernel[1] * op.kernel[2], False
-        sdev = getattr(layer, "_btx_sample_dev", None)  # captured training step: the sample index is a device word
         w_mu, w_rho, w_eps = BF.dgrad_weights_hip(mu_p, rho_p, op.out_channels, taps, op.in_channels, flip, _rng.seed(),
                                                   sample_idx, layer._btx_layer_id, sample_dev=sdev)
         dx = BF.contract_hip(kind, dy, w_mu, w_rho, None, None, opT, _rng.seed(), sample_idx, layer._btx_layer_id,
@@ -98,7 +102,7 @@ def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho):
             noise["sign_in"], noise["sign_out"] = nz["sign_out"], nz["sign_in"]
     dx = BF.contract_hip(kind, dy, BF.pack_gemm_major(w_mu.float(), opT), BF.pack_gemm_major(w_rho.float(), opT), None, None,
                          opT, _rng.seed(), sample_idx, layer._btx_layer_id, prec=layer.precision, noise=noise,
-                         extra_flags=flags, sample_dev=getattr(layer, "_btx_sample_dev", None))
+                         extra_flags=flags, sample_dev=sdev)
     return dx.reshape(x_shape) if nd == 0 else dx
 
 
@@ -110,6 +114,9 @@ class ContractFn(torch.autograd.Function):
         with torch.no_grad():
             out = layer._forward_hip(x, sample_idx=sample_idx)
         ctx.layer, ctx.sample_idx = layer, sample_idx
+        # the device sample word THIS forward read: a step with several MC passes (num_mc > 1) points the layer at another word
+        # before the next pass, and the backward must regenerate this pass's noise, not the last one's
+        ctx.sample_dev = getattr(layer, "_btx_sample_dev", None)
         ctx.save_for_backward(x, mu, rho, rho_b)  # mu: the data gradient contracts with it (autograd's version check applies)
         return out
 
@@ -136,7 +143,7 @@ class ContractFn(torch.autograd.Function):
             fast_dx = plain_w and fast_dgrad_ok(layer)  # the data gradient regenerates eps in its own operand pass
             need_nz = ((ctx.needs_input_grad[2] and not fast_dx) or not plain_w or need_signs or
                        (rho_b is not None and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6])))
-            sdev = getattr(layer, "_btx_sample_dev", None)  # captured step: eps / signs follow the device word, not `s`
+            sdev = ctx.sample_dev  # captured step: eps / signs follow the device word the forward read, not `s`
             nz = layer.materialize_noise(s, tuple(x.shape), tuple(dy.shape), x.dtype, signs=need_signs,
                                          sample_dev=sdev) if need_nz else {}
             dx = dmu = drho = dmu_b = drho_b = None
@@ -190,7 +197,7 @@ class ContractFn(torch.autograd.Function):
                     drho_b = (dbd if flip else db) * nz["eps_b"] * torch.sigmoid(rho_b.detach())
             if ctx.needs_input_grad[2]:
                 hashed = flip and not padded
-                dx = _data_grad_hip(layer, dy, tuple(x.shape), nz, s, hashed, mu_s, rho)
+                dx = _data_grad_hip(layer, dy, tuple(x.shape), nz, s, hashed, mu_s, rho, sdev)
                 if dx.dtype != x.dtype:
                     dx = dx.to(x.dtype)
         return None, None, dx, dmu, drho, dmu_b, drho_b
@@ -494,6 +501,46 @@ def max_pool_train(mp, x):
     return MaxPool2dTrainFn.apply(x, sq(mp.kernel_size), sq(mp.stride if mp.stride is not None else mp.kernel_size), sq(mp.padding))
 
 
+def _refuse_lstm(model, what):
+    from .layers.base_variational_layer import _VariationalLSTM
+    for name, m in model.named_modules():
+        if isinstance(m, _VariationalLSTM):
+            raise _lib.BtxError("%s: the model holds the Bayesian LSTM %r (%s); its time steps consume the sample indices s + t, "
+                                "which collide with the indices of the Monte-Carlo passes: use num_mc=1" % (what, name, type(m).__name__))
+
+
+def mc_train_forward(model, x, num_mc, step):
+    """[num_mc, B, C] logits of `num_mc` Monte-Carlo training forwards of `model` on `x`, carrying gradient: the eager form of the
+    reference's loop (examples/main_bayesian_cifar.py:363-372).  Pass k runs set_sample_index(model, (step * num_mc + k) &
+    0x7FFFFFFF, presample=x.is_cuda) and model(x); a tuple output contributes its element 0.  CPU tensors take the ATen route
+    with torch's CPU generator keyed on the index for the duration of the pass, as mc.mc_forward does.
+    Training BatchNorm sees num_mc forwards (running_* and num_batches_tracked advance num_mc times, as in the reference); num_mc
+    sets of saved activations live until the backward.  A model that holds a Bayesian LSTM is refused (BtxError), and so is a model
+    whose layers still read a device sample word (close() the GraphedTrainStep / GraphedMC first)."""
+    num_mc = int(num_mc)
+    if num_mc < 1:
+        raise ValueError("num_mc must be >= 1")
+    _refuse_lstm(model, "mc_train_forward")
+    for name, m in model.named_modules():
+        if getattr(m, "_btx_sample_dev", None) is not None:
+            # a live GraphedTrainStep / mc.GraphedMC keeps the sample index in ONE device word: every pass here would rewrite it and
+            # every backward would then regenerate the LAST pass's noise
+            raise _lib.BtxError("mc_train_forward: layer %r reads its sample index from a device word (a live GraphedTrainStep or "
+                                "GraphedMC on this model); close() it first" % name)
+    outs = []
+    for k in range(num_mc):
+        idx = (int(step) * num_mc + k) & 0x7FFFFFFF
+        _rng.set_sample_index(model, idx, presample=x.is_cuda)
+        if x.is_cuda:
+            out = model(x)
+        else:
+            with torch.random.fork_rng(devices=[]):
+                torch.default_generator.manual_seed(_rng.cpu_sample_seed(idx))  # the CPU generator ONLY
+                out = model(x)
+        outs.append(out[0] if isinstance(out, tuple) else out)
+    return torch.stack(outs)
+
+
 class GraphedTrainStep:
     """forward + loss + backward of `model` on a fixed batch, captured ONCE into a hipGraph and replayed per training step
     (reference README.md:114-125: `output = model(x); kl = get_kl_loss(model); loss = ce(output, y) + kl / batch_size;
@@ -518,28 +565,47 @@ class GraphedTrainStep:
     In-place parameter updates between replays are seen (the kernels read mu / rho where they live); x / target are read from the
     tensors given here (copy new batches INTO them).  Layers on padded layouts that need their input gradient (sign tensors keyed
     on the host) cannot be captured and raise.  Drop every reference to the loss / outputs of earlier EAGER steps of this model
-    before constructing one (torch: a live autograd graph pins its AccumulateGrad nodes to the stream it ran on)."""
+    before constructing one (torch: a live autograd graph pins its AccumulateGrad nodes to the stream it ran on).
 
-    def __init__(self, model, x, target, loss_fn=None, warmup=2, optimizer=None):
+    num_mc = n > 1: the reference's Monte-Carlo training loop (examples/main_bayesian_cifar.py:363-372) inside ONE graph.  The step
+    holds n device sample words; pass k points every layer at word k, pre-samples and runs model(x); the n outputs are stacked to
+    [n, B, C] and `loss_fn(stack, target)` is called ONCE, then loss.backward() and the captured optimizer.  run(step) writes the
+    words step * n + k with one copy.  The default loss is utils.mc_loss.mc_elbo_loss(stack, target, kl=get_kl_loss(model)):
+    CE(mean_k logits_k, y) + kl / B, the KL (RNG-free) evaluated once.  `out` of loss_fn is 3-D then; num_mc = 1 keeps the 2-D
+    `out`, the single word and the default loss above.  Consequences: training BatchNorm sees n forwards per step (running_* and
+    num_batches_tracked advance n times, as in the reference's loop); n sets of saved activations live until the backward (no
+    recomputation).  Models that hold a Bayesian LSTM are refused for n > 1 (its time steps consume the indices s + t, which would
+    collide with the passes')."""
+
+    def __init__(self, model, x, target, loss_fn=None, warmup=2, optimizer=None, num_mc=1):
         from .models.dnn_to_bnn import get_kl_loss
         from . import optim as _optim
         if not x.is_cuda:
             raise ValueError("GraphedTrainStep needs CUDA (ROCm) tensors")
+        self.num_mc = int(num_mc)
+        if self.num_mc < 1:
+            raise ValueError("num_mc must be >= 1")
+        if self.num_mc > 1:
+            _refuse_lstm(model, "GraphedTrainStep(num_mc=%d)" % self.num_mc)
         if optimizer is not None and not isinstance(optimizer, _optim._BtxOptimizer):
             raise TypeError("GraphedTrainStep(optimizer=) takes bayesian_torch_amd.optim.SGD / Adam / AdamW (got %s): a torch.optim "
                             "step cannot be captured here; call it after run() instead" % type(optimizer).__name__)
         self.optimizer, self._plan = optimizer, None
         self.model, self.x, self.target = model, x, target
         bs = x.shape[0]
+        if loss_fn is None and self.num_mc > 1:
+            from .utils.mc_loss import mc_elbo_loss
+            loss_fn = lambda out, tgt: mc_elbo_loss(out, tgt, kl=get_kl_loss(model), reduce="logits")  # noqa: E731
         self.loss_fn = loss_fn or (lambda out, tgt: torch.nn.functional.cross_entropy(out.float(), tgt) + get_kl_loss(model) / bs)
         dev = x.device
         import gc
         gc.collect()  # autograd graphs of earlier eager steps still referenced from garbage would pin AccumulateGrad nodes to the
         torch.cuda.synchronize(dev)  # caller's stream (torch warns that this "may break CUDA graph capture": it does)
         self._layers = [m for m in model.modules() if hasattr(m, "_btx_layer_id")]
-        self.sample_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sample_dev = torch.zeros(self.num_mc, dtype=torch.int32, device=dev)  # one word per MC pass
+        self._words = [self.sample_dev[k:k + 1] for k in range(self.num_mc)]
         for m in self._layers:
-            m.__dict__["_btx_sample_dev"] = self.sample_dev
+            m.__dict__["_btx_sample_dev"] = self._words[0]
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -568,16 +634,31 @@ class GraphedTrainStep:
     def _step(self):
         for p_ in self.model.parameters():
             p_.grad = None
-        _rng.presample(self.model, 0)  # one sampling launch for the forward of every layer (reads the device word)
-        out = self.model(self.x)
-        if isinstance(out, tuple):
-            out = out[0]
+        if self.num_mc == 1:
+            out = self._pass()
+        else:
+            outs = []
+            for w in self._words:  # pass k reads word k; each ContractFn keeps the word its forward read for its backward
+                for m in self._layers:
+                    m.__dict__["_btx_sample_dev"] = w
+                outs.append(self._pass())
+            out = torch.stack(outs)
         loss = self.loss_fn(out, self.target)
         loss.backward()
         return loss.detach()
 
+    def _pass(self):
+        _rng.presample(self.model, 0)  # one sampling launch for the forward of every layer (reads the device word)
+        out = self.model(self.x)
+        return out[0] if isinstance(out, tuple) else out
+
     def run(self, sample_idx):
-        self.sample_dev.fill_(int(sample_idx) & 0x7FFFFFFF)
+        """replay with MC sample index `sample_idx` (num_mc = n > 1: the step number; pass k draws sample step * n + k)"""
+        if self.num_mc == 1:
+            self.sample_dev.fill_(int(sample_idx) & 0x7FFFFFFF)
+        else:
+            n = self.num_mc
+            self.sample_dev.copy_(torch.tensor([(int(sample_idx) * n + k) & 0x7FFFFFFF for k in range(n)], dtype=torch.int32))
         if self._plan is not None:
             with torch.no_grad():
                 self.optimizer._advance(self._plan)  # step counts, and lr & co. as the groups hold them NOW, into the device blocks

@@ -539,6 +539,7 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
 
 
 WGRAD_ATOMICS = False  # A/B and tests: accumulate the weight gradient with f32 atomics instead of chunk slabs
+BIAS_ATOMICS = False   # A/B (tools/bias_grad_bench.py): the bias gradient as the weight-gradient kernel's by-product (f32 atomics over its chunks)
 
 
 def wgrad_hip(kind, x, dy, op, seed, sample_idx, layer_id, w_shape, signs=None, swap=False, bias=False, rowfuse=None,
@@ -609,11 +610,20 @@ def wgrad_hip(kind, x, dy, op, seed, sample_idx, layer_id, w_shape, signs=None, 
             raise _lib.BtxError("wgrad_hip: rho_flat must be the contiguous f32 GEMM-major rho of the layer")
         drho = dwd if flip else torch.empty_like(dwm)
     if wsb > 0:
+        # the slab path adds the WEIGHT gradient's chunks in a fixed order, but the kernel's bias sums would still meet in f32 atomics
+        # (last bit = arrival order of the chunks): the bias gradients come from btx_bias_grad instead, in a fixed order as well
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        own = bias and not BIAS_ATOMICS
         _lib.check(L.btx_contract_wgrad_ws(kind, ctypes.byref(g), xp.data_ptr(), dyp.data_ptr(), dwm.data_ptr(), ptr(dwd),
-                                           ptr(dbm), ptr(dbd), ctypes.byref(r), ctypes.byref(nz) if nz is not None else None,
-                                           act, flags, ws.data_ptr(), wsb, ptr(rho_flat), ptr(drho),
-                                           torch.cuda.current_stream(dev).cuda_stream))
+                                           None if own else ptr(dbm), None if own else ptr(dbd), ctypes.byref(r),
+                                           ctypes.byref(nz) if nz is not None else None,
+                                           act, flags, ws.data_ptr(), wsb, ptr(rho_flat), ptr(drho), stream))
+        if own:
+            m_px = dyp.numel() // n
+            bws = torch.empty(int(L.btx_bias_grad_workspace_bytes(m_px, n)) // 4, dtype=torch.float32, device=dev)
+            _lib.check(L.btx_bias_grad(kind, dyp.data_ptr(), m_px, n, act, dbm.data_ptr(), ptr(dbd), ctypes.byref(r),
+                                       nz.sign_out if nz is not None else None, flags, bws.data_ptr(), bws.numel() * 4, stream))
     else:
         _lib.check(L.btx_contract_wgrad(kind, ctypes.byref(g), xp.data_ptr(), dyp.data_ptr(), dwm.data_ptr(), ptr(dwd),
                                         ptr(dbm), ptr(dbd), ctypes.byref(r), ctypes.byref(nz) if nz is not None else None,

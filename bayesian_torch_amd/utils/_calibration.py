@@ -9,6 +9,8 @@ Two implementations of the same arithmetic:
     take (rows wider than mc.MC_MAX_CLASSES, other dtypes).  In float64 it is the oracle of the tests.
   * libbtx.so K9 (include/btx.h: btx_avu_fwd / btx_avu_bwd / btx_eau_fwd / btx_eau_bwd) behind `AvuFn` / `EauFn`: three launches
     for forward + backward, no host read, workspaces from torch's allocator — capturable under torch.cuda.graph.
+`avu_mc_chain` / `AvuMcFn` (btx_avu_mc_fwd / btx_avu_mc_bwd, csrc/btx_mcloss.hip) are the same loss on an MC stack [S, B, C] with the
+mutual information as the uncertainty (type=1).
 """
 import numpy as np
 import torch
@@ -18,6 +20,7 @@ from .. import _lib
 
 EPS = 1e-10
 N_THRESHOLDS = 21  # np.linspace(0, 1, 21) of the reference's area form
+AVU_MC_MAX_CLASSES = 16128  # BTX_AVU_MC_MAX_CLASSES: the type=1 backward keeps a row of C floats in LDS; wider rows run the chain
 
 
 def _backend():
@@ -76,6 +79,35 @@ def avu_chain(logits, labels, th, beta, area):
         r = (0.05 * (rk[:-1] + rk[1:]) * 0.5).sum().reshape(1)
     else:
         cert = ent.detach() <= _threshold_like(th, ent)
+        r = _ratio(wc, wu, good, cert).reshape(1)
+    return -1 * beta * torch.log(r + EPS), r
+
+
+def mc_row_stats(stack):
+    """confidence, prediction and model uncertainty of every batch row of an MC stack [S, B, C] of logits:
+    p_s = softmax(logits_s), pbar = mean_s p_s, conf / pred from pbar (lowest index on ties), and the mutual information
+    H(pbar) - mean_s H(p_s) with epsilon 1e-10 inside every log (the reference's model_uncertainty / expected_entropy)"""
+    probs = F.softmax(stack, dim=2)
+    pbar = probs.mean(0)
+    conf, pred = torch.max(pbar, 1)
+    h_bar = -1 * torch.sum(pbar * torch.log(pbar + EPS), dim=-1)
+    h_exp = (-1 * torch.sum(probs * torch.log(probs + EPS), dim=-1)).mean(0)
+    return conf, pred, h_bar - h_exp
+
+
+def avu_mc_chain(stack, labels, th, beta, area):
+    """avu_chain on an MC stack [S, B, C]: the same quadrant arithmetic with (conf, pred, uncertainty) of mc_row_stats"""
+    conf, pred, unc = mc_row_stats(stack)
+    good = pred == labels.reshape(-1)
+    tu = torch.tanh(unc)
+    w = torch.where(good, conf, 1 - conf)
+    wc, wu = w * (1 - tu), w * tu
+    if area:
+        cert = unc.detach().double().unsqueeze(0) <= area_thresholds(unc).unsqueeze(1)  # [K, B]
+        rk = _ratio(wc, wu, good, cert)
+        r = (0.05 * (rk[:-1] + rk[1:]) * 0.5).sum().reshape(1)
+    else:
+        cert = unc.detach() <= _threshold_like(th, unc)
         r = _ratio(wc, wu, good, cert).reshape(1)
     return -1 * beta * torch.log(r + EPS), r
 
@@ -185,7 +217,8 @@ class EauFn(torch.autograd.Function):
 def avu(logits, labels, th, beta, area):
     """dispatch: (loss [1], r [1])"""
     if logits.dim() != 2:
-        raise ValueError("logits must be [batch, classes]; MC-stacked [S, batch, classes] logits are not supported")
+        raise ValueError("logits must be [batch, classes] for type=0 (predictive entropy); MC-stacked [S, batch, classes] logits "
+                         "go with type=1 (model uncertainty)")
     if labels.numel() != logits.shape[0]:
         raise ValueError("labels must hold one class index per row of logits")
     from ..mc import MC_MAX_CLASSES
@@ -194,6 +227,53 @@ def avu(logits, labels, th, beta, area):
             and 0 < logits.shape[1] <= MC_MAX_CLASSES):
         return AvuFn.apply(logits, labels, th, beta, bool(area))
     return avu_chain(logits, labels, th, beta, bool(area))
+
+
+class AvuMcFn(torch.autograd.Function):
+    """(loss [1], r [1]) of an MC stack [S, B, C] of f32 / bf16 CUDA logits through btx_avu_mc_fwd (model uncertainty, type=1)"""
+
+    @staticmethod
+    def forward(ctx, stack, labels, th, beta, area):
+        lg = stack.contiguous()
+        lb = labels.reshape(-1).contiguous()
+        S, B, C = lg.shape
+        thf, thd = _th_args(0.0 if area else th, lg.device)
+        ws = torch.empty(_lib.lib().btx_mcloss_workspace_bytes(S, B) // 4, dtype=torch.float32, device=lg.device)
+        out = torch.empty(2, dtype=torch.float32, device=lg.device)
+        act = _lib.ACT_BF16 if lg.dtype == torch.bfloat16 else _lib.ACT_F32
+        _lib.check(_lib.lib().btx_avu_mc_fwd(lg.data_ptr(), lb.data_ptr(), S, B, C, act, 1 if area else 0, thf, _ptr(thd),
+                                             float(beta), out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                             torch.cuda.current_stream(lg.device).cuda_stream))
+        ctx.save_for_backward(lg, ws)
+        ctx.act = act
+        ctx.set_materialize_grads(False)
+        return out[0:1], out[1:2]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_r):
+        lg, ws = ctx.saved_tensors
+        if g_loss is None and g_r is None:
+            return None, None, None, None, None
+        g_loss = None if g_loss is None else g_loss.float().contiguous()
+        g_r = None if g_r is None else g_r.float().contiguous()
+        dl = torch.empty_like(lg)
+        S, B, C = lg.shape
+        _lib.check(_lib.lib().btx_avu_mc_bwd(lg.data_ptr(), S, B, C, ctx.act, _ptr(g_loss), _ptr(g_r), ws.data_ptr(),
+                                             ws.numel() * 4, dl.data_ptr(), torch.cuda.current_stream(lg.device).cuda_stream))
+        return dl, None, None, None, None
+
+
+def avu_mc(stack, labels, th, beta, area):
+    """dispatch for type=1 (model uncertainty): (loss [1], r [1]) of an MC stack [S, B, C]"""
+    if stack.dim() != 3:
+        raise ValueError("type=1 (model uncertainty) needs Monte-Carlo stacked logits [S, batch, classes]; "
+                         "use type=0 (predictive entropy) on [batch, classes] logits")
+    if labels.numel() != stack.shape[1]:
+        raise ValueError("labels must hold one class index per batch row of the stacked logits")
+    from .mc_loss import hip_usable
+    if hip_usable(stack, labels) and stack.shape[2] <= AVU_MC_MAX_CLASSES:
+        return AvuMcFn.apply(stack, labels, th, beta, bool(area))
+    return avu_mc_chain(stack, labels, th, beta, bool(area))
 
 
 def eau(error, other, error_th, other_th, beta, conf_form):

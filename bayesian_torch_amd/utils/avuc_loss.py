@@ -16,8 +16,13 @@ Deviations from the reference:
   * thresholds th_k = umin + t_k (umax - umin) are evaluated in double from the f32 umin / umax and compared with the entropy
     promoted to double; th_20 = umax exactly.  The reference rounds umax - umin in f32 first, which makes the membership of the
     most uncertain example at t = 1 a last-bit coin flip.
-  * type=1 (model uncertainty) needs MC-stacked [S, B, C] logits; on 2-D logits the reference indexes a 0-d tensor and
-    crashes, here it raises ValueError.  Stacked logits are not supported.
+  * type=1 (model uncertainty) takes MC-stacked [S, B, C] logits (autograd.mc_train_forward, or the `out` of
+    GraphedTrainStep(num_mc=S)) and labels [B]: p_s = softmax(logits_s), pbar = mean_s p_s, confidence / prediction from pbar, the
+    uncertainty is the mutual information H(pbar) - mean_s H(p_s) (epsilon 1e-10 inside every log), then the same quadrant
+    arithmetic; gradients flow through the soft weights into all S samples.  CUDA stacks with S <= 32 and C <= 16128 run btx_avu_mc_fwd / _bwd,
+    everything else the chain.  The reference gives no oracle value here: its forward applies softmax(dim=1) to whatever it gets,
+    i.e. over the BATCH axis of a stack.  On 2-D logits type=1 raises ValueError (the reference indexes a 0-d tensor and crashes);
+    3-D logits with type=0 raise as well.
   * the arg-max tie-break is the lowest index; no print of the counts.
 """
 import numpy as np
@@ -27,14 +32,18 @@ from torch import nn
 from . import _calibration as _c
 
 
-def _check_type(type):
-    if type != 0:
-        raise ValueError("type=1 (model uncertainty) needs Monte-Carlo stacked logits [S, batch, classes], which this "
-                         "implementation does not take; use type=0 (predictive entropy) on [batch, classes] logits")
+def _avu(logits, labels, th, beta, area, type):
+    if type == 0:
+        return _c.avu(logits, labels, th, beta, area)
+    if type == 1:
+        return _c.avu_mc(logits, labels, th, beta, area)
+    raise ValueError("type must be 0 (predictive entropy, [batch, classes] logits) or 1 (model uncertainty, Monte-Carlo stacked "
+                     "[S, batch, classes] logits), got %r" % (type,))
 
 
 class AvULoss(nn.Module):
-    """loss [1] = -beta * log(AvU + 1e-10) of logits [B, C] and labels [B] at one uncertainty threshold"""
+    """loss [1] = -beta * log(AvU + 1e-10) of logits [B, C] (type=0) or an MC stack [S, B, C] (type=1) and labels [B] at one
+    uncertainty threshold"""
 
     def __init__(self, beta=1):
         super().__init__()
@@ -42,8 +51,7 @@ class AvULoss(nn.Module):
         self.eps = _c.EPS
 
     def forward(self, logits, labels, optimal_uncertainty_threshold, type=0):
-        _check_type(type)
-        return _c.avu(logits, labels, optimal_uncertainty_threshold, self.beta, False)[0]
+        return _avu(logits, labels, optimal_uncertainty_threshold, self.beta, False, type)[0]
 
 
 class AUAvULoss(nn.Module):
@@ -56,8 +64,7 @@ class AUAvULoss(nn.Module):
         self.eps = _c.EPS
 
     def forward(self, logits, labels, type=0):
-        _check_type(type)
-        return _c.avu(logits, labels, None, self.beta, True)
+        return _avu(logits, labels, None, self.beta, True, type)
 
 
 def entropy(prob):

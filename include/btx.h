@@ -708,6 +708,48 @@ size_t btx_optim_grad_norm_workspace_bytes(int n_items, int64_t total_elements);
 int btx_optim_grad_norm(const BtxOptimItem* items, int n_items, float max_norm, float* out_dev, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* K12 (ABI 9, additive): loss heads on a stack of Monte-Carlo logits [S][B][C] (contiguous, act_dtype f32 or bf16),
+ * labels int64 [B].  f32 arithmetic, max-subtracted softmax / log-sum-exp; one workgroup per batch row for all S samples; every sum
+ * has a fixed shape and no atomics: two runs give the same bits.  No host read, no allocation: capturable into a hipGraph.
+ * 1 <= S <= BTX_MCLOSS_MAX_S, B >= 1 (else BTX_E_SHAPE), 1 <= C <= BTX_MCLOSS_MAX_CLASSES (C < 1: BTX_E_SHAPE, wider:
+ * BTX_E_UNSUPPORTED).  Rows off the 16-byte grid (any pointer, any C) take the element-wise path: same bits, never BTX_E_ALIGN.
+ * ws: btx_mcloss_workspace_bytes(S, B) bytes (enough for either head), 8-byte aligned, written by a forward and read by ITS backward.
+ * btx_mc_ce_fwd: out[0] = ce + (kl ? kl[0] * inv_b : 0);  reduce 0: ce = inv_b * sum_b CE(mean_s z_s[b], y_b), reduce 1:
+ *   ce = inv_b * sum_b mean_s CE(z_s[b], y_b);  CE with label smoothing ls in [0, 1): lse(z) - (1 - ls) z[y] - ls / C * sum_c z[c].
+ *   kl: DEVICE pointer to one f32, nullable.  inv_b: the caller's 1 / B.
+ * btx_mc_ce_bwd: dlogits [S][B][C] in act_dtype = g_loss[0] * d ce / d logits, fully overwritten; g_loss: DEVICE scalar.  (The gradient
+ *   of the kl input is g_loss[0] * inv_b: the caller's.)
+ * btx_avu_mc_fwd / btx_avu_mc_bwd: btx_avu_fwd / btx_avu_bwd with p_s = softmax(z_s), pbar = mean_s p_s, confidence and prediction
+ *   from pbar (lowest index on ties) and the uncertainty u = H(pbar) - mean_s H(p_s), epsilon 1e-10 inside every log, in place of the
+ *   entropy; area, th, th_dev, beta, out[0..1], g_loss, g_r as there.  Gradients flow through the soft weights into all S samples.
+ *   The backward keeps a row of C floats in LDS: C <= BTX_AVU_MC_MAX_CLASSES (wider: BTX_E_UNSUPPORTED, from forward and backward alike).
+ * Errors: BTX_E_NULL, BTX_E_SHAPE (also reduce / area not 0 or 1, label_smoothing outside [0, 1)), BTX_E_UNSUPPORTED, BTX_E_DTYPE,
+ *   BTX_E_WORKSPACE, BTX_E_ALIGN (ws only), all before anything is launched. */
+#define BTX_MCLOSS_MAX_S 32
+#define BTX_MCLOSS_MAX_CLASSES 24575
+#define BTX_AVU_MC_MAX_CLASSES 16128   /* btx_avu_mc_*: the backward's LDS row of C floats stays below the 64 KiB every kernel may use */
+size_t btx_mcloss_workspace_bytes(int S, int B);
+int btx_mc_ce_fwd(const void* logits, const int64_t* labels, int S, int B, int C, int act_dtype, int reduce, float label_smoothing,
+                  const float* kl, float inv_b, float* out, void* ws, size_t ws_bytes, void* stream);
+int btx_mc_ce_bwd(const void* logits, const int64_t* labels, int S, int B, int C, int act_dtype, int reduce, float label_smoothing,
+                  float inv_b, const float* g_loss, const void* ws, size_t ws_bytes, void* dlogits, void* stream);
+int btx_avu_mc_fwd(const void* logits, const int64_t* labels, int S, int B, int C, int act_dtype, int area, float th,
+                   const float* th_dev, float beta, float* out, void* ws, size_t ws_bytes, void* stream);
+int btx_avu_mc_bwd(const void* logits, int S, int B, int C, int act_dtype, const float* g_loss, const float* g_r, const void* ws,
+                   size_t ws_bytes, void* dlogits, void* stream);
+
+/* K13 (ABI 9, additive): the bias gradient of a variational layer with a fixed summation order,
+ *   db_mu[n] = sum_m dy[m][n],   Flipout also  db_delta[n] = sum_m dy[m][n] * s_out[m][n];   dy [M][N] pixel-major in act_dtype.
+ * s_out: `sign_out` (int8 +/-1, dy's layout) when non-NULL, else the hashed BTX-RNG v1 sign of element m * N + n under `rng` — the
+ * signs btx_contract_wgrad applies to dy (BTX_FLAG_SWAP_SIGNS in `flags` selects the SIGN_IN stream; rng->sample_idx_dev is honoured).
+ * btx_contract_wgrad[_ws] can return the same sums (db_mu / db_delta non-NULL), accumulated with f32 atomics over its pixel chunks:
+ * equal up to the order of the additions, not bit-reproducible.  Here a thread adds its pixels in order, rows and parts are added in
+ * index order: two runs give the same bits.  ws: btx_bias_grad_workspace_bytes(M, N) bytes, 4-byte aligned (may be NULL when M <= 1024).
+ * Errors: BTX_E_NULL, BTX_E_UNSUPPORTED (kind), BTX_E_SHAPE (M, N < 1), BTX_E_DTYPE, BTX_E_WORKSPACE, BTX_E_ALIGN (ws). */
+size_t btx_bias_grad_workspace_bytes(int64_t M, int N);
+int btx_bias_grad(int kind, const void* dy, int64_t M, int N, int act_dtype, float* db_mu, float* db_delta, const BtxRng* rng,
+                  const int8_t* sign_out, uint32_t flags, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
