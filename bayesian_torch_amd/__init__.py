@@ -13,6 +13,7 @@ import sys
 from . import _lib, functional, rng  # noqa: F401
 from . import layers, models, utils  # noqa: F401
 from . import optim  # noqa: F401
+from . import parallel  # noqa: F401
 from .functional import set_precision, get_precision, set_output_layout  # noqa: F401
 from .layers.base_variational_layer import set_backend  # noqa: F401
 from .models.dnn_to_bnn import dnn_to_bnn, get_kl_loss  # noqa: F401

@@ -108,6 +108,10 @@ class OptimItem(ctypes.Structure):
                 ("n", ctypes.c_int64)]
 
 
+class BucketItem(ctypes.Structure):  # K14: n elements at src <-> bucket + offset
+    _fields_ = [("src", ctypes.c_void_p), ("offset", ctypes.c_int64), ("n", ctypes.c_int64)]
+
+
 class OptimHyper(ctypes.Structure):  # the DEVICE block of BTX-OPT v1: 16 words, filled on the host and copied
     _fields_ = [(n, ctypes.c_float) for n in ("neg_lr", "wd", "decay_mul", "one_m_b1", "b2", "one_m_b2", "eps", "neg_step_size",
                                               "bc2s", "momentum", "one_m_damp")] + \
@@ -132,7 +136,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_q8_sample_delta", "btx_q8_contract_flipout",
            "btx_optim_sgd", "btx_optim_adam", "btx_optim_grad_norm_workspace_bytes", "btx_optim_grad_norm",
            "btx_mcloss_workspace_bytes", "btx_mc_ce_fwd", "btx_mc_ce_bwd", "btx_avu_mc_fwd", "btx_avu_mc_bwd",
-           "btx_bias_grad_workspace_bytes", "btx_bias_grad")
+           "btx_bias_grad_workspace_bytes", "btx_bias_grad",
+           "btx_bucket_pack", "btx_bucket_unpack")
 
 
 def lib_path():
@@ -299,6 +304,10 @@ def lib():
     L.btx_bias_grad_workspace_bytes.argtypes = [ctypes.c_int64, i32]
     L.btx_bias_grad.restype = i32
     L.btx_bias_grad.argtypes = [i32, vp, ctypes.c_int64, i32, i32, vp, vp, ctypes.POINTER(Rng), vp, ctypes.c_uint32, vp, sz, vp]
+    L.btx_bucket_pack.restype = i32
+    L.btx_bucket_pack.argtypes = [ctypes.POINTER(BucketItem), i32, f32, vp, vp]
+    L.btx_bucket_unpack.restype = i32
+    L.btx_bucket_unpack.argtypes = [ctypes.POINTER(BucketItem), i32, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -575,9 +575,26 @@ class GraphedTrainStep:
     `out`, the single word and the default loss above.  Consequences: training BatchNorm sees n forwards per step (running_* and
     num_batches_tracked advance n times, as in the reference's loop); n sets of saved activations live until the backward (no
     recomputation).  Models that hold a Bayesian LSTM are refused for n > 1 (its time steps consume the indices s + t, which would
-    collide with the passes')."""
+    collide with the passes').
 
-    def __init__(self, model, x, target, loss_fn=None, warmup=2, optimizer=None, num_mc=1):
+    group = a process group (torch.distributed.group.WORLD for the default one; None, the default, changes nothing even when
+    torch.distributed is initialised): data-parallel training, one process per GPU, parallel.GradReducer as `step.reducer`
+    (DESIGN.md §17).  Construction broadcasts rank 0's parameters and buffers (broadcast=False: skip it).  The default losses divide
+    the KL by `step.global_batch` = batch * world, so each rank's loss is CE(local shard) + KL / B_global; a custom loss_fn does that
+    scaling itself.  The step is TWO graphs with the eager collective between them:
+
+        graph A   forward, loss, backward, staging copies, btx_bucket_pack of every gradient and the loss (x f32(1 / world))
+        eager     ONE all_reduce(SUM) of the bucket on the replay stream
+        graph B   the captured optimizer, every item's gradient pointing at its slice of the bucket (the norm of max_grad_norm too:
+                  the REDUCED gradient is clipped)
+
+    run(step) writes the sample words (step * world + rank) * num_mc + k and returns the mean loss over the ranks (a view of the
+    bucket's last word).  With an optimizer, p.grad keeps this rank's LOCAL gradient and step.reducer.grad_view(p) is the reduced
+    one; with optimizer=None run() unpacks the bucket into p.grad (btx_bucket_unpack) so that a torch.optim step can follow.
+    forward_backward(step) and apply() are the two halves of run() on either side of the collective.  `group` may also be a
+    ready GradReducer (one built with rank= / world=: several ranks played in one process)."""
+
+    def __init__(self, model, x, target, loss_fn=None, warmup=2, optimizer=None, num_mc=1, group=None, broadcast=True):
         from .models.dnn_to_bnn import get_kl_loss
         from . import optim as _optim
         if not x.is_cuda:
@@ -593,6 +610,19 @@ class GraphedTrainStep:
         self.optimizer, self._plan = optimizer, None
         self.model, self.x, self.target = model, x, target
         bs = x.shape[0]
+        self.reducer, self.graph_b = None, None
+        if group is not None:
+            from .parallel import GradReducer
+            self.reducer = group if isinstance(group, GradReducer) else GradReducer(model, group=group, broadcast=broadcast)
+        world = 1 if self.reducer is None else self.reducer.world
+        self.global_batch = bs * world
+        if loss_fn is None and world > 1:  # (world == 1 keeps the expressions below: the same graph, bit for bit)
+            if self.num_mc > 1:
+                from .utils.mc_loss import mc_elbo_loss
+                loss_fn = lambda out, tgt: mc_elbo_loss(out, tgt, kl=get_kl_loss(model) / world, reduce="logits")  # noqa: E731
+            else:
+                B = self.global_batch
+                loss_fn = lambda out, tgt: torch.nn.functional.cross_entropy(out.float(), tgt) + get_kl_loss(model) / B  # noqa: E731
         if loss_fn is None and self.num_mc > 1:
             from .utils.mc_loss import mc_elbo_loss
             loss_fn = lambda out, tgt: mc_elbo_loss(out, tgt, kl=get_kl_loss(model), reduce="logits")  # noqa: E731
@@ -610,26 +640,43 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup) + 1):
-                self._step()
+                warm_loss = self._step()
+            if self.reducer is not None:   # both bucket kernels once, and the reducer's staging tensors allocated
+                self.reducer.pack(warm_loss)
+                self.reducer.unpack()
             if optimizer is not None:
                 optimizer._warm(dev)   # every update kernel once, on scratch tensors: the model is not touched
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         if optimizer is not None:
             with torch.no_grad():
-                optimizer._plan()      # state, staging buffers, device blocks and the norm workspace exist before the capture
+                # state, staging buffers, device blocks and the norm workspace exist before the capture
+                optimizer._plan(self._bucket_grads())
         for p_ in model.parameters():
             p_.grad = None
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             self.loss = self._step()
-            if optimizer is not None:
+            if self.reducer is not None:
+                self.reducer.pack(self.loss)
+            elif optimizer is not None:
                 with torch.no_grad():
                     self._plan = optimizer._plan()   # the item tables of THIS capture's gradient tensors
                     optimizer._launch(self._plan)
+        if self.reducer is not None and optimizer is not None:
+            self.graph_b = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph_b, capture_error_mode="thread_local"), torch.no_grad():
+                self._plan = optimizer._plan(self._bucket_grads())   # every gradient read from its slice of the reduced bucket
+                optimizer._launch(self._plan)
         # the graph writes its gradients into these pool tensors on every replay; `optimizer.zero_grad()` (set_to_none=True by
         # default) between replays detaches them from the parameters, so run() attaches them again
         self._grads = [(p_, p_.grad) for p_ in model.parameters() if p_.grad is not None]
+
+    def _bucket_grads(self):
+        """{parameter: its slice of the bucket} for the parameters that have a gradient; None without a group (p.grad is read)"""
+        if self.reducer is None:
+            return None
+        return {p_: self.reducer.grad_view(p_) for p_ in self.reducer.params if p_.grad is not None}
 
     def _step(self):
         for p_ in self.model.parameters():
@@ -653,7 +700,12 @@ class GraphedTrainStep:
         return out[0] if isinstance(out, tuple) else out
 
     def run(self, sample_idx):
-        """replay with MC sample index `sample_idx` (num_mc = n > 1: the step number; pass k draws sample step * n + k)"""
+        """replay with MC sample index `sample_idx` (num_mc = n > 1: the step number; pass k draws sample step * n + k).  With a group:
+        `sample_idx` is the step number, the same on every rank; returns the mean loss over the ranks."""
+        if self.reducer is not None:
+            self.forward_backward(sample_idx)
+            self.reducer.all_reduce()
+            return self.apply()
         if self.num_mc == 1:
             self.sample_dev.fill_(int(sample_idx) & 0x7FFFFFFF)
         else:
@@ -669,6 +721,32 @@ class GraphedTrainStep:
         if self._plan is not None:
             self.optimizer._finish(self._plan)       # the replay wrote the parameters through raw pointers: bump their versions
         return self.loss
+
+    def forward_backward(self, step):
+        """group= only, the first half of run(): sample words, the optimizer's host side, graph A (the bucket then holds this rank's
+        gradients and loss times f32(1 / world))"""
+        r, n = self.reducer, self.num_mc
+        if n == 1:
+            self.sample_dev.fill_(r.sample_index(step))
+        else:
+            self.sample_dev.copy_(torch.tensor([r.sample_index(step, k, n) for k in range(n)], dtype=torch.int32))
+        if self._plan is not None:
+            with torch.no_grad():
+                self.optimizer._advance(self._plan)
+        self.graph.replay()
+        for p_, g_ in self._grads:
+            if p_.grad is not g_:
+                p_.grad = g_
+
+    def apply(self):
+        """group= only, the second half of run(), after the bucket has been summed over the ranks: graph B (the update from the
+        bucket), or without an optimizer the bucket unpacked into p.grad; returns the mean loss"""
+        if self._plan is not None:
+            self.graph_b.replay()
+            self.optimizer._finish(self._plan)
+        else:
+            self.reducer.unpack()
+        return self.reducer.loss
 
     def close(self):
         for m in self._layers:

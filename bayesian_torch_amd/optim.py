@@ -91,15 +91,17 @@ class _BtxOptimizer(torch.optim.Optimizer):
         if isinstance(group["lr"], torch.Tensor):
             raise ValueError("lr: a tensor-valued lr is not supported (the host writes lr into the device block at every step)")
 
-    def _plan(self):
-        """state allocation, gradient staging buffers and the item tables of one step (no launch, no state change)"""
+    def _plan(self, grads=None):
+        """state allocation, gradient staging buffers and the item tables of one step (no launch, no state change).  grads: a mapping
+        {parameter: gradient tensor} read in place of p.grad (autograd.GraphedTrainStep(group=): the slices of the reduced bucket);
+        a parameter it does not hold is skipped"""
         plan = _Plan()
         plan.buckets, plan.cpu, plan.dev, plan.updated, plan.stages = [], [], None, [], []
         for group in self.param_groups:
             self._check_group(group)
             by_key = {}
             for p in group["params"]:
-                g = p.grad
+                g = p.grad if grads is None else grads.get(p)
                 if g is None or p.numel() == 0:
                     continue
                 if g.is_sparse:

@@ -750,6 +750,29 @@ size_t btx_bias_grad_workspace_bytes(int64_t M, int N);
 int btx_bias_grad(int kind, const void* dy, int64_t M, int N, int act_dtype, float* db_mu, float* db_delta, const BtxRng* rng,
                   const int8_t* sign_out, uint32_t flags, void* ws, size_t ws_bytes, void* stream);
 
+/* K14 (ABI 9, additive): the gradient bucket of data-parallel training.  Every gradient of a step (and the loss
+ * word) is scaled into ONE flat f32 buffer, the operand of the step's single all-reduce, and copied back out of it.  f32 only.
+ * BtxBucketItem (HOST array): n elements at src, walked flat, and their place in the bucket, bucket + offset (in elements).  The
+ *   caller lays the bucket out (parallel.GradReducer rounds every offset up to a multiple of 4 so that 16-byte aligned tensors
+ *   keep 16-byte accesses); the slices must not overlap.  Items with n == 0 are skipped.
+ * btx_bucket_pack:   bucket[offset + i] = src[i] * scale, ONE f32 multiply rounded once (the unit is built with -ffp-contract=off).
+ * btx_bucket_unpack: src[i] = bucket[offset + i], a plain copy.  It WRITES the memory src points to: the field is const because pack,
+ *   the common direction, only reads it, and unpack casts the qualifier away.
+ * The library folds the items into by-value kernel-argument tables of at most 48 per launch; a workgroup owns one chunk of
+ *   BTX_OPTIM_CHUNK elements of one item.  16-byte accesses when src and bucket + offset are both 16-byte aligned, scalar ones
+ *   otherwise: any 4-byte aligned tensor is valid.  Words of the bucket outside the items' slices are never written.
+ * Every launch is capturable (no allocation, no sync, no host read).  Errors, all before anything is launched: BTX_E_NULL (bucket,
+ *   items, the src of a non-empty item), BTX_E_SHAPE (n_items < 0, n < 0, offset < 0), BTX_E_UNSUPPORTED (more than
+ *   BTX_OPTIM_MAX_ITEMS items, an item of more than (2^31 - 1) * BTX_OPTIM_CHUNK elements), BTX_E_ALIGN (src or bucket not 4-byte
+ *   aligned).  n_items == 0 (or only empty items) launches nothing and returns 0. */
+typedef struct BtxBucketItem {
+  const float* src;
+  int64_t offset;
+  int64_t n;
+} BtxBucketItem;
+int btx_bucket_pack(const BtxBucketItem* items, int n_items, float scale, float* bucket, void* stream);
+int btx_bucket_unpack(const BtxBucketItem* items, int n_items, const float* bucket, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
