@@ -137,7 +137,10 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_optim_sgd", "btx_optim_adam", "btx_optim_grad_norm_workspace_bytes", "btx_optim_grad_norm",
            "btx_mcloss_workspace_bytes", "btx_mc_ce_fwd", "btx_mc_ce_bwd", "btx_avu_mc_fwd", "btx_avu_mc_bwd",
            "btx_bias_grad_workspace_bytes", "btx_bias_grad",
-           "btx_bucket_pack", "btx_bucket_unpack")
+           "btx_bucket_pack", "btx_bucket_unpack",
+           "btx_mc_eval_state_doubles", "btx_mc_eval_workspace_bytes", "btx_mc_eval")
+MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
+MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 
 
 def lib_path():
@@ -308,6 +311,12 @@ def lib():
     L.btx_bucket_pack.argtypes = [ctypes.POINTER(BucketItem), i32, f32, vp, vp]
     L.btx_bucket_unpack.restype = i32
     L.btx_bucket_unpack.argtypes = [ctypes.POINTER(BucketItem), i32, vp, vp]
+    L.btx_mc_eval_state_doubles.restype = sz
+    L.btx_mc_eval_state_doubles.argtypes = [i32, i32]
+    L.btx_mc_eval_workspace_bytes.restype = sz
+    L.btx_mc_eval_workspace_bytes.argtypes = [i32]
+    L.btx_mc_eval.restype = i32
+    L.btx_mc_eval.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, sz, vp, ctypes.c_int64, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -389,3 +389,352 @@ class GraphedMC:
                 m.__dict__.pop("_btx_static_x", None)
         self._static_packs.clear()  # only this graph's buffers: sibling graphs keep theirs
         self._tiles = {}
+
+
+# ---- evaluation head: BTX-EVAL v1 ---------------------------------------------------------------------------
+# What the reference's validate() / evaluate() (examples/main_bayesian_imagenet.py:549-642) and utils/avuc_loss.py:392-443 compute
+# on the host, kept on the device: update() folds a batch into a float64 state, compute() reads it once.
+EVAL_HEADER, EVAL_CURSOR, EVAL_DROPPED = _lib.MC_EVAL_HEADER, _lib.MC_EVAL_CURSOR, _lib.MC_EVAL_DROPPED
+EVAL_RECORD = ("pred", "rank", "conf", "p_y", "nll", "brier", "entropy", "mutual_information")
+_EVAL_ROW_THREADS = 256
+
+
+def _logf32(x):
+    """the model's logf: log in float64 rounded once to f32 (the correctly rounded value, whatever the host's f32 log is)"""
+    return torch.log(x.double()).float()
+
+
+def _row_sum32(terms):
+    """f32 sum over the last axis in the kernel's shape: 256 strided partials, a butterfly per wave, (w0 + w1) + (w2 + w3)"""
+    bs, C = terms.shape
+    k = -(-C // _EVAL_ROW_THREADS)
+    pad = terms.new_zeros(bs, k * _EVAL_ROW_THREADS)
+    pad[:, :C] = terms
+    w = pad.view(bs, k, _EVAL_ROW_THREADS)
+    acc = terms.new_zeros(bs, _EVAL_ROW_THREADS)
+    for j in range(k):
+        acc = acc + w[:, j]
+    acc = acc.view(bs, 4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc[..., :off] + acc[..., off:2 * off]
+    acc = acc[..., 0]
+    return (acc[:, 0] + acc[:, 1]) + (acc[:, 2] + acc[:, 3])
+
+
+def _fold_sum64(v):
+    """float64 sum over the last axis (rows of the batch) in the fold's shape: 64 strided partials and a butterfly"""
+    q, n = v.shape
+    k = -(-n // 64)
+    pad = v.new_zeros(q, k * 64)
+    pad[:, :n] = v
+    w = pad.view(q, k, 64)
+    acc = v.new_zeros(q, 64)
+    for j in range(k):
+        acc = acc + w[:, j]
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc[:, :off] + acc[:, off:2 * off]
+    return acc[:, 0]
+
+
+def _eval_rows_torch(packed, labels, bs, C):
+    """the records [bs, 8] of BTX-EVAL v1 with torch ops in f32 on the tensor's own device"""
+    packed = packed.float()
+    eps = torch.tensor(1e-15, dtype=torch.float32, device=packed.device)
+    zero = torch.zeros((), dtype=torch.float32, device=packed.device)
+    sum_p = packed[:bs * C].view(bs, C)
+    n = packed[2 * bs * C + bs + 1]
+    y = labels.reshape(bs).long()
+    valid = (y >= 0) & (y < C)
+    yi = torch.where(valid, y, torch.full_like(y, -1))
+    p = sum_p / n
+    pred = p.argmax(1)  # the first of equal maxima
+    conf = p.gather(1, pred[:, None])[:, 0]
+    py = torch.where(valid, p.gather(1, yi.clamp_min(0)[:, None])[:, 0], zero)
+    c = torch.arange(C, device=packed.device)[None, :]
+    rank = ((p > py[:, None]) | ((p == py[:, None]) & (c < yi[:, None]))).sum(1)
+    H = -_row_sum32(p * _logf32(p + eps))
+    d = p - (c == yi[:, None]).float()
+    brier = _row_sum32(d * d)
+    MI = H - packed[2 * bs * C:2 * bs * C + bs] / n
+    rec = packed.new_zeros(bs, 8)
+    rec[:, 0] = pred.float()
+    rec[:, 1] = torch.where(valid, rank, torch.full_like(rank, -1)).float()
+    rec[:, 2] = conf
+    rec[:, 3] = py
+    rec[:, 4] = torch.where(valid, -_logf32(py + eps), zero)
+    rec[:, 5] = torch.where(valid, brier, zero)
+    rec[:, 6] = H
+    rec[:, 7] = MI
+    return rec
+
+
+def _eval_fold_torch(state, rec, topk, nbins, th, use_mi, capacity):
+    """state += the batch of records rec [bs, 8], in the fold kernel's order (in place)"""
+    bs = rec.shape[0]
+    T = 0 if th is None else th.numel()
+    rank, conf32 = rec[:, 1], rec[:, 2]
+    valid, hit = rank >= 0, rank == 0
+    u32 = rec[:, 7] if use_mi else rec[:, 6]
+    u = u32.double()
+    z = u.new_zeros(bs)
+    rows = [valid, ~valid, hit, valid & (rank < float(topk))]
+    rows += [torch.where(valid, rec[:, j].double(), z) for j in (4, 5, 6, 7, 2)]
+    rows += [torch.where(hit, u, z), torch.where(valid & ~hit, u, z)]
+    b = (torch.ceil(conf32 * torch.tensor(float(nbins), dtype=torch.float32, device=rec.device)).long() - 1).clamp(0, nbins - 1)
+    for k in range(nbins):
+        m = valid & (b == k)
+        rows += [m, torch.where(m, conf32.double(), z), m & hit]
+    for t in range(T):
+        cert = u32 <= th[t]
+        rows += [valid & hit & cert, valid & hit & ~cert, valid & ~hit & cert, valid & ~hit & ~cert]
+    s = _fold_sum64(torch.stack([r.double() for r in rows]))
+    state[:11] += s[:11]
+    state[EVAL_HEADER:EVAL_HEADER + 3 * nbins + 4 * T] += s[11:]
+    cur = state[EVAL_CURSOR].clone()
+    state[EVAL_DROPPED] += (cur + bs - capacity).clamp(0.0, float(bs))
+    state[EVAL_CURSOR] = cur + bs
+    return state
+
+
+class Evaluator:
+    """Classification metrics of MC predictions, accumulated on the device (BTX-EVAL v1).
+
+        ev = Evaluator(1000, thresholds=[0.5, 1.0], capacity=50000)
+        for x, y in loader:
+            ev.update(mc_forward(model, x, 20), y)         # no host read; on the GPU two launches, capturable
+        print(ev.compute())                                # the one host read
+
+    update() takes the packed statistics of a batch (mc_forward / GraphedMC.packed) and int64 labels [bs].  A label outside
+    [0, num_classes) — ignore_index by default, and every other out-of-range value alike — marks an ignored row, which adds
+    nothing: pad a ragged last batch with them.  The state is a float64 vector (layout: include/btx.h K15); the per-example
+    records [pred, rank, conf, p_y, nll, brier, H, MI] of the first `capacity` rows are kept in a device buffer, the rest is
+    counted in `dropped`.  The thresholds live in a device tensor (`th`) that set_thresholds() rewrites in place, so a captured
+    update sees the new values."""
+
+    def __init__(self, num_classes, bins=15, topk=5, thresholds=None, uncertainty="entropy", capacity=0, ignore_index=-100,
+                 device=None):
+        if uncertainty not in ("entropy", "mi"):
+            raise ValueError("uncertainty must be 'entropy' or 'mi'")
+        if not 1 <= int(bins) <= _lib.MC_EVAL_MAX_BINS:
+            raise ValueError("bins must be in 1..%d" % _lib.MC_EVAL_MAX_BINS)
+        self.num_classes, self.bins, self.topk = int(num_classes), int(bins), int(topk)
+        if self.num_classes < 1 or self.topk < 1:
+            raise ValueError("num_classes and topk must be positive")
+        if 0 <= int(ignore_index) < self.num_classes:
+            raise ValueError("ignore_index must not be a class index")
+        self.use_mi, self.uncertainty, self.ignore_index = uncertainty == "mi", uncertainty, int(ignore_index)
+        th = [] if thresholds is None else [float(t) for t in torch.as_tensor(thresholds).reshape(-1).tolist()]
+        if len(th) > _lib.MC_EVAL_MAX_THRESHOLDS:
+            raise ValueError("at most %d thresholds" % _lib.MC_EVAL_MAX_THRESHOLDS)
+        self.T, self._th_init, self.capacity = len(th), th, int(capacity)
+        self.device = None
+        self.state = self.th = self.records_buffer = self.workspace = self._scratch = None
+        if device is not None:
+            self._alloc(torch.device(device))
+
+    def _alloc(self, dev):
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.state = torch.zeros(EVAL_HEADER + 3 * self.bins + 4 * self.T, dtype=torch.float64, device=dev)
+        self.th = torch.tensor(self._th_init, dtype=torch.float32, device=dev)
+        if self.capacity:
+            self.records_buffer = torch.zeros(self.capacity, 8, dtype=torch.float32, device=dev)
+
+    def set_thresholds(self, thresholds):
+        """rewrite the thresholds in place (same count): a captured update() reads the new values"""
+        self.th.copy_(torch.as_tensor(thresholds, dtype=torch.float32).reshape(-1))
+
+    def reserve(self, rows):
+        """grow the record buffer to hold at least `rows` records (a new allocation: not for use between replays of a captured
+        update)"""
+        rows = int(rows)
+        if rows <= self.capacity:
+            return
+        new = max(rows, 2 * self.capacity)
+        if self.device is not None:
+            buf = torch.zeros(new, 8, dtype=torch.float32, device=self.device)
+            if self.records_buffer is not None:
+                buf[:self.capacity] = self.records_buffer
+            self.records_buffer = buf
+        self.capacity = new
+
+    def update(self, packed, labels):
+        """fold one batch: packed [2 * bs * C + bs + 2] f32 and labels [bs] int64, on one device.  GPU: btx_mc_eval, two launches
+        on the current stream, capturable in torch.cuda.graph.  Rows the kernel does not take (C > _lib.MC_EVAL_MAX_CLASSES, a
+        packed vector that is not f32) and CPU tensors run the same arithmetic with torch ops."""
+        if self.device is None:
+            self._alloc(packed.device)
+        bs, C = labels.numel(), self.num_classes
+        if packed.device != self.device:
+            raise ValueError("packed is on %s, the evaluator's state on %s" % (packed.device, self.device))
+        if packed.numel() != packed_numel(bs, C):
+            raise ValueError("packed has %d elements, expected %d for bs %d, C %d" % (packed.numel(), packed_numel(bs, C), bs, C))
+        if packed.is_cuda and C <= _lib.MC_EVAL_MAX_CLASSES and packed.dtype == torch.float32:
+            pk = packed.contiguous()
+            lb = labels.reshape(bs).to(device=packed.device, dtype=torch.int64).contiguous()  # the kernel reads device memory
+            L = _lib.lib()
+            need = L.btx_mc_eval_workspace_bytes(bs)
+            if self.workspace is None or self.workspace.numel() * 4 < need:
+                self.workspace = torch.empty(need // 4, dtype=torch.float32, device=self.device)
+            rec = self.records_buffer
+            _lib.check(L.btx_mc_eval(pk.data_ptr(), lb.data_ptr(), bs, C, self.topk, self.bins, self.th.data_ptr() if self.T else None,
+                                     self.T, int(self.use_mi), self.state.data_ptr(), self.state.numel(),
+                                     rec.data_ptr() if rec is not None else None, rec.shape[0] if rec is not None else 0,
+                                     self.workspace.data_ptr(), self.workspace.numel() * 4,
+                                     torch.cuda.current_stream(self.device).cuda_stream))
+            return self
+        rec = _eval_rows_torch(packed, labels.to(packed.device), bs, C)
+        cap = 0 if self.records_buffer is None else self.records_buffer.shape[0]
+        if cap:
+            at = self.state[EVAL_CURSOR].long() + torch.arange(bs, device=rec.device)
+            keep = at < cap
+            self.records_buffer[at[keep]] = rec[keep]
+        _eval_fold_torch(self.state, rec, self.topk, self.bins, self.th, self.use_mi, cap)
+        return self
+
+    def update_logits(self, logits, labels):
+        """one deterministic (or single-sample) forward, the reference's validate() form: the logits are accumulated into a
+        zeroed scratch packed vector (accumulate: softmax and entropy of ONE sample), then update()"""
+        bs, C = logits.shape
+        n = packed_numel(bs, C)
+        if self._scratch is None or self._scratch.numel() != n or self._scratch.device != logits.device:
+            self._scratch = torch.zeros(n, dtype=torch.float32, device=logits.device)
+        self._scratch.zero_()
+        accumulate(self._scratch, logits)
+        return self.update(self._scratch, labels)
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+        return self
+
+    def _add_state(self, other_state):
+        keep = self.state[EVAL_CURSOR:EVAL_DROPPED + 1].clone()
+        self.state += other_state
+        self.state[EVAL_CURSOR:EVAL_DROPPED + 1] = keep
+
+    def merge(self, other):
+        """add another evaluator's state (same classes / bins / thresholds).  The record cursor, the dropped count and the
+        records themselves stay this evaluator's own."""
+        if (other.num_classes, other.bins, other.T, other.use_mi, other.topk) != (self.num_classes, self.bins, self.T, self.use_mi,
+                                                                                 self.topk):
+            raise ValueError("merge of evaluators with different settings")
+        if other.state is None:
+            return self
+        if self.device is None:
+            self._alloc(other.device)
+        self._add_state(other.state.to(self.device))
+        return self
+
+    def reduce(self, group=None):
+        """ONE float64 all_reduce(SUM) of the state over `group`, for a validation set sharded over ranks: afterwards every
+        rank's compute() is that of the whole set.  The records stay local — each rank keeps the examples it saw, with its own
+        cursor and dropped count; nothing gathers them."""
+        if dist.is_available() and dist.is_initialized():
+            keep = self.state[EVAL_CURSOR:EVAL_DROPPED + 1].clone()
+            dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+            self.state[EVAL_CURSOR:EVAL_DROPPED + 1] = keep
+        return self
+
+    def compute(self):
+        """-> dict of the metrics; the one host read (the state vector)"""
+        import numpy as np
+        if self.state is None:
+            raise ValueError("compute() before the first update()")
+        s = self.state.cpu().numpy()
+        n = s[0]
+        d = n if n > 0 else 1.0
+        bins = s[EVAL_HEADER:EVAL_HEADER + 3 * self.bins].reshape(self.bins, 3).copy()
+        quad = s[EVAL_HEADER + 3 * self.bins:].reshape(self.T, 4).copy()
+        gap = np.abs(bins[:, 2] - bins[:, 1])
+        filled = bins[:, 0] > 0
+        qs = quad.sum(1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            hits = s[2]
+            out = {"n": int(n), "ignored": int(s[1]), "top1": s[2] / d, "topk": s[3] / d, "nll": s[4] / d, "brier": s[5] / d,
+                   "ece": float(gap.sum() / d), "mce": float((gap[filled] / bins[filled, 0]).max()) if filled.any() else 0.0,
+                   "mean_entropy": s[6] / d, "mean_mi": s[7] / d, "mean_conf": s[8] / d,
+                   "mean_u_correct": s[9] / hits if hits > 0 else float("nan"),
+                   "mean_u_incorrect": s[10] / (n - hits) if n - hits > 0 else float("nan"),
+                   "avu": np.where(qs > 0, (quad[:, 0] + quad[:, 3]) / np.where(qs > 0, qs, 1.0), np.nan),
+                   "quadrants": quad.astype(np.int64), "bins": bins, "dropped": int(s[EVAL_DROPPED])}
+        return {k: (float(v) if isinstance(v, np.floating) else v) for k, v in out.items()}
+
+    def records(self):
+        """-> dict of numpy arrays [N] over the kept rows, ignored rows left out: pred, rank (int64), correct (bool), conf, p_y,
+        nll, brier, entropy, mutual_information (float32), and target (int64): pred where the row is correct, -1 elsewhere — the
+        label itself is not kept, and utils.avuc_loss.eval_avu(r["pred"], r["target"], r["entropy"]) / accuracy_vs_uncertainty only
+        compare it with pred."""
+        import numpy as np
+        if self.state is None or self.records_buffer is None:
+            rec = np.zeros((0, 8), np.float32)
+        else:
+            kept = min(int(self.state[EVAL_CURSOR].item()), self.records_buffer.shape[0])
+            rec = self.records_buffer[:kept].cpu().numpy()
+        rec = rec[rec[:, 1] >= 0]
+        out = {name: rec[:, j].copy() for j, name in enumerate(EVAL_RECORD)}
+        out["pred"], out["rank"] = out["pred"].astype(np.int64), out["rank"].astype(np.int64)
+        out["correct"] = out["rank"] == 0
+        out["target"] = np.where(out["correct"], out["pred"], -1)
+        return out
+
+
+@torch.no_grad()
+def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0, evaluator=None, group=None):
+    """The reference's evaluate() loop (examples/main_bayesian_imagenet.py:598-642): `num_samples` MC forwards of every batch of
+    `batches` (an iterable of (x, y)), mean probabilities, argmax, accuracy — and everything else Evaluator accumulates — with no
+    host read inside the loop.  Returns the evaluator; call compute() / records() on it.
+
+    graphed (default: on for GPU batches): ONE GraphedMC is captured on the first batch; per batch its packed vector is zeroed,
+    set_input() copies the batch in, the samples run `lanes` per replay (num_samples must be a multiple of lanes) and update()
+    folds the result.  A ragged last batch is padded to the captured shape with zeros and ignore_index labels.  Otherwise:
+    mc_forward + update per batch.  Every rank runs all samples of ITS batches (the validation set, not the samples, is what is
+    sharded here); with `group` the states are summed at the end by Evaluator.reduce(group).
+    evaluator=None: one is built on the first batch that keeps per-example records, its buffer grown between the batches."""
+    ev, grow, g, seen = evaluator, evaluator is None, None, 0
+    lanes = max(1, int(lanes))
+    try:
+        for x, y in batches:
+            use_graph = x.is_cuda if graphed is None else bool(graphed)
+            if use_graph and not x.is_cuda:
+                raise ValueError("graphed evaluation needs CUDA (ROCm) tensors")
+            lane_n = lanes if x.is_cuda else 1
+            if use_graph:
+                if num_samples % lane_n:
+                    raise ValueError("num_samples must be a multiple of lanes for graphed evaluation")
+                if g is None:
+                    g = GraphedMC(model, x.clone(), lanes=lane_n, static_input=True)
+                bs = g.x.shape[0]
+                if x.shape[0] > bs or x.shape[1:] != g.x.shape[1:]:
+                    raise ValueError("a batch larger than the first (captured) batch")
+                if x.shape[0] < bs:
+                    xp = torch.zeros_like(g.x)
+                    xp[:x.shape[0]] = x
+                    yp = torch.full((bs,), ev.ignore_index if ev is not None else -100, dtype=torch.int64, device=y.device)
+                    yp[:y.numel()] = y
+                    x, y = xp, yp
+                g.packed.zero_()
+                g.set_input(x)
+                for s0 in range(0, num_samples, lane_n):
+                    idx = [sample_offset + s for s in range(s0, s0 + lane_n)]
+                    if lane_n == 1:
+                        g.run(idx[0])
+                    else:
+                        g.run_many(idx)
+                packed = g.packed
+            else:
+                packed = mc_forward(model, x, num_samples, sample_offset=sample_offset, reduce=False, lanes=lane_n, rank=0, world=1)
+            bs = x.shape[0]
+            if ev is None:
+                ev = Evaluator((packed.numel() - 2 - bs) // (2 * bs), device=packed.device)
+            if grow:
+                seen += bs
+                ev.reserve(seen)
+            ev.update(packed, y.to(packed.device))
+    finally:
+        if g is not None:
+            g.close()
+    if ev is not None and group is not None:
+        ev.reduce(group)
+    return ev

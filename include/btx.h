@@ -773,6 +773,40 @@ typedef struct BtxBucketItem {
 int btx_bucket_pack(const BtxBucketItem* items, int n_items, float scale, float* bucket, void* stream);
 int btx_bucket_unpack(const BtxBucketItem* items, int n_items, const float* bucket, void* stream);
 
+/* K15 (ABI 9, additive; DESIGN.md §18, BTX-EVAL v1): evaluation of a batch from its packed MC statistics (K6) and its labels, on
+ * the device and without a host read — what examples/main_bayesian_imagenet.py:549-595 (validate: top-1 / top-5) and :598-642
+ * (evaluate: mean probabilities, argmax, accuracy) do on the host, with the entropy / mutual information of utils/util.py:41-60
+ * and the quadrant counts of utils/avuc_loss.py:392-443 (eval_avu / accuracy_vs_uncertainty, a Python loop per example).
+ * Per row (f32, every operation rounded once, sums of a shape fixed by C): p = sum_p / n, pred = lowest index of the largest p,
+ *   conf = p[pred]; a row is valid iff 0 <= label < C (every other label is ignored and adds nothing);
+ *   rank = #{c : p_c > p_y} + #{c < y : p_c == p_y}; nll = -logf(p_y + 1e-15f); brier = sum_c (p_c - [c == y])^2;
+ *   H = -sum_c p_c logf(p_c + 1e-15f); MI = H - sum_H / n.
+ * The row's record [pred, rank, conf, p_y, nll, brier, H, MI] (rank = -1, p_y = nll = brier = 0 when ignored) goes to the workspace
+ *   and, when records != NULL, to records[cursor + row] for cursor + row < capacity (cursor: the state word below).
+ * state (float64, accumulated in place: zero it to reset; add two states to merge them):
+ *   [0] valid rows  [1] ignored rows  [2] top-1 hits  [3] top-k hits (rank < topk)  [4] sum nll  [5] sum brier  [6] sum H
+ *   [7] sum MI  [8] sum conf  [9] sum u over correct rows  [10] sum u over incorrect rows  (u = H, or MI when use_mi)
+ *   [BTX_MC_EVAL_CURSOR] rows seen (advanced by bs per call)  [BTX_MC_EVAL_DROPPED] rows whose record did not fit  [13..15] spare
+ *   [BTX_MC_EVAL_HEADER + 3 b ..] ECE bin b of nbins, b = clamp((int)ceilf(conf * nbins) - 1, 0, nbins - 1): rows, sum conf, top-1 hits
+ *   [BTX_MC_EVAL_HEADER + 3 nbins + 4 t ..] threshold t of T: n_ac, n_au, n_ic, n_iu with certain <=> u <= th[t]
+ *   th is DEVICE memory, read by the launch.  Sums are taken in double in an order fixed by bs alone: no atomics.
+ * Nothing varies per batch but the tensors' contents, so a captured call can be replayed.  Any 4-byte aligned packed / th /
+ *   records / ws and 8-byte aligned labels / state are valid (element-wise accesses).
+ * Errors, all before anything is launched: BTX_E_NULL (packed, labels, state, ws; th with T > 0; records with capacity > 0),
+ *   BTX_E_SHAPE (bs, C, topk < 1, nbins outside 1..BTX_MC_EVAL_MAX_BINS, T outside 0..BTX_MC_EVAL_MAX_THRESHOLDS, capacity < 0,
+ *   use_mi not 0 or 1), BTX_E_UNSUPPORTED (C > BTX_MC_EVAL_MAX_CLASSES: the Python face uses torch ops on the device),
+ *   BTX_E_WORKSPACE (ws_bytes, state_doubles below the two helpers), BTX_E_ALIGN (below the element type's alignment). */
+#define BTX_MC_EVAL_MAX_CLASSES 24575   /* the K6 limit: what the accumulate kernels pack, this head evaluates */
+#define BTX_MC_EVAL_MAX_BINS 64
+#define BTX_MC_EVAL_MAX_THRESHOLDS 32
+#define BTX_MC_EVAL_HEADER 16
+#define BTX_MC_EVAL_CURSOR 11
+#define BTX_MC_EVAL_DROPPED 12
+size_t btx_mc_eval_state_doubles(int nbins, int T);   /* 0 for nbins / T out of range */
+size_t btx_mc_eval_workspace_bytes(int bs);
+int btx_mc_eval(const float* packed, const int64_t* labels, int bs, int C, int topk, int nbins, const float* th, int T, int use_mi,
+                double* state, size_t state_doubles, float* records, int64_t capacity, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
