@@ -138,9 +138,13 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_mcloss_workspace_bytes", "btx_mc_ce_fwd", "btx_mc_ce_bwd", "btx_avu_mc_fwd", "btx_avu_mc_bwd",
            "btx_bias_grad_workspace_bytes", "btx_bias_grad",
            "btx_bucket_pack", "btx_bucket_unpack",
-           "btx_mc_eval_state_doubles", "btx_mc_eval_workspace_bytes", "btx_mc_eval")
+           "btx_mc_eval_state_doubles", "btx_mc_eval_workspace_bytes", "btx_mc_eval",
+           "btx_mc_moments_lanes", "btx_mc_gnll_workspace_bytes", "btx_mc_gnll_fwd", "btx_mc_gnll_bwd",
+           "btx_reg_eval_workspace_bytes", "btx_reg_eval_update")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
+REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
+REG_CHUNK = 4096
 
 
 def lib_path():
@@ -317,6 +321,19 @@ def lib():
     L.btx_mc_eval_workspace_bytes.argtypes = [i32]
     L.btx_mc_eval.restype = i32
     L.btx_mc_eval.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, sz, vp, ctypes.c_int64, vp, sz, vp]
+    f64 = ctypes.c_double
+    L.btx_mc_moments_lanes.restype = i32
+    L.btx_mc_moments_lanes.argtypes = [vp, i32, i32, i32, i32, i32, f64, vp, vp]
+    L.btx_mc_gnll_workspace_bytes.restype = sz
+    L.btx_mc_gnll_workspace_bytes.argtypes = [i32, i32]
+    L.btx_mc_gnll_fwd.restype = i32
+    L.btx_mc_gnll_fwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, sz, vp]
+    L.btx_mc_gnll_bwd.restype = i32
+    L.btx_mc_gnll_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp]
+    L.btx_reg_eval_workspace_bytes.restype = sz
+    L.btx_reg_eval_workspace_bytes.argtypes = [i32, i32]
+    L.btx_reg_eval_update.restype = i32
+    L.btx_reg_eval_update.argtypes = [vp, vp, i32, i32, f64, f64, vp, i32, vp, sz, vp, ctypes.c_int64, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -88,14 +88,111 @@ def unpack(packed, bs, num_classes):
             "mutual_information": pred_h - mean_h, "kl": packed[2 * bs * C + bs] / n, "samples": n}
 
 
+class _SoftmaxStats:
+    """the classification statistics above behind the interface the drivers use (`stats=None`): the same functions, f32"""
+    dtype = torch.float32
+
+    @staticmethod
+    def numel(bs, width):
+        return packed_numel(bs, width)
+
+    @staticmethod
+    def accumulate(packed, out, kl=0.0):
+        return accumulate(packed, out, kl)
+
+    @staticmethod
+    def accumulate_lanes(packed, out, lanes, kl=0.0):
+        return accumulate_lanes(packed, out, lanes, kl)
+
+
+_SOFTMAX = _SoftmaxStats()
+
+
+class GaussianStats:
+    """MC moment statistics of a model that predicts real values (BTX-REG v1) — pass as `stats=` to mc_forward,
+    mc_forward_batched, GraphedMC and evaluate.
+
+    variance="log": the output is [rows, 2 D], columns [0, D) the mean m and [D, 2 D) the log-variance s (Kendall & Gal);
+    variance=None: [rows, D], the mean alone.  The packed vector is FLOAT64, 3 N + 2 words with N = bs * D:
+        [ N sum_s m | N sum_s m^2 | N sum_s v | sum_s KL | number of samples ],  v = (double)expf(s), m^2 the exact f64 product
+    (the third block stays zero with variance=None).  float64 because E[m^2] - E[m]^2 cancels in f32 for un-standardised targets.
+    GPU tensors in f32 / bf16: btx_mc_moments_lanes, ONE element-wise launch for all lanes, equal to one call per sample bit for
+    bit.  CPU tensors and other dtypes: the same arithmetic with torch ops in float64 (expf: exp in float64 rounded to f32)."""
+    dtype = torch.float64
+
+    def __init__(self, variance="log"):
+        if variance not in ("log", None):
+            raise ValueError("variance must be 'log' or None, got %r" % (variance,))
+        self.variance = variance
+
+    def dims(self, width):
+        """D of an output of `width` columns"""
+        width = int(width)
+        if self.variance == "log":
+            if width < 2 or width % 2:
+                raise ValueError("variance='log' needs an even output width (mean | log-variance), got %d" % width)
+            return width // 2
+        if width < 1:
+            raise ValueError("empty output")
+        return width
+
+    def numel(self, bs, width):
+        return 3 * int(bs) * self.dims(width) + 2
+
+    def accumulate(self, packed, out, kl=0.0):
+        return self.accumulate_lanes(packed, out, 1, kl)
+
+    def accumulate_lanes(self, packed, out, lanes, kl=0.0):
+        """packed += the statistics of `lanes` MC samples whose outputs sit back to back along the batch axis ([lanes * bs, W])"""
+        lanes = int(lanes)
+        if out.dim() != 2 or lanes < 1 or out.shape[0] % lanes:
+            raise ValueError("out must be [lanes * bs, W]")
+        bs, W = out.shape[0] // lanes, out.shape[1]
+        D = self.dims(W)
+        N = bs * D
+        if packed.dtype != torch.float64 or packed.numel() != 3 * N + 2 or packed.device != out.device:
+            raise ValueError("packed must be a float64 vector of %d words on %s" % (3 * N + 2, out.device))
+        has_var = self.variance == "log"
+        if out.is_cuda and out.dtype in (torch.float32, torch.bfloat16) and packed.is_contiguous() and N <= 2 ** 31 - 3:
+            o = out.contiguous()
+            act = _lib.ACT_F32 if o.dtype == torch.float32 else _lib.ACT_BF16
+            _lib.check(_lib.lib().btx_mc_moments_lanes(o.data_ptr(), lanes, bs, D, int(has_var), act, float(kl), packed.data_ptr(),
+                                                       torch.cuda.current_stream(o.device).cuda_stream))
+            return packed
+        for k in range(lanes):
+            o = out[k * bs:(k + 1) * bs]
+            o = o if o.dtype == torch.float64 else o.float()  # what the kernel widens: the f32 value
+            m = o[:, :D].double().reshape(-1)
+            packed[:N] += m
+            packed[N:2 * N] += m * m
+            if has_var:
+                packed[2 * N:3 * N] += torch.exp(o[:, D:].double()).float().double().reshape(-1)
+            packed[3 * N] += float(kl)
+            packed[3 * N + 1] += 1.0
+        return packed
+
+    @staticmethod
+    def unpack(packed, bs):
+        """-> dict(mean, epistemic_var (clamped at 0), aleatoric_var, total_var [bs, D], kl, samples), float64"""
+        N = (packed.numel() - 2) // 3
+        D = N // int(bs)
+        n = packed[3 * N + 1]
+        mean = (packed[:N] / n).reshape(bs, D)
+        ep = ((packed[N:2 * N] / n).reshape(bs, D) - mean * mean).clamp_min(0)
+        al = (packed[2 * N:3 * N] / n).reshape(bs, D)
+        return {"mean": mean, "epistemic_var": ep, "aleatoric_var": al, "total_var": ep + al, "kl": packed[3 * N] / n, "samples": n}
+
+
 @torch.no_grad()
 def mc_forward(model, x, num_samples, sample_offset=0, with_kl=False, group=None, reduce=True, lanes=1, rank=None,
-               world=None):
+               world=None, stats=None):
     """Run `num_samples` MC forward passes of `model` on `x`, sharded over the ranks of `group` (or the default
     group when torch.distributed is initialised), and return the all-reduced packed statistics tensor.
     lanes > 1 (GPU): this rank evaluates its samples `lanes` at a time, one launch per layer for all of them
     (rng.set_sample_lanes) — the same numbers as one at a time.  rank / world: override the process group's (tests that
-    play several ranks in one process, with reduce=False)."""
+    play several ranks in one process, with reduce=False).  stats: None — the softmax statistics above (f32) — or a GaussianStats
+    (regression: float64 moment sums; the all-reduce is the same single call)."""
+    stats = _SOFTMAX if stats is None else stats
     r0, w0 = 0, 1
     if dist.is_available() and dist.is_initialized():
         r0, w0 = dist.get_rank(group), dist.get_world_size(group)
@@ -132,15 +229,15 @@ def mc_forward(model, x, num_samples, sample_offset=0, with_kl=False, group=None
         if isinstance(logits, tuple):
             logits = logits[0]
         if packed is None:
-            packed = torch.zeros(packed_numel(bs, logits.shape[1]), dtype=torch.float32, device=logits.device)
-        accumulate_lanes(packed, logits, len(grp), kl)
+            packed = torch.zeros(stats.numel(bs, logits.shape[1]), dtype=stats.dtype, device=logits.device)
+        stats.accumulate_lanes(packed, logits, len(grp), kl)
     if lanes > 1:
         _rng.set_sample_lanes(model, None)
     if packed is None:  # this rank got no sample: it still takes part in the collective
         with torch.no_grad():
             _rng.set_sample_index(model, sample_offset)
             shape = model(x).shape
-        packed = torch.zeros(packed_numel(*shape), dtype=torch.float32, device=x.device)
+        packed = torch.zeros(stats.numel(*shape), dtype=stats.dtype, device=x.device)
     if reduce and dist.is_available() and dist.is_initialized() and (w0 > 1 or world == w0):
         # also in a 1-rank group: the packed vector takes the same route (RCCL on a GPU) whatever the rank count
         dist.all_reduce(packed, op=dist.ReduceOp.SUM, group=group)
@@ -148,12 +245,14 @@ def mc_forward(model, x, num_samples, sample_offset=0, with_kl=False, group=None
 
 
 @torch.no_grad()
-def mc_forward_batched(model, x, num_samples, chunk=4, sample_offset=0, with_kl=False):
+def mc_forward_batched(model, x, num_samples, chunk=4, sample_offset=0, with_kl=False, stats=None):
     """Opt-in batched-MC Flipout: the reference's own trick `data = torch.cat([data]*S, 0)` then ONE
     forward (examples/main_bayesian_flipout_imagenet.py:613-618).  `chunk` replicas of the batch go through the model
     together: they share one weight perturbation (one sampling pass, `chunk` x larger pixel tiles) and are decorrelated
     by their per-example Flipout signs only — pseudo-independent samples, NOT the statistics of `mc_forward`, which
-    draws fresh weights per sample.  Returns the packed statistics of all `num_samples` replicas (this rank only)."""
+    draws fresh weights per sample.  Returns the packed statistics of all `num_samples` replicas (this rank only).  stats: as in
+    mc_forward."""
+    stats = _SOFTMAX if stats is None else stats
     bs = x.shape[0]
     packed = None
     kl = float(get_kl_loss(model)) if with_kl else 0.0
@@ -166,9 +265,9 @@ def mc_forward_batched(model, x, num_samples, chunk=4, sample_offset=0, with_kl=
         if isinstance(logits, tuple):
             logits = logits[0]
         if packed is None:
-            packed = torch.zeros(packed_numel(bs, logits.shape[1]), dtype=torch.float32, device=logits.device)
+            packed = torch.zeros(stats.numel(bs, logits.shape[1]), dtype=stats.dtype, device=logits.device)
         for i in range(c):
-            accumulate(packed, logits[i * bs:(i + 1) * bs], kl)
+            stats.accumulate(packed, logits[i * bs:(i + 1) * bs], kl)
         done += c
         cid += 1
     return packed
@@ -193,7 +292,7 @@ class GraphedMC:
     replay unless static_input=True (then call set_input() to change it)."""
 
     def __init__(self, model, x, kl=0.0, warmup=2, lanes=1, keep_logits=False, concurrent_hint=None, lane_mode="launch",
-                 static_input=False, capture_stream=None):
+                 static_input=False, capture_stream=None, stats=None):
         """lanes > 1: one replay evaluates `lanes` MC samples (independent noise: the same results as one at a time); use
         run_many().  lane_mode "launch" (default): the samples are lanes of ONE launch per layer (rng.set_sample_lanes:
         4x the workgroups per launch fill the 256 CUs where one sample of a 7x7 / 14x14 layer cannot, and one
@@ -201,7 +300,9 @@ class GraphedMC:
         once (refresh_weights() after a parameter update), a replay samples sigma*eps only.  "streams": each sample on
         its own stream inside the graph, one launch per (layer, sample) — the round-2 form, kept for A/B.
         static_input (lane_mode "launch"): the input batch is the same for every replay, so a row-fused stem packs it into
-        its kernel layout ONCE, outside the graph, instead of once per replay (set_input() re-packs)."""
+        its kernel layout ONCE, outside the graph, instead of once per replay (set_input() re-packs).
+        stats: None — the softmax statistics (f32 packed vector) — or a GaussianStats (regression: float64 moment sums)."""
+        self.stats = _SOFTMAX if stats is None else stats
         if not x.is_cuda:
             raise ValueError("GraphedMC needs CUDA (ROCm) tensors")
         if lane_mode not in ("launch", "streams"):
@@ -312,8 +413,8 @@ class GraphedMC:
         bs = self.bs
         if self.packed is None:
             self.logits_shape = (bs, logits.shape[1])
-            self.packed = torch.zeros(packed_numel(bs, logits.shape[1]), dtype=torch.float32, device=logits.device)
-        accumulate_lanes(self.packed, logits, self.lanes, self.kl)  # one launch for all lanes of the replay
+            self.packed = torch.zeros(self.stats.numel(bs, logits.shape[1]), dtype=self.stats.dtype, device=logits.device)
+        self.stats.accumulate_lanes(self.packed, logits, self.lanes, self.kl)  # one launch for all lanes of the replay
         if self.keep_logits:
             for k in range(self.lanes):
                 self.lane_logits[k] = logits[k * bs:(k + 1) * bs]
@@ -355,10 +456,10 @@ class GraphedMC:
             logits = logits[0]
         if self._lane_packed[k] is None:
             self.logits_shape = tuple(logits.shape)
-            self._lane_packed[k] = torch.zeros(packed_numel(*logits.shape), dtype=torch.float32, device=logits.device)
+            self._lane_packed[k] = torch.zeros(self.stats.numel(*logits.shape), dtype=self.stats.dtype, device=logits.device)
             if k == 0:
                 self.packed = self._lane_packed[0]
-        accumulate(self._lane_packed[k], logits, self.kl)
+        self.stats.accumulate(self._lane_packed[k], logits, self.kl)
         if self.keep_logits:
             self.lane_logits[k] = logits
 
@@ -680,8 +781,229 @@ class Evaluator:
         return out
 
 
+# ---- regression: BTX-REG v1 --------------------------------------------------------------------------------
+REG_HEADER, REG_CURSOR, REG_DROPPED = _lib.REG_EVAL_HEADER, _lib.REG_EVAL_CURSOR, _lib.REG_EVAL_DROPPED
+REG_RECORD = ("mean", "epistemic_var", "aleatoric_var", "err")
+_REG_SUMS = 9
+_TWO_PI = 6.283185307179586
+
+
+def _chunk_fold_sum64(v):
+    """float64 sums over the last axis of v [Q, N] in the kernels' shape: per chunk of 4096 elements 256 strided partials added in
+    order from zero, a butterfly per wave, (w0 + w1) + (w2 + w3); then the fold over the chunks (_fold_sum64)"""
+    q, n = v.shape
+    nch = -(-n // _lib.REG_CHUNK)
+    pad = v.new_zeros(q, nch * _lib.REG_CHUNK)
+    pad[:, :n] = v
+    w = pad.view(q, nch, _lib.REG_CHUNK // 256, 256)
+    acc = v.new_zeros(q, nch, 256)
+    for j in range(w.shape[2]):
+        acc = acc + w[:, :, j]
+    acc = acc.view(q, nch, 4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        acc = acc[..., :off] + acc[..., off:2 * off]
+    acc = acc[..., 0]
+    part = (acc[..., 0] + acc[..., 1]) + (acc[..., 2] + acc[..., 3])
+    return _fold_sum64(part)
+
+
+def normal_quantiles_squared(levels):
+    """z_k^2 with z_k = sqrt(2) erfinv(level_k): the half-width, in standard deviations, of the central interval of a normal that
+    holds `level_k` of its mass.  float64, on the host."""
+    lv = torch.as_tensor(levels, dtype=torch.float64).reshape(-1)
+    z = 2.0 ** 0.5 * torch.erfinv(lv)
+    return z * z
+
+
+class RegressionEvaluator:
+    """Regression metrics of MC predictions, accumulated on the device (BTX-REG v1).
+
+        st = GaussianStats("log")
+        ev = RegressionEvaluator(dims=1, capacity=10000)
+        for x, y in loader:
+            ev.update(mc_forward(model, x, 20, stats=st), y)   # no host read; on the GPU two launches, capturable
+        print(ev.compute())                                    # the one host read
+
+    update() takes the packed moments of a batch (GaussianStats layout, float64) and float32 targets [bs, dims].  A NaN target
+    marks an ignored element, which adds nothing: pad a ragged last batch with them.  noise_var: a fixed observation-noise variance
+    added to the aleatoric part (the variance=None form); min_var: floor of the predictive variance.  levels: the central-interval
+    coverage levels (at most 8).  The state is a float64 vector (layout: include/btx.h K16); the records (mean, epistemic,
+    aleatoric, err) of the first `capacity` ELEMENTS are kept in a device buffer, the rest is counted in `dropped`."""
+
+    def __init__(self, dims, levels=(0.5, 0.8, 0.9, 0.95), noise_var=None, min_var=1e-12, capacity=0, device=None):
+        self.dims = int(dims)
+        if self.dims < 1:
+            raise ValueError("dims must be positive")
+        self.levels = [float(v) for v in torch.as_tensor(levels, dtype=torch.float64).reshape(-1).tolist()]
+        if len(self.levels) > _lib.REG_EVAL_MAX_LEVELS or any(not 0.0 < v < 1.0 for v in self.levels):
+            raise ValueError("at most %d levels, each inside (0, 1)" % _lib.REG_EVAL_MAX_LEVELS)
+        if noise_var is not None and not float(noise_var) >= 0.0:
+            raise ValueError("noise_var must not be negative")
+        if not float(min_var) > 0.0:
+            raise ValueError("min_var must be positive")
+        self.K, self.noise_var, self.min_var, self.capacity = len(self.levels), noise_var, float(min_var), int(capacity)
+        self.device = None
+        self.state = self.z2 = self.records_buffer = self.workspace = self._scratch = None
+        if device is not None:
+            self._alloc(torch.device(device))
+
+    def _alloc(self, dev):
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.state = torch.zeros(REG_HEADER + self.K, dtype=torch.float64, device=dev)
+        self.z2 = normal_quantiles_squared(self.levels).to(dev)
+        if self.capacity:
+            self.records_buffer = torch.zeros(self.capacity, 4, dtype=torch.float32, device=dev)
+
+    def reserve(self, elements):
+        """grow the record buffer to hold at least `elements` records (a new allocation: not for use between replays of a captured
+        update)"""
+        elements = int(elements)
+        if elements <= self.capacity:
+            return
+        new = max(elements, 2 * self.capacity)
+        if self.device is not None:
+            buf = torch.zeros(new, 4, dtype=torch.float32, device=self.device)
+            if self.records_buffer is not None:
+                buf[:self.capacity] = self.records_buffer
+            self.records_buffer = buf
+        self.capacity = new
+
+    def update(self, packed, target):
+        """fold one batch: packed [3 * bs * dims + 2] float64 and target [bs, dims] float32, on one device.  GPU:
+        btx_reg_eval_update, two launches on the current stream, capturable in torch.cuda.graph.  CPU tensors run the same
+        arithmetic with torch ops in float64."""
+        if self.device is None:
+            self._alloc(packed.device)
+        D = self.dims
+        N = target.numel()
+        if N % D or N < 1:
+            raise ValueError("target must be [bs, %d]" % D)
+        bs = N // D
+        if packed.device != self.device:
+            raise ValueError("packed is on %s, the evaluator's state on %s" % (packed.device, self.device))
+        if packed.numel() != 3 * N + 2 or packed.dtype != torch.float64:
+            raise ValueError("packed must hold %d float64 words for bs %d, dims %d (GaussianStats)" % (3 * N + 2, bs, D))
+        y = target.to(device=packed.device, dtype=torch.float32).reshape(N).contiguous()
+        nv = 0.0 if self.noise_var is None else float(self.noise_var)
+        if packed.is_cuda:
+            pk = packed.contiguous()
+            L = _lib.lib()
+            need = L.btx_reg_eval_workspace_bytes(bs, D)
+            if self.workspace is None or self.workspace.numel() * 8 < need:
+                self.workspace = torch.empty(need // 8, dtype=torch.float64, device=self.device)
+            rec = self.records_buffer
+            _lib.check(L.btx_reg_eval_update(pk.data_ptr(), y.data_ptr(), bs, D, nv, self.min_var, self.z2.data_ptr() if self.K else None,
+                                             self.K, self.state.data_ptr(), self.state.numel(),
+                                             rec.data_ptr() if rec is not None else None, rec.shape[0] if rec is not None else 0,
+                                             self.workspace.data_ptr(), self.workspace.numel() * 8,
+                                             torch.cuda.current_stream(self.device).cuda_stream))
+            return self
+        n = packed[3 * N + 1]
+        yd = y.double()
+        ok = ~torch.isnan(yd)
+        mean = packed[:N] / n
+        ep = (packed[N:2 * N] / n - mean * mean).clamp_min(0.0)
+        al = packed[2 * N:3 * N] / n + nv
+        var = (ep + al).clamp_min(self.min_var)
+        err = yd - mean
+        e2 = err * err
+        nll = 0.5 * (torch.log((_TWO_PI * var).float().double()).float().double() + e2 / var)
+        z = torch.zeros_like(yd)
+        rows = [ok.double(), (~ok).double()]
+        rows += [torch.where(ok, t, z) for t in (e2, err.abs(), nll, ep, al, yd, yd * yd)]
+        rows += [(ok & (e2 <= self.z2[k] * var)).double() for k in range(self.K)]
+        s = _chunk_fold_sum64(torch.stack(rows))
+        cap = 0 if self.records_buffer is None else self.records_buffer.shape[0]
+        cur = self.state[REG_CURSOR].clone()
+        if cap:
+            at = cur.long() + torch.arange(N)
+            keep = at < cap
+            self.records_buffer[at[keep]] = torch.stack([mean, ep, al, err], 1).float()[keep]
+        self.state[:_REG_SUMS] += s[:_REG_SUMS]
+        self.state[REG_HEADER:REG_HEADER + self.K] += s[_REG_SUMS:]
+        self.state[REG_DROPPED] += (cur + N - cap).clamp(0.0, float(N))
+        self.state[REG_CURSOR] = cur + N
+        return self
+
+    def update_outputs(self, out, target):
+        """one deterministic (or single-sample) forward: the outputs [bs, 2 * dims] (mean | log-variance) or [bs, dims] (mean) are
+        accumulated into a zeroed scratch packed vector as ONE sample, then update()"""
+        bs, W = out.shape
+        if W not in (self.dims, 2 * self.dims):
+            raise ValueError("out must be [bs, %d] or [bs, %d]" % (self.dims, 2 * self.dims))
+        st = GaussianStats("log" if W == 2 * self.dims else None)
+        n = st.numel(bs, W)
+        if self._scratch is None or self._scratch.numel() != n or self._scratch.device != out.device:
+            self._scratch = torch.zeros(n, dtype=torch.float64, device=out.device)
+        self._scratch.zero_()
+        st.accumulate(self._scratch, out)
+        return self.update(self._scratch, target)
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+        return self
+
+    def merge(self, other):
+        """add another evaluator's state (same dims / levels).  The record cursor, the dropped count and the records themselves stay
+        this evaluator's own."""
+        if (other.dims, other.levels) != (self.dims, self.levels):
+            raise ValueError("merge of evaluators with different settings")
+        if other.state is None:
+            return self
+        if self.device is None:
+            self._alloc(other.device)
+        keep = self.state[REG_CURSOR:REG_DROPPED + 1].clone()
+        self.state += other.state.to(self.device)
+        self.state[REG_CURSOR:REG_DROPPED + 1] = keep
+        return self
+
+    def reduce(self, group=None):
+        """ONE float64 all_reduce(SUM) of the state over `group`; the cursor words and the records stay local"""
+        if dist.is_available() and dist.is_initialized():
+            keep = self.state[REG_CURSOR:REG_DROPPED + 1].clone()
+            dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
+            self.state[REG_CURSOR:REG_DROPPED + 1] = keep
+        return self
+
+    def compute(self):
+        """-> dict of the metrics; the one host read (the state vector)"""
+        import numpy as np
+        if self.state is None:
+            raise ValueError("compute() before the first update()")
+        s = self.state.cpu().numpy()
+        n = s[0]
+        d = n if n > 0 else 1.0
+        mse = s[2] / d
+        sst = s[8] - s[7] * s[7] / d
+        cov = s[REG_HEADER:REG_HEADER + self.K] / d
+        lv = np.asarray(self.levels, dtype=np.float64)
+        out = {"n": int(n), "ignored": int(s[1]), "mse": mse, "rmse": float(np.sqrt(mse)), "mae": s[3] / d, "nll": s[4] / d,
+               "r2": float(1.0 - s[2] / sst) if sst > 0 else float("nan"),
+               "mean_epistemic_var": s[5] / d, "mean_aleatoric_var": s[6] / d, "mean_total_var": (s[5] + s[6]) / d,
+               "coverage": cov, "levels": lv, "calibration_error": float(((cov - lv) ** 2).mean()) if self.K else 0.0,
+               "dropped": int(s[REG_DROPPED])}
+        return {k: (float(v) if isinstance(v, np.floating) else v) for k, v in out.items()}
+
+    def records(self):
+        """-> dict of numpy float32 arrays [M] over the kept elements, ignored ones left out: mean, epistemic_var, aleatoric_var,
+        err, and error = |err|, unc = epistemic_var + aleatoric_var — the vectors uncertainty_calibration_loss.EaULoss takes"""
+        import numpy as np
+        if self.state is None or self.records_buffer is None:
+            rec = np.zeros((0, 4), np.float32)
+        else:
+            kept = min(int(self.state[REG_CURSOR].item()), self.records_buffer.shape[0])
+            rec = self.records_buffer[:kept].cpu().numpy()
+        rec = rec[~np.isnan(rec[:, 3])]
+        out = {name: rec[:, j].copy() for j, name in enumerate(REG_RECORD)}
+        out["error"], out["unc"] = np.abs(out["err"]), out["epistemic_var"] + out["aleatoric_var"]
+        return out
+
+
 @torch.no_grad()
-def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0, evaluator=None, group=None):
+def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0, evaluator=None, group=None, stats=None):
     """The reference's evaluate() loop (examples/main_bayesian_imagenet.py:598-642): `num_samples` MC forwards of every batch of
     `batches` (an iterable of (x, y)), mean probabilities, argmax, accuracy — and everything else Evaluator accumulates — with no
     host read inside the loop.  Returns the evaluator; call compute() / records() on it.
@@ -691,8 +1013,13 @@ def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0
     folds the result.  A ragged last batch is padded to the captured shape with zeros and ignore_index labels.  Otherwise:
     mc_forward + update per batch.  Every rank runs all samples of ITS batches (the validation set, not the samples, is what is
     sharded here); with `group` the states are summed at the end by Evaluator.reduce(group).
-    evaluator=None: one is built on the first batch that keeps per-example records, its buffer grown between the batches."""
+    evaluator=None: one is built on the first batch that keeps per-example records, its buffer grown between the batches.
+    stats=GaussianStats(...) with evaluator=RegressionEvaluator(...) (or None: one is built): the same loop for a model that predicts
+    real values; targets are float32 [bs, D] and a ragged last batch is padded with zero rows and NaN targets."""
     ev, grow, g, seen = evaluator, evaluator is None, None, 0
+    reg = isinstance(stats, GaussianStats)
+    if ev is not None and reg != isinstance(ev, RegressionEvaluator):
+        raise ValueError("stats=GaussianStats goes with a RegressionEvaluator, stats=None with an Evaluator")
     lanes = max(1, int(lanes))
     try:
         for x, y in batches:
@@ -704,15 +1031,19 @@ def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0
                 if num_samples % lane_n:
                     raise ValueError("num_samples must be a multiple of lanes for graphed evaluation")
                 if g is None:
-                    g = GraphedMC(model, x.clone(), lanes=lane_n, static_input=True)
+                    g = GraphedMC(model, x.clone(), lanes=lane_n, static_input=True, stats=stats)
                 bs = g.x.shape[0]
                 if x.shape[0] > bs or x.shape[1:] != g.x.shape[1:]:
                     raise ValueError("a batch larger than the first (captured) batch")
                 if x.shape[0] < bs:
                     xp = torch.zeros_like(g.x)
                     xp[:x.shape[0]] = x
-                    yp = torch.full((bs,), ev.ignore_index if ev is not None else -100, dtype=torch.int64, device=y.device)
-                    yp[:y.numel()] = y
+                    if reg:
+                        yp = torch.full((bs, y.numel() // x.shape[0]), float("nan"), dtype=torch.float32, device=y.device)
+                        yp[:x.shape[0]] = y.reshape(x.shape[0], -1)
+                    else:
+                        yp = torch.full((bs,), ev.ignore_index if ev is not None else -100, dtype=torch.int64, device=y.device)
+                        yp[:y.numel()] = y
                     x, y = xp, yp
                 g.packed.zero_()
                 g.set_input(x)
@@ -724,12 +1055,15 @@ def evaluate(model, batches, num_samples, lanes=1, graphed=None, sample_offset=0
                         g.run_many(idx)
                 packed = g.packed
             else:
-                packed = mc_forward(model, x, num_samples, sample_offset=sample_offset, reduce=False, lanes=lane_n, rank=0, world=1)
+                packed = mc_forward(model, x, num_samples, sample_offset=sample_offset, reduce=False, lanes=lane_n, rank=0, world=1,
+                                    stats=stats)
             bs = x.shape[0]
-            if ev is None:
+            if ev is None and reg:
+                ev = RegressionEvaluator((packed.numel() - 2) // (3 * bs), device=packed.device)
+            elif ev is None:
                 ev = Evaluator((packed.numel() - 2 - bs) // (2 * bs), device=packed.device)
             if grow:
-                seen += bs
+                seen += bs * ev.dims if reg else bs
                 ev.reserve(seen)
             ev.update(packed, y.to(packed.device))
     finally:

@@ -1,4 +1,4 @@
 from .util import get_rho, entropy, predictive_entropy, mutual_information  # noqa: F401
 from . import avuc_loss, uncertainty_calibration_loss  # noqa: F401
 from . import mc_loss  # noqa: F401
-from .mc_loss import MCCrossEntropy, mc_elbo_loss  # noqa: F401
+from .mc_loss import MCCrossEntropy, MCGaussianNLL, mc_elbo_loss, mc_gaussian_nll  # noqa: F401

@@ -807,6 +807,59 @@ size_t btx_mc_eval_workspace_bytes(int bs);
 int btx_mc_eval(const float* packed, const int64_t* labels, int bs, int C, int topk, int nbins, const float* th, int T, int use_mi,
                 double* state, size_t state_doubles, float* records, int64_t capacity, void* ws, size_t ws_bytes, void* stream);
 
+/* K16 (ABI 9, additive; DESIGN.md §19, BTX-REG v1): the two ends of a model that predicts real values.  A model output is
+ * out [rows][W] in act_dtype (f32 or bf16): has_var = 1: W = 2 D, columns [0, D) the mean m and [D, 2 D) the log-variance s;
+ * has_var = 0: W = D, the mean alone.  Elements e = b * D + d, N = rows * D <= 2^31 - 3 (more: BTX_E_UNSUPPORTED).
+ * Every launch goes to the caller's stream, allocates nothing, reads nothing on the host and uses no atomics: capturable, and two
+ * runs give the same bits.  Sums over the elements ("chunk / fold"): terms widen to double; a workgroup of 256 threads owns a chunk
+ * of 4096 elements, thread t adds e = t, t + 256, ... in order from zero, a xor butterfly per wave (32, 16, ..., 1), then
+ * (w0 + w1) + (w2 + w3); ONE workgroup folds the chunks' partials, lane l adding l, l + 64, ..., with the same butterfly.
+ *
+ * btx_mc_moments_lanes: packed (float64, 3 N + 2 words) += the statistics of `lanes` samples, out [lanes * bs][W] back to back:
+ *   [N sum m | N sum m^2 | N sum v | sum kl | samples], v = (double)expf(s), m^2 the exact double product of the widened value; the
+ *   third block is left untouched when has_var = 0.  One element-wise launch; a thread folds the lanes of its elements in order, so
+ *   one call equals `lanes` calls with lanes = 1 bit for bit.  16-byte accesses when out and packed are 16-byte aligned and D is a
+ *   multiple of 16 / sizeof(element), element-wise ones otherwise: same bits, and no valid tensor ends in BTX_E_ALIGN.
+ * btx_mc_gnll_fwd: out[0] = the Gaussian negative log-likelihood of the stack [S][B][W] against target [B][D] (f32), 1 <= S <=
+ *   BTX_MCLOSS_MAX_S.  Per element f32, every operation rounded once.  has_var = 0: s = logf(noise_var) for every sample, noise_var > 0.
+ *   reduce 1 ("loss"):    l = 0.5 (s + (y - m)^2 expf(-s));  out = sum_{s,b,d} l / (S B) + [full] 0.5 log(2 pi) D + kl[0] / B
+ *   reduce 0 ("moments"): mbar = (sum_s m_s) / S, vbar = (sum_s expf(s_s)) / S + (sum_s (m_s - mbar)^2) / S,
+ *                         l = 0.5 (logf(vbar) + (y - mbar)^2 / vbar);  out = sum_{b,d} l / B + [full] ... + kl[0] / B
+ *   The sum is the chunk / fold sum; the division, the constant and the kl term are taken in double and rounded to f32 once.
+ *   kl: DEVICE pointer to one f32, nullable.  ws: btx_mc_gnll_workspace_bytes(B, D) bytes, 8-byte aligned.  Two launches.
+ * btx_mc_gnll_bwd: dstack [S][B][W] in act_dtype (bf16: round to nearest even) = g_loss[0] * d out / d stack, fully overwritten, one
+ *   element-wise launch; g_loss: DEVICE scalar, multiplied last.  With k = 1 / (S B), r = y - m (reduce 1) or y - mbar (reduce 0):
+ *   reduce 1: d m_s = -(r expf(-s)) k, d s_s = 0.5 (1 - r^2 expf(-s)) k;  reduce 0: a = 1 / vbar - r^2 / vbar^2,
+ *   d m_s = (-(r / vbar) + (m_s - mbar) a) k, d s_s = 0.5 expf(s_s) a k.  (The gradient of kl is g_loss[0] / B: the caller's.)
+ * btx_reg_eval_update: folds a batch — packed as above and target [bs][D] f32 — into state (float64).  Per element, in double with
+ *   every operation rounded once: n = packed[3 N + 1], mean = sum_m / n, ep = max(sum_m2 / n - mean^2, 0), al = sum_v / n + noise_var,
+ *   var = max(ep + al, min_var), err = y - mean, nll = 0.5 ((double)logf((float)(2 pi var)) + err^2 / var),
+ *   cover_k = [err^2 <= z2[k] var], k < K <= BTX_REG_EVAL_MAX_LEVELS; z2: DEVICE doubles (the squared normal quantiles).  A NaN target
+ *   marks an ignored element, which adds nothing.  state, accumulated in place (zero it to reset, add two states to merge them):
+ *   [0] valid  [1] ignored  [2] sum err^2  [3] sum |err|  [4] sum nll  [5] sum ep  [6] sum al  [7] sum y  [8] sum y^2
+ *   [BTX_REG_EVAL_CURSOR] elements seen  [BTX_REG_EVAL_DROPPED] elements whose record did not fit  [11..15] spare
+ *   [BTX_REG_EVAL_HEADER + k] elements covered at level k.  records != NULL: records[cursor + e] = (mean, ep, al, err) as f32 for
+ *   cursor + e < capacity (err is NaN on an ignored element).  Two launches; ws: btx_reg_eval_workspace_bytes(bs, D) bytes.
+ * Errors, all before anything is launched: BTX_E_NULL, BTX_E_SHAPE (lanes, S, rows, D < 1, S > BTX_MCLOSS_MAX_S, a flag that is not
+ *   0 or 1, has_var = 0 with noise_var <= 0, K outside 0..BTX_REG_EVAL_MAX_LEVELS, capacity < 0, noise_var < 0, min_var <= 0),
+ *   BTX_E_UNSUPPORTED (N), BTX_E_DTYPE, BTX_E_WORKSPACE (ws_bytes, state_doubles < BTX_REG_EVAL_HEADER + K), BTX_E_ALIGN (a pointer
+ *   below the alignment of its own element type). */
+#define BTX_REG_EVAL_MAX_LEVELS 8
+#define BTX_REG_EVAL_HEADER 16
+#define BTX_REG_EVAL_CURSOR 9
+#define BTX_REG_EVAL_DROPPED 10
+int btx_mc_moments_lanes(const void* out, int lanes, int bs, int D, int has_var, int act_dtype, double kl, double* packed,
+                         void* stream);
+size_t btx_mc_gnll_workspace_bytes(int B, int D);
+int btx_mc_gnll_fwd(const void* stack, const float* target, int S, int B, int D, int has_var, int act_dtype, int reduce, float noise_var,
+                    int full, const float* kl, float* out, void* ws, size_t ws_bytes, void* stream);
+int btx_mc_gnll_bwd(const void* stack, const float* target, int S, int B, int D, int has_var, int act_dtype, int reduce, float noise_var,
+                    const float* g_loss, void* dstack, void* stream);
+size_t btx_reg_eval_workspace_bytes(int bs, int D);
+int btx_reg_eval_update(const double* packed, const float* target, int bs, int D, double noise_var, double min_var, const double* z2,
+                        int K, double* state, size_t state_doubles, float* records, int64_t capacity, void* ws, size_t ws_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
