@@ -10,38 +10,13 @@
 // Determinism: every sum has a shape fixed by (B, C) alone — a lane's strided partial, a xor butterfly inside the wave (both
 // partners add the same two numbers, so all lanes hold the same bits), and partials of the fold added in index order by one
 // thread.  No atomics.  The quadrant sums and everything after them are double.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/btx.h"
+// The workspace layout (CALIB_*, HDR_*) and wave_sum live in btx_heads.h; the fold's AvU mode also serves btx_mcloss.hip, through
+// btx::launch_avu_fold.
+#include "btx_heads.h"
 
 #define CALIB_EPS 1e-10f
-#define CALIB_K_AREA 21
-#define CALIB_HDR_FLOATS 160   // header of the workspace, see hdr_* below
-#define CALIB_ROW_FLOATS 8     // per-row record: conf, H, tanh(H), code, row max, 3 spare
-#define CALIB_FOLD_THREADS 1024
-#define CALIB_FOLD_WAVES 16
-
-// workspace header (float index)
-#define HDR_LOSS 0
-#define HDR_R 1
-#define HDR_DLDR 2      // d loss / d r
-#define HDR_K 3         // number of thresholds, as int bits
-#define HDR_THA 4       // EaU / EaC: the error threshold the forward used
-#define HDR_G 8         // [K][4] d r / d n_q, quadrant q = (good ? 0 : 2) + (certain ? 0 : 1)
-#define HDR_TH 96       // [K] thresholds, double (8-byte aligned: 96 * 4 = 384)
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---- (1) per-row softmax statistics ---------------------------------------------------------------------------------
 template <typename ACT>
@@ -288,6 +263,11 @@ __global__ __launch_bounds__(256) void eau_bwd_kernel(const float* __restrict__ 
 
 }  // namespace
 
+void btx::launch_avu_fold(int B, int area, float th, const float* th_dev, float beta, float* out, float* ws, hipStream_t st) {
+  hipLaunchKernelGGL(calib_fold_kernel<0>, dim3(1), dim3(CALIB_FOLD_THREADS), 0, st, (const float*)nullptr, (const float*)nullptr,
+                     B, area ? CALIB_K_AREA : 1, 0.f, (const float*)nullptr, th, th_dev, beta, out, ws);
+}
+
 extern "C" {
 
 size_t btx_calib_workspace_bytes(int B) {
@@ -299,38 +279,30 @@ int btx_avu_fwd(const void* logits, const int64_t* labels, int B, int C, int act
                 float beta, float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!logits || !labels || !out || !ws) return BTX_E_NULL;
   if (B <= 0 || C <= 0 || (area != 0 && area != 1)) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  if (!act_esize(act_dtype)) return BTX_E_DTYPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
-  float* rows = (float*)ws + CALIB_HDR_FLOATS;
-  const dim3 grid((B + 3) / 4);
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(avu_row_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, (const long long*)labels, B, C, rows);
-  else
-    hipLaunchKernelGGL(avu_row_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)logits, (const long long*)labels, B, C,
-                       rows);
-  hipLaunchKernelGGL(calib_fold_kernel<0>, dim3(1), dim3(CALIB_FOLD_THREADS), 0, st, (const float*)nullptr, (const float*)nullptr,
-                     B, area ? CALIB_K_AREA : 1, 0.f, (const float*)nullptr, th, th_dev, beta, out, (float*)ws);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(avu_row_kernel<T>, dim3((B + 3) / 4), dim3(256), 0, st, (const T*)logits, (const long long*)labels, B, C,
+                       (float*)ws + CALIB_HDR_FLOATS);
+    btx::launch_avu_fold(B, area, th, th_dev, beta, out, (float*)ws, st);
+  });
 }
 
 int btx_avu_bwd(const void* logits, int B, int C, int act_dtype, const float* g_loss, const float* g_r, const void* ws,
                 size_t ws_bytes, void* dlogits, void* stream) {
   if (!logits || !ws || !dlogits || (!g_loss && !g_r)) return BTX_E_NULL;
   if (B <= 0 || C <= 0) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  if (!act_esize(act_dtype)) return BTX_E_DTYPE;
   if (ws_bytes < btx_calib_workspace_bytes(B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((B + 3) / 4);
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(avu_bwd_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, B, C, g_loss, g_r, (const float*)ws,
-                       (float*)dlogits);
-  else
-    hipLaunchKernelGGL(avu_bwd_kernel<__bf16>, grid, dim3(256), 0, st, (const __bf16*)logits, B, C, g_loss, g_r,
-                       (const float*)ws, (__bf16*)dlogits);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(avu_bwd_kernel<T>, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const T*)logits, B, C, g_loss, g_r,
+                       (const float*)ws, (T*)dlogits);
+  });
 }
 
 int btx_eau_fwd(const float* error, const float* other, int B, int conf_form, float error_th, const float* error_th_dev,

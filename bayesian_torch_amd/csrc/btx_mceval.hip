@@ -12,9 +12,9 @@
 // the same two numbers, so every lane holds the same bits) and (w0 + w1) + (w2 + w3) over the four waves; a state sum is a
 // lane's strided partial over the rows (i = lane, lane + 64, ...) and the same butterfly.  Shapes fixed by C and bs alone, no
 // atomics, no "last block" counters.  Every load and store is element-wise: any 4-byte aligned packed / workspace / records.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/btx.h"
+// The butterfly is wave_sum of btx_heads.h; the pairwise sum over the four waves is spelled out in the row kernel, which folds five
+// quantities behind ONE barrier (block_sum_pairwise4 would take one per quantity).
+#include "btx_heads.h"
 
 #define EVAL_EPS 1e-15f
 #define EVAL_ROW_THREADS 256
@@ -22,22 +22,6 @@
 #define EVAL_FOLD_WAVES 16
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // the ECE bin of a confidence: right-closed bins ((b / nbins, (b + 1) / nbins])
 __device__ __forceinline__ int eval_bin(float conf, int nbins) {

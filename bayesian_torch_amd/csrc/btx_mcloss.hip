@@ -10,110 +10,18 @@
 // (max, 1 / sum) pairs, the reduction partials and, in the AvUC backward, the row of d H(pbar) / d pbar.
 // Determinism: a thread owns the classes c0 .. c0 + V - 1 (V = 16 bytes of logits) for c0 = V * (tid + 256 i) on the vector path
 // AND on the scalar path (rows off the 16-byte grid), so both paths add the same numbers in the same order; partials meet in a xor
-// butterfly inside the wave and the four wave partials are added in index order.  No atomics.  The sums over B are double.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/btx.h"
+// butterfly inside the wave and the four wave partials are added in index order (block_sum_inorder4 of btx_heads.h, which also holds
+// Vw / load_v / store_v and the calibration workspace layout).  No atomics.  The sums over B are double.
+#include "btx_heads.h"
 
 #define MCL_THREADS 256
 #define MCL_WAVES 4
 #define MCL_EPS 1e-10f
-#define MCL_K_AREA 21
-#define MCL_HDR_FLOATS 160   // the header of btx_calib.hip (same slots), then the per-row records, then the per-(s, b) pairs
-#define MCL_ROW_FLOATS 8     // conf, u, tanh(u), code, 4 spare
-#define MCL_FOLD_THREADS 1024
-#define MCL_FOLD_WAVES 16
-
-#define HDR_DLDR 2
-#define HDR_K 3
-#define HDR_G 8
-#define HDR_TH 96
 
 namespace {
 
-template <typename ACT> struct Vw;
-template <> struct Vw<float> { static constexpr int V = 4; };
-template <> struct Vw<__bf16> { static constexpr int V = 8; };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// sums / maxima over the workgroup; every thread returns the same bits.  `red`: MCL_WAVES floats of LDS.
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();  // red may still be read from the previous reduction
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = red[0];
-#pragma unroll
-  for (int w = 1; w < MCL_WAVES; ++w) t += red[w];
-  return t;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = red[0];
-#pragma unroll
-  for (int w = 1; w < MCL_WAVES; ++w) t = fmaxf(t, red[w]);
-  return t;
-}
-
-// V consecutive elements of a row from class c0 on: one 16-byte load when `vec` (row on the grid, C % V == 0), else element by
-// element with the tail left at 0
-template <typename ACT>
-__device__ __forceinline__ void load_v(const ACT* __restrict__ row, int c0, int C, bool vec, float* v) {
-  constexpr int V = Vw<ACT>::V;
-  if (vec) {
-    if constexpr (sizeof(ACT) == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(row + c0);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      const uint4 q = *reinterpret_cast<const uint4*>(row + c0);
-      const unsigned int w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[2 * j] = __uint_as_float(w[j] << 16);
-        v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = (c0 + j < C) ? (float)row[c0 + j] : 0.f;
-  }
-}
-
-template <typename ACT>
-__device__ __forceinline__ void store_v(ACT* __restrict__ row, int c0, int C, bool vec, const float* v) {
-  constexpr int V = Vw<ACT>::V;
-  if (vec) {
-    if constexpr (sizeof(ACT) == 4) {
-      *reinterpret_cast<float4*>(row + c0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      union { uint4 q; __bf16 h[8]; } u;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) u.h[j] = (__bf16)v[j];
-      *reinterpret_cast<uint4*>(row + c0) = u.q;
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j)
-      if (c0 + j < C) row[c0 + j] = (ACT)v[j];
-  }
-}
-
 // V values of the row the cross-entropy sees: the mean over `sin` samples (stride `ss` elements) in sample order; sin = 1 with
-// inv = 1 is the sample itself, bit for bit
+// inv = 1 is the sample itself, bit for bit.  (Stays here: the units differ in how they pin contraction, see btx_heads.h.)
 template <typename ACT>
 __device__ __forceinline__ void mean_v(const ACT* __restrict__ row, size_t ss, int sin, float inv, int c0, int C, bool vec, float* v) {
   constexpr int V = Vw<ACT>::V;
@@ -154,7 +62,7 @@ __global__ __launch_bounds__(MCL_THREADS) void mc_ce_row_kernel(const ACT* __res
       for (int j = 0; j < V; ++j)
         if (c0 + j < C) mx = fmaxf(mx, v[j]);
     }
-    mx = block_max(mx, red);
+    mx = block_max_inorder4(mx, red);
     float se = 0.f, sz = 0.f;
     for (int c0 = threadIdx.x * V; c0 < C; c0 += MCL_THREADS * V) {
       float v[V];
@@ -163,8 +71,8 @@ __global__ __launch_bounds__(MCL_THREADS) void mc_ce_row_kernel(const ACT* __res
       for (int j = 0; j < V; ++j)
         if (c0 + j < C) { se += expf(v[j] - mx); sz += v[j]; }
     }
-    se = block_sum(se, red);
-    sz = block_sum(sz, red);
+    se = block_sum_inorder4(se, red);
+    sz = block_sum_inorder4(sz, red);
     if (threadIdx.x == 0) {
       float zy = 0.f;
       if (y_ok) {
@@ -246,7 +154,7 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_row_kernel(const ACT* __re
   const int b = blockIdx.x;
   const size_t ss = (size_t)B * C;
   const ACT* row0 = logits + (size_t)b * C;
-  float* pairs = ws + MCL_HDR_FLOATS + (size_t)B * MCL_ROW_FLOATS;
+  float* pairs = ws + CALIB_HDR_FLOATS + (size_t)B * CALIB_ROW_FLOATS;
   for (int s = 0; s < S; ++s) {
     const ACT* row = row0 + (size_t)s * ss;
     float mx = -INFINITY;
@@ -257,7 +165,7 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_row_kernel(const ACT* __re
       for (int j = 0; j < V; ++j)
         if (c0 + j < C) mx = fmaxf(mx, v[j]);
     }
-    mx = block_max(mx, red);
+    mx = block_max_inorder4(mx, red);
     float se = 0.f;
     for (int c0 = threadIdx.x * V; c0 < C; c0 += MCL_THREADS * V) {
       float v[V];
@@ -266,7 +174,7 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_row_kernel(const ACT* __re
       for (int j = 0; j < V; ++j)
         if (c0 + j < C) se += expf(v[j] - mx);
     }
-    se = block_sum(se, red);
+    se = block_sum_inorder4(se, red);
     if (threadIdx.x == 0) {
       m_s[s] = mx;
       i_s[s] = 1.0f / se;
@@ -302,8 +210,8 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_row_kernel(const ACT* __re
         if (p > best) { best = p; am = c0 + j; }  // ascending classes: a tie keeps the lowest index
       }
   }
-  eh = block_sum(eh, red);
-  hb = block_sum(hb, red);
+  eh = block_sum_inorder4(eh, red);
+  hb = block_sum_inorder4(hb, red);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     const float ob = __shfl_xor(best, off, 64);
@@ -318,100 +226,11 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_row_kernel(const ACT* __re
       if (red[w] > best || (red[w] == best && redi[w] < am)) { best = red[w]; am = redi[w]; }
     if (am >= C) am = 0;  // a row of NaN compares false everywhere: keep the index inside the row
     const float u = hb - eh * invS;
-    float* r = ws + MCL_HDR_FLOATS + (size_t)b * MCL_ROW_FLOATS;
+    float* r = ws + CALIB_HDR_FLOATS + (size_t)b * CALIB_ROW_FLOATS;
     r[0] = best;
     r[1] = u;
     r[2] = tanhf(u);
     r[3] = __int_as_float((am << 1) | (labels[b] == (long long)am ? 1 : 0));
-  }
-}
-
-// the fold of btx_calib.hip (its AvU mode) on the records above: thresholds, quadrant sums in double, the loss and d r / d n_q
-__global__ __launch_bounds__(MCL_FOLD_THREADS) void avu_mc_fold_kernel(int B, int K, float th_b, const float* __restrict__ th_b_dev,
-                                                                      float beta, float* __restrict__ out, float* __restrict__ ws) {
-#pragma clang fp contract(off)
-  __shared__ double part[MCL_K_AREA][MCL_FOLD_WAVES][4];
-  __shared__ double th_s[MCL_K_AREA];
-  __shared__ double r_s[MCL_K_AREA];
-  __shared__ float mm_s[2][MCL_FOLD_WAVES];
-  const float* rows = ws + MCL_HDR_FLOATS;
-  const int wave = threadIdx.x >> 6, li = threadIdx.x & 63;
-  if (th_b_dev) th_b = *th_b_dev;
-  if (K > 1) {
-    float lo = INFINITY, hi = -INFINITY;
-    for (int i = threadIdx.x; i < B; i += MCL_FOLD_THREADS) {
-      const float h = rows[(size_t)i * MCL_ROW_FLOATS + 1];
-      lo = fminf(lo, h);
-      hi = fmaxf(hi, h);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = fminf(lo, __shfl_xor(lo, off, 64));
-      hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    }
-    if (li == 0) { mm_s[0][wave] = lo; mm_s[1][wave] = hi; }
-    __syncthreads();
-    if (threadIdx.x < K) {
-      for (int w = 0; w < MCL_FOLD_WAVES; ++w) { lo = fminf(lo, mm_s[0][w]); hi = fmaxf(hi, mm_s[1][w]); }
-      const int k = threadIdx.x;
-      th_s[k] = (k == K - 1) ? (double)hi : (double)lo + ((double)k * 0.05) * ((double)hi - (double)lo);
-    }
-  } else if (threadIdx.x == 0) {
-    th_s[0] = (double)th_b;
-  }
-  __syncthreads();
-  const int SL = min(MCL_FOLD_WAVES, (B + 63) / 64);
-  for (int item = wave; item < K * SL; item += MCL_FOLD_WAVES) {  // wave-uniform
-    const int k = item / SL, s = item - k * SL;
-    const double th = th_s[k];
-    double n[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = s * 64 + li; i < B; i += 64 * SL) {
-      const float* r = rows + (size_t)i * MCL_ROW_FLOATS;
-      const float cf = r[0], t = r[2];
-      const bool good = (__float_as_int(r[3]) & 1) != 0;
-      const float w = good ? cf : 1.0f - cf;
-      const bool cert = (double)r[1] <= th;
-      const int q = (good ? 0 : 2) + (cert ? 0 : 1);
-      const double wq = (double)(cert ? w * (1.0f - t) : w * t);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) n[j] += (q == j) ? wq : 0.0;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) n[j] = wave_sum(n[j]);
-    if (li == 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) part[k][s][j] = n[j];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    const int k = threadIdx.x;
-    double n[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int s = 0; s < SL; ++s)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) n[j] += part[k][s][j];
-    const double num = n[0] + n[3];
-    const double den = ((n[0] + n[1]) + (n[2] + n[3])) + 1e-10;
-    r_s[k] = num / den;
-    const double wk = (K == 1) ? 1.0 : ((k == 0 || k == K - 1) ? 0.025 : 0.05);
-    float* G = ws + HDR_G + 4 * k;
-    G[0] = (float)(wk * (den - num) / (den * den));
-    G[1] = (float)(wk * (-num) / (den * den));
-    G[2] = G[1];
-    G[3] = G[0];
-    ((double*)(ws + HDR_TH))[k] = th_s[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = r_s[0];
-    if (K > 1) {
-      r = 0.0;
-      for (int k = 0; k + 1 < K; ++k) r += 0.05 * (r_s[k] + r_s[k + 1]) * 0.5;
-    }
-    out[0] = (float)(-(double)beta * log(r + 1e-10));
-    out[1] = (float)r;
-    ws[HDR_DLDR] = (float)(-(double)beta / (r + 1e-10));
-    ws[HDR_K] = __int_as_float(K);
   }
 }
 
@@ -430,14 +249,14 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_bwd_kernel(const ACT* __re
   __shared__ float m_s[BTX_MCLOSS_MAX_S], i_s[BTX_MCLOSS_MAX_S];
   const int b = blockIdx.x;
   const size_t ss = (size_t)B * C;
-  const float* r = ws + MCL_HDR_FLOATS + (size_t)b * MCL_ROW_FLOATS;
-  const float* pairs = ws + MCL_HDR_FLOATS + (size_t)B * MCL_ROW_FLOATS;
+  const float* r = ws + CALIB_HDR_FLOATS + (size_t)b * CALIB_ROW_FLOATS;
+  const float* pairs = ws + CALIB_HDR_FLOATS + (size_t)B * CALIB_ROW_FLOATS;
   const float cf = r[0], t = r[2];
   const double u = (double)r[1];
   const int code = __float_as_int(r[3]);
   const bool good = code & 1;
   const int am = min(max(code >> 1, 0), C - 1);
-  const int K = min(max(__float_as_int(ws[HDR_K]), 0), MCL_K_AREA);
+  const int K = min(max(__float_as_int(ws[HDR_K]), 0), CALIB_K_AREA);
   const double* th = (const double*)(ws + HDR_TH);
   const float* G = ws + HDR_G;
   float sa = 0.f, su = 0.f;
@@ -488,7 +307,7 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_bwd_kernel(const ACT* __re
           a += p * (gb[c0 + j] + (logf(p + MCL_EPS) + p / (p + MCL_EPS)));
         }
     }
-    a = block_sum(a, red);
+    a = block_sum_inorder4(a, red);
     const float pm = expf((float)row[am] - mx) * is;
     for (int c0 = threadIdx.x * V; c0 < C; c0 += MCL_THREADS * V) {
       float v[V], d[V];
@@ -507,12 +326,8 @@ __global__ __launch_bounds__(MCL_THREADS) void avu_mc_bwd_kernel(const ACT* __re
   }
 }
 
-inline bool on_grid(const void* p, int C, int esize) {
-  return (((uintptr_t)p) & 15) == 0 && (C % (16 / esize)) == 0;
-}
-
 inline size_t ce_floats(int S, int B) { return (size_t)B + 2 * (size_t)S * B; }
-inline size_t avu_floats(int S, int B) { return (size_t)MCL_HDR_FLOATS + (size_t)B * MCL_ROW_FLOATS + 2 * (size_t)S * B; }
+inline size_t avu_floats(int S, int B) { return (size_t)CALIB_HDR_FLOATS + (size_t)B * CALIB_ROW_FLOATS + 2 * (size_t)S * B; }
 
 inline int check_shape(int S, int B, int C) {
   if (S < 1 || S > BTX_MCLOSS_MAX_S || B < 1 || C < 1) return BTX_E_SHAPE;
@@ -536,18 +351,17 @@ int btx_mc_ce_fwd(const void* logits, const int64_t* labels, int S, int B, int C
   if (!logits || !labels || !out || !ws) return BTX_E_NULL;
   if (const int rc = check_shape(S, B, C)) return rc;
   if ((reduce != 0 && reduce != 1) || !(label_smoothing >= 0.f && label_smoothing < 1.f)) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if (ws_bytes < 4 * ce_floats(S, B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 3) return BTX_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(mc_ce_row_kernel<float>, dim3(B), dim3(MCL_THREADS), 0, st, (const float*)logits, (const long long*)labels,
-                       S, B, C, reduce, label_smoothing, on_grid(logits, C, 4), (float*)ws);
-  else
-    hipLaunchKernelGGL(mc_ce_row_kernel<__bf16>, dim3(B), dim3(MCL_THREADS), 0, st, (const __bf16*)logits,
-                       (const long long*)labels, S, B, C, reduce, label_smoothing, on_grid(logits, C, 2), (float*)ws);
-  hipLaunchKernelGGL(mc_ce_fold_kernel, dim3(1), dim3(MCL_THREADS), 0, st, (const float*)ws, B, inv_b, kl, out);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(mc_ce_row_kernel<T>, dim3(B), dim3(MCL_THREADS), 0, st, (const T*)logits, (const long long*)labels, S, B, C,
+                       reduce, label_smoothing, on_grid(logits, C, esize), (float*)ws);
+    hipLaunchKernelGGL(mc_ce_fold_kernel, dim3(1), dim3(MCL_THREADS), 0, st, (const float*)ws, B, inv_b, kl, out);
+  });
 }
 
 int btx_mc_ce_bwd(const void* logits, const int64_t* labels, int S, int B, int C, int act_dtype, int reduce, float label_smoothing,
@@ -555,19 +369,16 @@ int btx_mc_ce_bwd(const void* logits, const int64_t* labels, int S, int B, int C
   if (!logits || !labels || !g_loss || !ws || !dlogits) return BTX_E_NULL;
   if (const int rc = check_shape(S, B, C)) return rc;
   if ((reduce != 0 && reduce != 1) || !(label_smoothing >= 0.f && label_smoothing < 1.f)) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if (ws_bytes < 4 * ce_floats(S, B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 3) return BTX_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(mc_ce_bwd_kernel<float>, dim3(B), dim3(MCL_THREADS), 0, st, (const float*)logits, (const long long*)labels,
-                       S, B, C, reduce, label_smoothing, inv_b, on_grid(logits, C, 4) && on_grid(dlogits, C, 4), g_loss,
-                       (const float*)ws, (float*)dlogits);
-  else
-    hipLaunchKernelGGL(mc_ce_bwd_kernel<__bf16>, dim3(B), dim3(MCL_THREADS), 0, st, (const __bf16*)logits,
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(mc_ce_bwd_kernel<T>, dim3(B), dim3(MCL_THREADS), 0, (hipStream_t)stream, (const T*)logits,
                        (const long long*)labels, S, B, C, reduce, label_smoothing, inv_b,
-                       on_grid(logits, C, 2) && on_grid(dlogits, C, 2), g_loss, (const float*)ws, (__bf16*)dlogits);
-  return (int)hipGetLastError();
+                       on_grid(logits, C, esize) && on_grid(dlogits, C, esize), g_loss, (const float*)ws, (T*)dlogits);
+  });
 }
 
 int btx_avu_mc_fwd(const void* logits, const int64_t* labels, int S, int B, int C, int act_dtype, int area, float th,
@@ -576,19 +387,19 @@ int btx_avu_mc_fwd(const void* logits, const int64_t* labels, int S, int B, int 
   if (const int rc = check_shape(S, B, C)) return rc;
   if (C > BTX_AVU_MC_MAX_CLASSES) return BTX_E_UNSUPPORTED;
   if (area != 0 && area != 1) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if (ws_bytes < 4 * avu_floats(S, B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;  // the header holds the thresholds as doubles
   hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(avu_mc_row_kernel<float>, dim3(B), dim3(MCL_THREADS), 0, st, (const float*)logits, (const long long*)labels,
-                       S, B, C, on_grid(logits, C, 4), (float*)ws);
-  else
-    hipLaunchKernelGGL(avu_mc_row_kernel<__bf16>, dim3(B), dim3(MCL_THREADS), 0, st, (const __bf16*)logits,
-                       (const long long*)labels, S, B, C, on_grid(logits, C, 2), (float*)ws);
-  hipLaunchKernelGGL(avu_mc_fold_kernel, dim3(1), dim3(MCL_FOLD_THREADS), 0, st, B, area ? MCL_K_AREA : 1, th, th_dev, beta, out,
-                     (float*)ws);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(avu_mc_row_kernel<T>, dim3(B), dim3(MCL_THREADS), 0, st, (const T*)logits, (const long long*)labels, S, B, C,
+                       on_grid(logits, C, esize), (float*)ws);
+    // the fold of btx_calib.hip on the records above.  Next to what the backward reads (HDR_DLDR, HDR_K, HDR_G, HDR_TH) it stores
+    // HDR_LOSS, HDR_R and HDR_THA: inside the header avu_floats() reserves, read by no kernel of this unit.
+    btx::launch_avu_fold(B, area, th, th_dev, beta, out, (float*)ws, st);
+  });
 }
 
 int btx_avu_mc_bwd(const void* logits, int S, int B, int C, int act_dtype, const float* g_loss, const float* g_r, const void* ws,
@@ -596,19 +407,17 @@ int btx_avu_mc_bwd(const void* logits, int S, int B, int C, int act_dtype, const
   if (!logits || !ws || !dlogits || (!g_loss && !g_r)) return BTX_E_NULL;
   if (const int rc = check_shape(S, B, C)) return rc;
   if (C > BTX_AVU_MC_MAX_CLASSES) return BTX_E_UNSUPPORTED;  // the backward's LDS row stays below 64 KiB: no per-function opt-in
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if (ws_bytes < 4 * avu_floats(S, B)) return BTX_E_WORKSPACE;
   if (((uintptr_t)ws) & 7) return BTX_E_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  const bool f32 = act_dtype == BTX_ACT_F32;
   const size_t lds = (((size_t)C + 7) & ~(size_t)7) * 4;  // the row of dH/dp at pbar: inside the 64 KiB every kernel may use
-  if (f32)
-    hipLaunchKernelGGL(avu_mc_bwd_kernel<float>, dim3(B), dim3(MCL_THREADS), lds, st, (const float*)logits, S, B, C,
-                       on_grid(logits, C, 4) && on_grid(dlogits, C, 4), g_loss, g_r, (const float*)ws, (float*)dlogits);
-  else
-    hipLaunchKernelGGL(avu_mc_bwd_kernel<__bf16>, dim3(B), dim3(MCL_THREADS), lds, st, (const __bf16*)logits, S, B, C,
-                       on_grid(logits, C, 2) && on_grid(dlogits, C, 2), g_loss, g_r, (const float*)ws, (__bf16*)dlogits);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(avu_mc_bwd_kernel<T>, dim3(B), dim3(MCL_THREADS), lds, (hipStream_t)stream, (const T*)logits, S, B, C,
+                       on_grid(logits, C, esize) && on_grid(dlogits, C, esize), g_loss, g_r, (const float*)ws, (T*)dlogits);
+  });
 }
 
 }  // extern "C"
+

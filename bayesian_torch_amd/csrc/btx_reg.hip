@@ -7,12 +7,10 @@
 // Output layout: W = 2 D with has_var (columns [0, D) the mean m, [D, 2 D) the log-variance s, Kendall & Gal), W = D without.
 // Per-element arithmetic is f32 in the loss head and f64 in the evaluator, every operation rounded once: the unit is built with
 // -ffp-contract=off.  Sums: element terms widen to double; one workgroup of 256 threads owns a chunk of REG_CHUNK elements, thread
-// t adds e = t, t + 256, ... in order from zero, a xor butterfly inside the wave, (w0 + w1) + (w2 + w3); a one-workgroup fold adds
-// the chunks' partials (lane l: l, l + 64, ...) with the same butterfly.  Shapes fixed by the element count alone: no atomics, no
-// "last block" counters, no host read.  Plain vector stores only.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/btx.h"
+// t adds e = t, t + 256, ... in order from zero, a xor butterfly inside the wave, (w0 + w1) + (w2 + w3) (block_sum_pairwise4 of
+// btx_heads.h); a one-workgroup fold adds the chunks' partials (lane l: l, l + 64, ...) with the same butterfly.  Shapes fixed by
+// the element count alone: no atomics, no "last block" counters, no host read.  Plain vector stores only.
+#include "btx_heads.h"
 
 #define REG_THREADS 256
 #define REG_CHUNK 4096
@@ -23,48 +21,6 @@
 #define REG_TWO_PI 6.283185307179586
 
 namespace {
-
-template <typename ACT> struct Vw;
-template <> struct Vw<float> { static constexpr int V = 4; };
-template <> struct Vw<__bf16> { static constexpr int V = 8; };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// the sum of a 256-thread workgroup: valid in thread 0.  `part`: 4 doubles of LDS.
-__device__ __forceinline__ double block_sum4(double v, double* part) {
-  v = wave_sum(v);
-  __syncthreads();  // part may still be read from the previous reduction
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// V consecutive values from p: one 16-byte load when `vec`, else element by element with the tail (n valid) left at 0
-template <typename ACT>
-__device__ __forceinline__ void load_v(const ACT* __restrict__ p, int n, bool vec, float* v) {
-  constexpr int V = Vw<ACT>::V;
-  if (vec) {
-    if constexpr (sizeof(ACT) == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(p);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      const uint4 q = *reinterpret_cast<const uint4*>(p);
-      const unsigned int w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        v[2 * j] = __uint_as_float(w[j] << 16);
-        v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < V; ++j) v[j] = (j < n) ? (float)p[j] : 0.f;
-  }
-}
 
 // ---- MC moment statistics ---------------------------------------------------------------------------------------------
 // A thread owns the elements e0 .. e0 + V - 1 (V = 16 bytes of outputs) and folds the lanes in order, so `lanes` samples in one
@@ -97,7 +53,7 @@ __global__ __launch_bounds__(REG_THREADS) void moments_kernel(const ACT* __restr
     for (int k = 0; k < lanes; ++k) {
       const ACT* row = out + ((size_t)k * bs + b) * (size_t)W + d;
       float m[V];
-      load_v<ACT>(row, V, true, m);
+      load_v<ACT>(row, 0, V, true, m);
 #pragma unroll
       for (int j = 0; j < V; ++j) {
         const double md = (double)m[j];
@@ -106,7 +62,7 @@ __global__ __launch_bounds__(REG_THREADS) void moments_kernel(const ACT* __restr
       }
       if (has_var) {
         float s[V];
-        load_v<ACT>(row + D, V, true, s);
+        load_v<ACT>(row + D, 0, V, true, s);
 #pragma unroll
         for (int j = 0; j < V; ++j) sv[j] += (double)expf(s[j]);
       }
@@ -191,7 +147,7 @@ __global__ __launch_bounds__(REG_THREADS) void gnll_chunk_kernel(const ACT* __re
     }
     acc += term;
   }
-  const double t = block_sum4(acc, part);
+  const double t = block_sum_pairwise4(acc, part);
   if (threadIdx.x == 0) ws[blockIdx.x] = t;
 }
 
@@ -301,7 +257,7 @@ __global__ __launch_bounds__(REG_THREADS) void reg_eval_chunk_kernel(const doubl
   }
 #pragma unroll
   for (int j = 0; j < REG_EVAL_Q; ++j) {
-    const double t = block_sum4(a[j], part);
+    const double t = block_sum_pairwise4(a[j], part);
     if (threadIdx.x == 0) ws[(size_t)blockIdx.x * REG_EVAL_Q + j] = t;
   }
 }
@@ -325,8 +281,6 @@ __global__ __launch_bounds__(REG_FOLD_THREADS) void reg_eval_fold_kernel(const d
   }
 }
 
-inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
 inline int check_reg_shape(long long rows, int D, int has_var) {
   if (rows < 1 || D < 1 || (has_var != 0 && has_var != 1)) return BTX_E_SHAPE;
   if (rows * (long long)D > 2147483647LL - 2) return BTX_E_UNSUPPORTED;
@@ -344,21 +298,18 @@ int btx_mc_moments_lanes(const void* out, int lanes, int bs, int D, int has_var,
   if (!out || !packed) return BTX_E_NULL;
   if (lanes < 1 || bs < 1) return BTX_E_SHAPE;
   if (const int rc = check_reg_shape(bs, D, has_var)) return rc;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
-  const int esize = act_dtype == BTX_ACT_F32 ? 4 : 2;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if ((((uintptr_t)out) & (uintptr_t)(esize - 1)) || (((uintptr_t)packed) & 7)) return BTX_E_ALIGN;  // below the element types' own
   const int W = has_var ? 2 * D : D, V = 16 / esize;
   const long long N = (long long)bs * D;
-  const bool vec = aligned16(out) && aligned16(packed) && (D % V) == 0;  // then N % V == 0 and every block of packed is on the grid
+  const bool vec = on_grid(out, D, esize) && aligned16(packed);  // then N % V == 0 and every block of packed is on the grid
   const unsigned grid = (unsigned)((N + (long long)REG_THREADS * V - 1) / ((long long)REG_THREADS * V));
-  hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(moments_kernel<float>, dim3(grid), dim3(REG_THREADS), 0, st, (const float*)out, lanes, bs, D, W, has_var, kl, vec,
-                       packed);
-  else
-    hipLaunchKernelGGL(moments_kernel<__bf16>, dim3(grid), dim3(REG_THREADS), 0, st, (const __bf16*)out, lanes, bs, D, W, has_var, kl,
-                       vec, packed);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(moments_kernel<T>, dim3(grid), dim3(REG_THREADS), 0, (hipStream_t)stream, (const T*)out, lanes, bs, D, W,
+                       has_var, kl, vec, packed);
+  });
 }
 
 size_t btx_mc_gnll_workspace_bytes(int B, int D) {
@@ -372,8 +323,8 @@ static int gnll_check(const void* stack, const float* target, int S, int B, int 
   if (S < 1 || S > BTX_MCLOSS_MAX_S || (reduce != 0 && reduce != 1)) return BTX_E_SHAPE;
   if (const int rc = check_reg_shape(B, D, has_var)) return rc;
   if (!has_var && !(noise_var > 0.f)) return BTX_E_SHAPE;
-  if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
-  const int esize = act_dtype == BTX_ACT_F32 ? 4 : 2;
+  const int esize = act_esize(act_dtype);
+  if (!esize) return BTX_E_DTYPE;
   if ((((uintptr_t)stack) & (uintptr_t)(esize - 1)) || (((uintptr_t)target) & 3)) return BTX_E_ALIGN;
   return 0;
 }
@@ -391,34 +342,28 @@ int btx_mc_gnll_fwd(const void* stack, const float* target, int S, int B, int D,
   const double div = reduce ? (double)S * (double)B : (double)B;
   const double add = full ? 0.5 * 1.8378770664093453 * (double)D : 0.0;  // 0.5 log(2 pi) D
   hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(gnll_chunk_kernel<float>, dim3(nchunks), dim3(REG_THREADS), 0, st, (const float*)stack, target, S, B, D, W,
-                       has_var, s0, reduce, (double*)ws);
-  else
-    hipLaunchKernelGGL(gnll_chunk_kernel<__bf16>, dim3(nchunks), dim3(REG_THREADS), 0, st, (const __bf16*)stack, target, S, B, D, W,
-                       has_var, s0, reduce, (double*)ws);
-  hipLaunchKernelGGL(gnll_fold_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, nchunks, div, add, (double)B, kl, out);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(gnll_chunk_kernel<T>, dim3(nchunks), dim3(REG_THREADS), 0, st, (const T*)stack, target, S, B, D, W, has_var, s0,
+                       reduce, (double*)ws);
+    hipLaunchKernelGGL(gnll_fold_kernel, dim3(1), dim3(64), 0, st, (const double*)ws, nchunks, div, add, (double)B, kl, out);
+  });
 }
 
 int btx_mc_gnll_bwd(const void* stack, const float* target, int S, int B, int D, int has_var, int act_dtype, int reduce, float noise_var,
                     const float* g_loss, void* dstack, void* stream) {
   if (!g_loss || !dstack) return BTX_E_NULL;
   if (const int rc = gnll_check(stack, target, S, B, D, has_var, act_dtype, reduce, noise_var)) return rc;
-  const int esize = act_dtype == BTX_ACT_F32 ? 4 : 2;
-  if ((((uintptr_t)dstack) & (uintptr_t)(esize - 1)) || (((uintptr_t)g_loss) & 3)) return BTX_E_ALIGN;
+  if ((((uintptr_t)dstack) & (uintptr_t)(act_esize(act_dtype) - 1)) || (((uintptr_t)g_loss) & 3)) return BTX_E_ALIGN;
   const long long N = (long long)B * D;
   const int W = has_var ? 2 * D : D;
   const float s0 = has_var ? 0.f : logf(noise_var);
   const unsigned grid = (unsigned)((N + REG_THREADS - 1) / REG_THREADS);
-  hipStream_t st = (hipStream_t)stream;
-  if (act_dtype == BTX_ACT_F32)
-    hipLaunchKernelGGL(gnll_bwd_kernel<float>, dim3(grid), dim3(REG_THREADS), 0, st, (const float*)stack, target, S, B, D, W, has_var, s0,
-                       reduce, g_loss, (float*)dstack);
-  else
-    hipLaunchKernelGGL(gnll_bwd_kernel<__bf16>, dim3(grid), dim3(REG_THREADS), 0, st, (const __bf16*)stack, target, S, B, D, W, has_var,
-                       s0, reduce, g_loss, (__bf16*)dstack);
-  return (int)hipGetLastError();
+  return launch_by_act(act_dtype, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(gnll_bwd_kernel<T>, dim3(grid), dim3(REG_THREADS), 0, (hipStream_t)stream, (const T*)stack, target, S, B, D, W,
+                       has_var, s0, reduce, g_loss, (T*)dstack);
+  });
 }
 
 size_t btx_reg_eval_workspace_bytes(int bs, int D) {

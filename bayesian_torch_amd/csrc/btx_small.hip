@@ -5,6 +5,7 @@
 #include <string.h>
 #include "../../include/btx.h"
 #include "btx_contract.h"
+#include "btx_heads.h"  // launch_by_act
 #include "btx_rng.h"
 
 using namespace btx;
@@ -549,15 +550,6 @@ static int maxpool_grid(const void* a, const void* b, const uint8_t* idx, bool w
   const long long blocks = (pg->total + 255) / 256;
   pg->blocks = (int)(blocks > 262144 ? 262144 : blocks);
   return 0;
-}
-
-// launches through f(T()), T the element type behind a BTX_ACT_* code
-template <typename F>
-static int launch_by_act(int dtype, F f) {
-  if (dtype == BTX_ACT_BF16) f((__bf16)0.f);
-  else if (dtype == BTX_ACT_F32) f(0.f);
-  else return BTX_E_DTYPE;
-  return (int)hipGetLastError();
 }
 
 extern "C" {

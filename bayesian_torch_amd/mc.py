@@ -597,7 +597,94 @@ def _eval_fold_torch(state, rec, topk, nbins, th, use_mi, capacity):
     return state
 
 
-class Evaluator:
+class _DeviceEvaluator:
+    """What Evaluator and RegressionEvaluator share: a float64 state vector on one device with two cursor words (records seen,
+    records dropped), a float32 record buffer [capacity, _WIDTH] of which the rows below the cursor are kept, a grow-only kernel
+    workspace and a scratch packed vector.  A subclass sets _CURSOR / _DROPPED / _WIDTH and supplies _state_numel(),
+    _alloc_settings(dev) (its device-side settings), _settings() (what merge compares), update, compute and records."""
+    _CURSOR = _DROPPED = _WIDTH = None
+
+    def _init_buffers(self, capacity, device):
+        self.capacity = int(capacity)
+        self.device = None
+        self.state = self.records_buffer = self.workspace = self._scratch = None
+        if device is not None:
+            self._alloc(torch.device(device))
+
+    def _alloc(self, dev):
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.state = torch.zeros(self._state_numel(), dtype=torch.float64, device=dev)
+        self._alloc_settings(dev)
+        if self.capacity:
+            self.records_buffer = torch.zeros(self.capacity, self._WIDTH, dtype=torch.float32, device=dev)
+
+    def _reserve(self, n):
+        n = int(n)
+        if n <= self.capacity:
+            return
+        new = max(n, 2 * self.capacity)
+        if self.device is not None:
+            buf = torch.zeros(new, self._WIDTH, dtype=torch.float32, device=self.device)
+            if self.records_buffer is not None:
+                buf[:self.capacity] = self.records_buffer
+            self.records_buffer = buf
+        self.capacity = new
+
+    def _workspace_for(self, need, dtype):
+        """the workspace, grown to `need` bytes: (pointer, bytes)"""
+        ws = self.workspace
+        if ws is None or ws.numel() * ws.element_size() < need:
+            ws = self.workspace = torch.empty(need // (torch.finfo(dtype).bits // 8), dtype=dtype, device=self.device)
+        return ws.data_ptr(), ws.numel() * ws.element_size()
+
+    def _records_args(self):
+        """(pointer or None, rows) of the record buffer, as the kernels take them"""
+        rec = self.records_buffer
+        return (None, 0) if rec is None else (rec.data_ptr(), rec.shape[0])
+
+    def _zeroed_scratch(self, n, dtype, dev):
+        if self._scratch is None or self._scratch.numel() != n or self._scratch.device != dev:
+            self._scratch = torch.zeros(n, dtype=dtype, device=dev)
+        return self._scratch.zero_()
+
+    def reset(self):
+        if self.state is not None:
+            self.state.zero_()
+        return self
+
+    def _with_cursor_kept(self, op):
+        """op(state), which sums into the state in place; the cursor words stay this evaluator's own"""
+        keep = self.state[self._CURSOR:self._DROPPED + 1].clone()
+        op(self.state)
+        self.state[self._CURSOR:self._DROPPED + 1] = keep
+
+    def _merge(self, other):
+        if other._settings() != self._settings():
+            raise ValueError("merge of evaluators with different settings")
+        if other.state is None:
+            return self
+        if self.device is None:
+            self._alloc(other.device)
+        self._with_cursor_kept(lambda s: s.add_(other.state.to(self.device)))
+        return self
+
+    def _reduce(self, group):
+        if dist.is_available() and dist.is_initialized():
+            self._with_cursor_kept(lambda s: dist.all_reduce(s, op=dist.ReduceOp.SUM, group=group))
+        return self
+
+    def _kept_records(self):
+        """numpy [kept, _WIDTH]: the rows of the record buffer below the cursor"""
+        import numpy as np
+        if self.state is None or self.records_buffer is None:
+            return np.zeros((0, self._WIDTH), np.float32)
+        kept = min(int(self.state[self._CURSOR].item()), self.records_buffer.shape[0])
+        return self.records_buffer[:kept].cpu().numpy()
+
+
+class Evaluator(_DeviceEvaluator):
     """Classification metrics of MC predictions, accumulated on the device (BTX-EVAL v1).
 
         ev = Evaluator(1000, thresholds=[0.5, 1.0], capacity=50000)
@@ -627,20 +714,19 @@ class Evaluator:
         th = [] if thresholds is None else [float(t) for t in torch.as_tensor(thresholds).reshape(-1).tolist()]
         if len(th) > _lib.MC_EVAL_MAX_THRESHOLDS:
             raise ValueError("at most %d thresholds" % _lib.MC_EVAL_MAX_THRESHOLDS)
-        self.T, self._th_init, self.capacity = len(th), th, int(capacity)
-        self.device = None
-        self.state = self.th = self.records_buffer = self.workspace = self._scratch = None
-        if device is not None:
-            self._alloc(torch.device(device))
+        self.T, self._th_init, self.th = len(th), th, None
+        self._init_buffers(capacity, device)
 
-    def _alloc(self, dev):
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        self.state = torch.zeros(EVAL_HEADER + 3 * self.bins + 4 * self.T, dtype=torch.float64, device=dev)
+    _CURSOR, _DROPPED, _WIDTH = EVAL_CURSOR, EVAL_DROPPED, 8
+
+    def _state_numel(self):
+        return EVAL_HEADER + 3 * self.bins + 4 * self.T
+
+    def _alloc_settings(self, dev):
         self.th = torch.tensor(self._th_init, dtype=torch.float32, device=dev)
-        if self.capacity:
-            self.records_buffer = torch.zeros(self.capacity, 8, dtype=torch.float32, device=dev)
+
+    def _settings(self):
+        return self.num_classes, self.bins, self.T, self.use_mi, self.topk
 
     def set_thresholds(self, thresholds):
         """rewrite the thresholds in place (same count): a captured update() reads the new values"""
@@ -649,16 +735,7 @@ class Evaluator:
     def reserve(self, rows):
         """grow the record buffer to hold at least `rows` records (a new allocation: not for use between replays of a captured
         update)"""
-        rows = int(rows)
-        if rows <= self.capacity:
-            return
-        new = max(rows, 2 * self.capacity)
-        if self.device is not None:
-            buf = torch.zeros(new, 8, dtype=torch.float32, device=self.device)
-            if self.records_buffer is not None:
-                buf[:self.capacity] = self.records_buffer
-            self.records_buffer = buf
-        self.capacity = new
+        self._reserve(rows)
 
     def update(self, packed, labels):
         """fold one batch: packed [2 * bs * C + bs + 2] f32 and labels [bs] int64, on one device.  GPU: btx_mc_eval, two launches
@@ -675,14 +752,9 @@ class Evaluator:
             pk = packed.contiguous()
             lb = labels.reshape(bs).to(device=packed.device, dtype=torch.int64).contiguous()  # the kernel reads device memory
             L = _lib.lib()
-            need = L.btx_mc_eval_workspace_bytes(bs)
-            if self.workspace is None or self.workspace.numel() * 4 < need:
-                self.workspace = torch.empty(need // 4, dtype=torch.float32, device=self.device)
-            rec = self.records_buffer
             _lib.check(L.btx_mc_eval(pk.data_ptr(), lb.data_ptr(), bs, C, self.topk, self.bins, self.th.data_ptr() if self.T else None,
-                                     self.T, int(self.use_mi), self.state.data_ptr(), self.state.numel(),
-                                     rec.data_ptr() if rec is not None else None, rec.shape[0] if rec is not None else 0,
-                                     self.workspace.data_ptr(), self.workspace.numel() * 4,
+                                     self.T, int(self.use_mi), self.state.data_ptr(), self.state.numel(), *self._records_args(),
+                                     *self._workspace_for(L.btx_mc_eval_workspace_bytes(bs), torch.float32),
                                      torch.cuda.current_stream(self.device).cuda_stream))
             return self
         rec = _eval_rows_torch(packed, labels.to(packed.device), bs, C)
@@ -698,45 +770,20 @@ class Evaluator:
         """one deterministic (or single-sample) forward, the reference's validate() form: the logits are accumulated into a
         zeroed scratch packed vector (accumulate: softmax and entropy of ONE sample), then update()"""
         bs, C = logits.shape
-        n = packed_numel(bs, C)
-        if self._scratch is None or self._scratch.numel() != n or self._scratch.device != logits.device:
-            self._scratch = torch.zeros(n, dtype=torch.float32, device=logits.device)
-        self._scratch.zero_()
-        accumulate(self._scratch, logits)
-        return self.update(self._scratch, labels)
-
-    def reset(self):
-        if self.state is not None:
-            self.state.zero_()
-        return self
-
-    def _add_state(self, other_state):
-        keep = self.state[EVAL_CURSOR:EVAL_DROPPED + 1].clone()
-        self.state += other_state
-        self.state[EVAL_CURSOR:EVAL_DROPPED + 1] = keep
+        scratch = self._zeroed_scratch(packed_numel(bs, C), torch.float32, logits.device)
+        accumulate(scratch, logits)
+        return self.update(scratch, labels)
 
     def merge(self, other):
         """add another evaluator's state (same classes / bins / thresholds).  The record cursor, the dropped count and the
         records themselves stay this evaluator's own."""
-        if (other.num_classes, other.bins, other.T, other.use_mi, other.topk) != (self.num_classes, self.bins, self.T, self.use_mi,
-                                                                                 self.topk):
-            raise ValueError("merge of evaluators with different settings")
-        if other.state is None:
-            return self
-        if self.device is None:
-            self._alloc(other.device)
-        self._add_state(other.state.to(self.device))
-        return self
+        return self._merge(other)
 
     def reduce(self, group=None):
         """ONE float64 all_reduce(SUM) of the state over `group`, for a validation set sharded over ranks: afterwards every
         rank's compute() is that of the whole set.  The records stay local — each rank keeps the examples it saw, with its own
         cursor and dropped count; nothing gathers them."""
-        if dist.is_available() and dist.is_initialized():
-            keep = self.state[EVAL_CURSOR:EVAL_DROPPED + 1].clone()
-            dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
-            self.state[EVAL_CURSOR:EVAL_DROPPED + 1] = keep
-        return self
+        return self._reduce(group)
 
     def compute(self):
         """-> dict of the metrics; the one host read (the state vector)"""
@@ -768,11 +815,7 @@ class Evaluator:
         label itself is not kept, and utils.avuc_loss.eval_avu(r["pred"], r["target"], r["entropy"]) / accuracy_vs_uncertainty only
         compare it with pred."""
         import numpy as np
-        if self.state is None or self.records_buffer is None:
-            rec = np.zeros((0, 8), np.float32)
-        else:
-            kept = min(int(self.state[EVAL_CURSOR].item()), self.records_buffer.shape[0])
-            rec = self.records_buffer[:kept].cpu().numpy()
+        rec = self._kept_records()
         rec = rec[rec[:, 1] >= 0]
         out = {name: rec[:, j].copy() for j, name in enumerate(EVAL_RECORD)}
         out["pred"], out["rank"] = out["pred"].astype(np.int64), out["rank"].astype(np.int64)
@@ -815,7 +858,7 @@ def normal_quantiles_squared(levels):
     return z * z
 
 
-class RegressionEvaluator:
+class RegressionEvaluator(_DeviceEvaluator):
     """Regression metrics of MC predictions, accumulated on the device (BTX-REG v1).
 
         st = GaussianStats("log")
@@ -841,34 +884,24 @@ class RegressionEvaluator:
             raise ValueError("noise_var must not be negative")
         if not float(min_var) > 0.0:
             raise ValueError("min_var must be positive")
-        self.K, self.noise_var, self.min_var, self.capacity = len(self.levels), noise_var, float(min_var), int(capacity)
-        self.device = None
-        self.state = self.z2 = self.records_buffer = self.workspace = self._scratch = None
-        if device is not None:
-            self._alloc(torch.device(device))
+        self.K, self.noise_var, self.min_var, self.z2 = len(self.levels), noise_var, float(min_var), None
+        self._init_buffers(capacity, device)
 
-    def _alloc(self, dev):
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.device = dev
-        self.state = torch.zeros(REG_HEADER + self.K, dtype=torch.float64, device=dev)
+    _CURSOR, _DROPPED, _WIDTH = REG_CURSOR, REG_DROPPED, 4
+
+    def _state_numel(self):
+        return REG_HEADER + self.K
+
+    def _alloc_settings(self, dev):
         self.z2 = normal_quantiles_squared(self.levels).to(dev)
-        if self.capacity:
-            self.records_buffer = torch.zeros(self.capacity, 4, dtype=torch.float32, device=dev)
+
+    def _settings(self):
+        return self.dims, self.levels
 
     def reserve(self, elements):
         """grow the record buffer to hold at least `elements` records (a new allocation: not for use between replays of a captured
         update)"""
-        elements = int(elements)
-        if elements <= self.capacity:
-            return
-        new = max(elements, 2 * self.capacity)
-        if self.device is not None:
-            buf = torch.zeros(new, 4, dtype=torch.float32, device=self.device)
-            if self.records_buffer is not None:
-                buf[:self.capacity] = self.records_buffer
-            self.records_buffer = buf
-        self.capacity = new
+        self._reserve(elements)
 
     def update(self, packed, target):
         """fold one batch: packed [3 * bs * dims + 2] float64 and target [bs, dims] float32, on one device.  GPU:
@@ -890,14 +923,9 @@ class RegressionEvaluator:
         if packed.is_cuda:
             pk = packed.contiguous()
             L = _lib.lib()
-            need = L.btx_reg_eval_workspace_bytes(bs, D)
-            if self.workspace is None or self.workspace.numel() * 8 < need:
-                self.workspace = torch.empty(need // 8, dtype=torch.float64, device=self.device)
-            rec = self.records_buffer
             _lib.check(L.btx_reg_eval_update(pk.data_ptr(), y.data_ptr(), bs, D, nv, self.min_var, self.z2.data_ptr() if self.K else None,
-                                             self.K, self.state.data_ptr(), self.state.numel(),
-                                             rec.data_ptr() if rec is not None else None, rec.shape[0] if rec is not None else 0,
-                                             self.workspace.data_ptr(), self.workspace.numel() * 8,
+                                             self.K, self.state.data_ptr(), self.state.numel(), *self._records_args(),
+                                             *self._workspace_for(L.btx_reg_eval_workspace_bytes(bs, D), torch.float64),
                                              torch.cuda.current_stream(self.device).cuda_stream))
             return self
         n = packed[3 * N + 1]
@@ -934,39 +962,18 @@ class RegressionEvaluator:
         if W not in (self.dims, 2 * self.dims):
             raise ValueError("out must be [bs, %d] or [bs, %d]" % (self.dims, 2 * self.dims))
         st = GaussianStats("log" if W == 2 * self.dims else None)
-        n = st.numel(bs, W)
-        if self._scratch is None or self._scratch.numel() != n or self._scratch.device != out.device:
-            self._scratch = torch.zeros(n, dtype=torch.float64, device=out.device)
-        self._scratch.zero_()
-        st.accumulate(self._scratch, out)
-        return self.update(self._scratch, target)
-
-    def reset(self):
-        if self.state is not None:
-            self.state.zero_()
-        return self
+        scratch = self._zeroed_scratch(st.numel(bs, W), torch.float64, out.device)
+        st.accumulate(scratch, out)
+        return self.update(scratch, target)
 
     def merge(self, other):
         """add another evaluator's state (same dims / levels).  The record cursor, the dropped count and the records themselves stay
         this evaluator's own."""
-        if (other.dims, other.levels) != (self.dims, self.levels):
-            raise ValueError("merge of evaluators with different settings")
-        if other.state is None:
-            return self
-        if self.device is None:
-            self._alloc(other.device)
-        keep = self.state[REG_CURSOR:REG_DROPPED + 1].clone()
-        self.state += other.state.to(self.device)
-        self.state[REG_CURSOR:REG_DROPPED + 1] = keep
-        return self
+        return self._merge(other)
 
     def reduce(self, group=None):
         """ONE float64 all_reduce(SUM) of the state over `group`; the cursor words and the records stay local"""
-        if dist.is_available() and dist.is_initialized():
-            keep = self.state[REG_CURSOR:REG_DROPPED + 1].clone()
-            dist.all_reduce(self.state, op=dist.ReduceOp.SUM, group=group)
-            self.state[REG_CURSOR:REG_DROPPED + 1] = keep
-        return self
+        return self._reduce(group)
 
     def compute(self):
         """-> dict of the metrics; the one host read (the state vector)"""
@@ -991,11 +998,7 @@ class RegressionEvaluator:
         """-> dict of numpy float32 arrays [M] over the kept elements, ignored ones left out: mean, epistemic_var, aleatoric_var,
         err, and error = |err|, unc = epistemic_var + aleatoric_var — the vectors uncertainty_calibration_loss.EaULoss takes"""
         import numpy as np
-        if self.state is None or self.records_buffer is None:
-            rec = np.zeros((0, 4), np.float32)
-        else:
-            kept = min(int(self.state[REG_CURSOR].item()), self.records_buffer.shape[0])
-            rec = self.records_buffer[:kept].cpu().numpy()
+        rec = self._kept_records()
         rec = rec[~np.isnan(rec[:, 3])]
         out = {name: rec[:, j].copy() for j, name in enumerate(REG_RECORD)}
         out["error"], out["unc"] = np.abs(out["err"]), out["epistemic_var"] + out["aleatoric_var"]

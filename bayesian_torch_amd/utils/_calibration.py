@@ -148,38 +148,46 @@ def _workspace(B, dev):
     return torch.empty(_lib.lib().btx_calib_workspace_bytes(B) // 4, dtype=torch.float32, device=dev)
 
 
+def _avu_forward(ctx, fwd, ws_bytes, logits, labels, th, beta, area):
+    """forward of AvuFn ([B, C] logits) and AvuMcFn ([S, B, C]): the entry point `fwd` takes the logits' shape as its leading
+    integers and `ws_bytes` all of it but the classes"""
+    lg = logits.contiguous()
+    lb = labels.reshape(-1).contiguous()
+    thf, thd = _th_args(0.0 if area else th, lg.device)
+    L = _lib.lib()
+    ws = torch.empty(getattr(L, ws_bytes)(*lg.shape[:-1]) // 4, dtype=torch.float32, device=lg.device)
+    out = torch.empty(2, dtype=torch.float32, device=lg.device)
+    act = _lib.ACT_BF16 if lg.dtype == torch.bfloat16 else _lib.ACT_F32
+    _lib.check(getattr(L, fwd)(lg.data_ptr(), lb.data_ptr(), *lg.shape, act, 1 if area else 0, thf, _ptr(thd), float(beta),
+                               out.data_ptr(), ws.data_ptr(), ws.numel() * 4, torch.cuda.current_stream(lg.device).cuda_stream))
+    ctx.save_for_backward(lg, ws)
+    ctx.act = act
+    ctx.set_materialize_grads(False)
+    return out[0:1], out[1:2]
+
+
+def _avu_backward(ctx, bwd, g_loss, g_r):
+    lg, ws = ctx.saved_tensors
+    if g_loss is None and g_r is None:
+        return None, None, None, None, None
+    g_loss = None if g_loss is None else g_loss.float().contiguous()
+    g_r = None if g_r is None else g_r.float().contiguous()
+    dl = torch.empty_like(lg)
+    _lib.check(getattr(_lib.lib(), bwd)(lg.data_ptr(), *lg.shape, ctx.act, _ptr(g_loss), _ptr(g_r), ws.data_ptr(), ws.numel() * 4,
+                                        dl.data_ptr(), torch.cuda.current_stream(lg.device).cuda_stream))
+    return dl, None, None, None, None
+
+
 class AvuFn(torch.autograd.Function):
     """(loss [1], r [1]) of [B, C] f32 / bf16 CUDA logits through btx_avu_fwd; both outputs are f32 and carry gradient."""
 
     @staticmethod
     def forward(ctx, logits, labels, th, beta, area):
-        lg = logits.contiguous()
-        lb = labels.reshape(-1).contiguous()
-        B, C = lg.shape
-        thf, thd = _th_args(0.0 if area else th, lg.device)
-        ws = _workspace(B, lg.device)
-        out = torch.empty(2, dtype=torch.float32, device=lg.device)
-        act = _lib.ACT_BF16 if lg.dtype == torch.bfloat16 else _lib.ACT_F32
-        _lib.check(_lib.lib().btx_avu_fwd(lg.data_ptr(), lb.data_ptr(), B, C, act, 1 if area else 0, thf, _ptr(thd), float(beta),
-                                          out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                          torch.cuda.current_stream(lg.device).cuda_stream))
-        ctx.save_for_backward(lg, ws)
-        ctx.act = act
-        ctx.set_materialize_grads(False)
-        return out[0:1], out[1:2]
+        return _avu_forward(ctx, "btx_avu_fwd", "btx_calib_workspace_bytes", logits, labels, th, beta, area)
 
     @staticmethod
     def backward(ctx, g_loss, g_r):
-        lg, ws = ctx.saved_tensors
-        if g_loss is None and g_r is None:
-            return None, None, None, None, None
-        g_loss = None if g_loss is None else g_loss.float().contiguous()
-        g_r = None if g_r is None else g_r.float().contiguous()
-        dl = torch.empty_like(lg)
-        B, C = lg.shape
-        _lib.check(_lib.lib().btx_avu_bwd(lg.data_ptr(), B, C, ctx.act, _ptr(g_loss), _ptr(g_r), ws.data_ptr(), ws.numel() * 4,
-                                          dl.data_ptr(), torch.cuda.current_stream(lg.device).cuda_stream))
-        return dl, None, None, None, None
+        return _avu_backward(ctx, "btx_avu_bwd", g_loss, g_r)
 
 
 class EauFn(torch.autograd.Function):
@@ -234,33 +242,11 @@ class AvuMcFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, stack, labels, th, beta, area):
-        lg = stack.contiguous()
-        lb = labels.reshape(-1).contiguous()
-        S, B, C = lg.shape
-        thf, thd = _th_args(0.0 if area else th, lg.device)
-        ws = torch.empty(_lib.lib().btx_mcloss_workspace_bytes(S, B) // 4, dtype=torch.float32, device=lg.device)
-        out = torch.empty(2, dtype=torch.float32, device=lg.device)
-        act = _lib.ACT_BF16 if lg.dtype == torch.bfloat16 else _lib.ACT_F32
-        _lib.check(_lib.lib().btx_avu_mc_fwd(lg.data_ptr(), lb.data_ptr(), S, B, C, act, 1 if area else 0, thf, _ptr(thd),
-                                             float(beta), out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
-                                             torch.cuda.current_stream(lg.device).cuda_stream))
-        ctx.save_for_backward(lg, ws)
-        ctx.act = act
-        ctx.set_materialize_grads(False)
-        return out[0:1], out[1:2]
+        return _avu_forward(ctx, "btx_avu_mc_fwd", "btx_mcloss_workspace_bytes", stack, labels, th, beta, area)
 
     @staticmethod
     def backward(ctx, g_loss, g_r):
-        lg, ws = ctx.saved_tensors
-        if g_loss is None and g_r is None:
-            return None, None, None, None, None
-        g_loss = None if g_loss is None else g_loss.float().contiguous()
-        g_r = None if g_r is None else g_r.float().contiguous()
-        dl = torch.empty_like(lg)
-        S, B, C = lg.shape
-        _lib.check(_lib.lib().btx_avu_mc_bwd(lg.data_ptr(), S, B, C, ctx.act, _ptr(g_loss), _ptr(g_r), ws.data_ptr(),
-                                             ws.numel() * 4, dl.data_ptr(), torch.cuda.current_stream(lg.device).cuda_stream))
-        return dl, None, None, None, None
+        return _avu_backward(ctx, "btx_avu_mc_bwd", g_loss, g_r)
 
 
 def avu_mc(stack, labels, th, beta, area):

@@ -251,7 +251,13 @@ def _worker(rank, world, port, out_path):
     packed, y, _ = _halves(g)[rank]
     ev = mc.Evaluator(10, thresholds=g["th3"], capacity=24).update(_t(packed), _t(y))
     ev.reduce()
-    torch.save({"state": ev.state, "pred": torch.from_numpy(ev.records()["pred"])}, out_path + str(rank))
+    import reg_model as RM
+    c = RM.eval_case(7, 5, 4, seed=1 + rank)
+    reg = mc.RegressionEvaluator(5, levels=c["levels"], capacity=40).update(torch.from_numpy(c["packed"]), torch.from_numpy(c["y"]))
+    before = reg.state.clone()
+    reg.reduce()
+    torch.save({"state": ev.state, "pred": torch.from_numpy(ev.records()["pred"]), "reg_before": before, "reg_state": reg.state,
+                "reg_err": torch.from_numpy(reg.records()["err"])}, out_path + str(rank))
     dist.destroy_process_group()
 
 
@@ -263,17 +269,63 @@ def _free_port():
     return p
 
 
-def test_reduce_world2_equals_one_pass(tmp_path):
+@pytest.fixture(scope="module")
+def two_ranks(tmp_path_factory):
+    """what the two gloo ranks of _worker saved: ONE spawn for the tests below"""
+    out = str(tmp_path_factory.mktemp("gloo") / "rank")
+    mp.spawn(_worker, args=(2, _free_port(), out), nprocs=2, join=True)
+    return [torch.load(out + str(r)) for r in (0, 1)]
+
+
+def test_reduce_world2_equals_one_pass(two_ranks):
     """a validation set sharded over two ranks: after ONE all_reduce both ranks hold the state of the whole set, and each keeps
     the records of its own shard"""
     from bayesian_torch_amd import mc
     g = M.golden_case("s8_b48_c10")
     one = mc.Evaluator(10, thresholds=g["th3"]).update(_t(g["packed"]), _t(g["labels"]))
-    out = str(tmp_path / "rank")
-    mp.spawn(_worker, args=(2, _free_port(), out), nprocs=2, join=True)
-    got = [torch.load(out + str(r)) for r in (0, 1)]
+    got = two_ranks
     assert torch.equal(got[0]["state"][:M.CURSOR], got[1]["state"][:M.CURSOR])
     for r in (0, 1):
         _assert_states_agree(got[r]["state"].numpy(), one.state.numpy())
         assert got[r]["state"][M.CURSOR] == 24
         assert np.array_equal(got[r]["pred"].numpy(), g["pred"][24 * r:24 * r + 24])
+
+
+def test_regression_reduce_world2_sums_the_states(two_ranks):
+    """RegressionEvaluator.reduce over the same two ranks: both hold the sum of the two states (exact: a two-term float64 sum),
+    each with its own cursor words and the records of its own shard"""
+    import reg_model as RM
+    before = [two_ranks[r]["reg_before"] for r in (0, 1)]
+    for r in (0, 1):
+        want = before[0] + before[1]
+        want[RM.CURSOR:RM.DROPPED + 1] = before[r][RM.CURSOR:RM.DROPPED + 1]
+        assert torch.equal(two_ranks[r]["reg_state"], want)
+        assert want[RM.CURSOR] == 35 and want[RM.DROPPED] == 0
+        y = RM.eval_case(7, 5, 4, seed=1 + r)["y"]
+        assert two_ranks[r]["reg_err"].numel() == int(np.sum(~np.isnan(y)))
+
+
+def test_reset_merge_into_fresh_and_reduce_without_a_group():
+    """the state handling RegressionEvaluator's tests cover, for Evaluator: reset zeroes every word (the cursor too, so records
+    start over), merge allocates an evaluator that saw nothing and skips one that saw nothing, reduce without a process group is a
+    no-op"""
+    from bayesian_torch_amd import mc
+    g = M.golden_case("s5_b33_c2")
+    pk, y = _t(g["packed"]), _t(g["labels"])
+    ev = mc.Evaluator(2, capacity=40).update(pk, y)
+    once, rec = ev.state.clone(), ev.records_buffer.clone()
+    assert ev.reduce() is ev and torch.equal(ev.state, once)
+    assert ev.update(pk, y).reset() is ev and not ev.state.any()
+    ev.update(pk, y)
+    assert torch.equal(ev.state, once) and torch.equal(ev.records_buffer[:33], rec[:33])
+    fresh = mc.Evaluator(2)
+    assert fresh.reset() is fresh and fresh.merge(mc.Evaluator(2)) is fresh and fresh.state is None
+    fresh.merge(ev)
+    want = once.clone()
+    want[M.CURSOR:M.DROPPED + 1] = 0.0  # the cursor words stay local: the fresh evaluator saw no row
+    assert fresh.device == ev.device and torch.equal(fresh.state, want) and fresh.compute()["n"] == once[0]
+    ev.reserve(30)
+    assert ev.capacity == 40  # already large enough
+    held = ev.records_buffer.clone()
+    ev.reserve(41)
+    assert ev.capacity == 80 and torch.equal(ev.records_buffer[:40], held) and not ev.records_buffer[40:].any()

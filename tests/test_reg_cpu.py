@@ -261,6 +261,30 @@ def test_merge_adds_two_states():
         a.merge(mc.RegressionEvaluator(5, levels=(0.5,)))
 
 
+def test_reset_merge_into_fresh_and_reserve():
+    """reset zeroes every word (the cursor too, so records start over); merge allocates an evaluator that saw nothing and skips one
+    that saw nothing; reserve grows the record buffer and keeps what it holds"""
+    mc, _ = _mods()
+    c = RM.eval_case(7, 5, 4, seed=1)
+    pk, y = torch.from_numpy(c["packed"]), torch.from_numpy(c["y"])
+    ev = _evaluator(mc, c, capacity=40).update(pk, y)
+    once, rec = ev.state.clone(), ev.records_buffer.clone()
+    assert ev.update(pk, y).reset() is ev and not ev.state.any()
+    ev.update(pk, y)
+    assert np.array_equal(_bits(ev.state), _bits(once)) and np.array_equal(_bits(ev.records_buffer[:35]), _bits(rec[:35]))
+    fresh = _evaluator(mc, c)
+    assert fresh.reset() is fresh and fresh.merge(_evaluator(mc, c)) is fresh and fresh.state is None
+    fresh.merge(ev)
+    want = once.clone()
+    want[RM.CURSOR:RM.DROPPED + 1] = 0.0  # the cursor words stay local: the fresh evaluator saw no element
+    assert fresh.device == ev.device and torch.equal(fresh.state, want) and fresh.compute()["n"] == once[0]
+    ev.reserve(30)
+    assert ev.capacity == 40  # already large enough
+    held = ev.records_buffer.clone()
+    ev.reserve(41)
+    assert ev.capacity == 80 and np.array_equal(_bits(ev.records_buffer[:40]), _bits(held)) and not ev.records_buffer[40:].any()
+
+
 def test_coverage_of_a_calibrated_predictive_lands_on_the_levels():
     """y ~ N(mean, var) on 4096 elements: the count at level p is Binomial(4096, p); 4 standard deviations"""
     mc, _ = _mods()
