@@ -30,6 +30,10 @@
 // FAST variants (GEN=false) need whole 16-byte granules (C/groups % 8 == 0 for bf16, % 4 for f32, aligned
 // pointers) and generate all noise in-kernel.  GEN=true is the element-wise gather path: any shape, and the
 // explicit-noise parity mode (eps / sign tensors supplied by the caller).
+//
+// KIND == 2 (BTX_KIND_LRT, local reparameterization) reuses the two accumulator sets of Flipout with no weight
+// noise at all: the mean GEMM contracts (mu, x), the variance GEMM (sigma^2, x^2) — x^2 is formed on the fragment registers where
+// Flipout's sign XOR sits — and the store draws ONE normal per output element: y = accm + sqrt(accd) * zeta.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -583,8 +587,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
   auto process_stage = [&](int buf) {
     unsigned char* sb = smem + buf * STAGE_BYTES;
     if (w_thread) {
-      float eps[4];
-      if constexpr (!GEN) {
+      float eps[4] = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (KIND == 2) {
+        // local reparameterization: no weight noise, nothing to draw in the K loop
+      } else if constexpr (!GEN) {
         btx_normal4((uint32_t)(w_idx >> 2), rl.sample, p.layer, 0u, p.seed_lo, p.seed_hi, eps);
       } else {
         if (p.eps_w) {  // parity mode: explicit eps
@@ -605,18 +611,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
         if constexpr (KIND == 0) {
           wm[e] = ok ? __builtin_fmaf(sg, eps[e], wmu_r[e]) : 0.f;
           wd[e] = 0.f;
-        } else {
+        } else if constexpr (KIND == 1) {
           wm[e] = ok ? wmu_r[e] : 0.f;
           wd[e] = ok ? sg * eps[e] : 0.f;
+        } else {  // BTX-LRT v1: sigma^2 = f32(sigma * sigma), rounded once more where the contraction is bf16
+          wm[e] = ok ? wmu_r[e] : 0.f;
+          wd[e] = ok ? sg * sg : 0.f;
         }
       }
       const int wo = (w_row * BN + w_chan) * 16 + w_half * 8;
       if constexpr (PREC == 1) {
         *(u32x2*)(sb + WMU_OFF + wo) = pack_quad_bf16(wm);
-        if constexpr (KIND == 1) *(u32x2*)(sb + WDL_OFF + wo) = pack_quad_bf16(wd);
+        if constexpr (KIND != 0) *(u32x2*)(sb + WDL_OFF + wo) = pack_quad_bf16(wd);
       } else {
         *(u32x4*)(sb + WMU_OFF + wo) = (u32x4){f2u(wm[0]), f2u(wm[1]), f2u(wm[2]), f2u(wm[3])};
-        if constexpr (KIND == 1)
+        if constexpr (KIND != 0)
           *(u32x4*)(sb + WDL_OFF + wo) = (u32x4){f2u(wd[0]), f2u(wd[1]), f2u(wd[2]), f2u(wd[3])};
       }
     }
@@ -662,7 +671,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
         if constexpr (KIND == 1) sw[mi] = *(const uint32_t*)(sb + SIGN_OFF + (row * BM + pl) * 4);
       }
       wm = *(const u32x4*)(sb + WMU_OFF + (row * BN + wv_n * 32 + l31) * 16);
-      if constexpr (KIND == 1) wd = *(const u32x4*)(sb + WDL_OFF + (row * BN + wv_n * 32 + l31) * 16);
+      if constexpr (KIND != 0) wd = *(const u32x4*)(sb + WDL_OFF + (row * BN + wv_n * 32 + l31) * 16);
       if constexpr (PREC == 1) {
 #pragma unroll
         for (int mi = 0; mi < 2; ++mi)
@@ -674,6 +683,21 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
             u32x4 a2;
 #pragma unroll
             for (int d = 0; d < 4; ++d) a2[d] = a[mi][d] ^ ((sw[mi] << d) & 0x80008000u);
+            accd[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wd),
+                                                               __builtin_bit_cast(bf16x8, a2), accd[mi], 0, 0, 0);
+          }
+        }
+        if constexpr (KIND == 2) {  // variance operand bf16(f32(x) * f32(x)): squared in f32, rounded once
+#pragma unroll
+          for (int mi = 0; mi < 2; ++mi) {
+            float f[8];
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+              const float lo = u2f(a[mi][d] << 16), hi = u2f(a[mi][d] & 0xffff0000u);
+              f[2 * d] = lo * lo;
+              f[2 * d + 1] = hi * hi;
+            }
+            const u32x4 a2 = pack_granule<1>(f);
             accd[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wd),
                                                                __builtin_bit_cast(bf16x8, a2), accd[mi], 0, 0, 0);
           }
@@ -690,6 +714,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
             for (int mi = 0; mi < 2; ++mi) {
               const float a2 = u2f(a[mi][e] ^ ((sw[mi] << shf) & 0x80000000u));
               accd[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(u2f(wd[e]), a2, accd[mi], 0, 0, 0);
+            }
+          }
+          if constexpr (KIND == 2) {
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) {
+              const float x1 = u2f(a[mi][e]);
+              accd[mi] = __builtin_amdgcn_mfma_f32_32x32x2f32(u2f(wd[e]), x1 * x1, accd[mi], 0, 0, 0);
             }
           }
         }
@@ -728,11 +759,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
       float bm = 0.f, bdl = 0.f;
       if (col < p.Ng) {
         const int gcol = group * p.Ng + col;
-        const float eb = p.eps_b ? p.eps_b[gcol]
-                                 : btx_normal1((unsigned long long)gcol, rl.sample, p.layer, 1u, p.seed_lo, p.seed_hi);
         const float sb_ = btx_softplus_fast(p.rho_b[gcol]);
-        if constexpr (KIND == 0) { bm = __builtin_fmaf(sb_, eb, p.mu_b[gcol]); }
-        else { bm = p.mu_b[gcol]; bdl = sb_ * eb; }
+        if constexpr (KIND == 2) {  // the bias enters the mean with mu_b and the variance with sigma_b^2: no draw of its own
+          bm = p.mu_b[gcol]; bdl = sb_ * sb_;
+        } else {
+          const float eb = p.eps_b ? p.eps_b[gcol]
+                                   : btx_normal1((unsigned long long)gcol, rl.sample, p.layer, 1u, p.seed_lo, p.seed_hi);
+          if constexpr (KIND == 0) { bm = __builtin_fmaf(sb_, eb, p.mu_b[gcol]); }
+          else { bm = p.mu_b[gcol]; bdl = sb_ * eb; }
+        }
       }
       bias_lds[tid] = bm;
       bias_lds[BN + tid] = bdl;
@@ -772,11 +807,34 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
         const int c0 = ntile * BN + cl;
         if (c0 >= p.Ng) continue;
         float v[4];
+        float zeta[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (KIND == 2) {
+          // zeta = eps(stream 4, linear index of the element in the lane's own output tensor): one Philox call for a run that is
+          // 4-aligned in that tensor (the group btx_fill_eps draws together).  A run off that grid (ragged N, odd Ng under groups)
+          // straddles two groups: both are drawn and the elements picked by index — the values btx_normal1 returns, in two
+          // Philox calls instead of four
+          const unsigned long long i0 = (unsigned long long)(orow + c0);
+          const uint32_t zblk = (uint32_t)(i0 >> 2);
+          const int zoff = (int)(i0 & 3ull);
+          float za[4], zb[4] = {0.f, 0.f, 0.f, 0.f};
+          btx_normal4(zblk, rl.sample, p.layer, 4u, p.seed_lo, p.seed_hi, za);
+          if (zoff != 0) btx_normal4(zblk + 1u, rl.sample, p.layer, 4u, p.seed_lo, p.seed_hi, zb);
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const int j = zoff + rr;
+            zeta[rr] = j == 0 ? za[0] : j == 1 ? za[1] : j == 2 ? za[2] : j == 3 ? za[3] : j == 4 ? zb[0] : j == 5 ? zb[1] : zb[2];
+          }
+        }
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
           const int col = c0 + rr;
           float val = accm[mi][4 * q + rr];
           if (has_bias) val += bias_lds[cl + rr];
+          if constexpr (KIND == 2) {  // sqrt is not linear: the planner never splits K for this kind
+            float var = accd[mi][4 * q + rr];
+            if (has_bias) var += bias_lds[BN + cl + rr];
+            val = __builtin_fmaf(__builtin_sqrtf(var), zeta[rr], val);
+          }
           if constexpr (KIND == 1) {
             float dl = accd[mi][4 * q + rr];
             if (has_bias) dl += bias_lds[BN + cl + rr];
@@ -907,11 +965,13 @@ static int launch_contract_impl(int kind, int act_bf16, bool gen, const Contract
     hipLaunchKernelGGL(kfn, dim3(nwg), dim3(NTHREADS), LDS_BYTES, st, p);                                         \
   } while (0)
   if (!act_bf16) {
-    if (kind == 0) { if (gen) BTX_LAUNCH(float, 0, true); else BTX_LAUNCH(float, 0, false); }
-    else           { if (gen) BTX_LAUNCH(float, 1, true); else BTX_LAUNCH(float, 1, false); }
+    if (kind == 0)      { if (gen) BTX_LAUNCH(float, 0, true); else BTX_LAUNCH(float, 0, false); }
+    else if (kind == 1) { if (gen) BTX_LAUNCH(float, 1, true); else BTX_LAUNCH(float, 1, false); }
+    else                { if (gen) BTX_LAUNCH(float, 2, true); else BTX_LAUNCH(float, 2, false); }
   } else {
-    if (kind == 0) { if (gen) BTX_LAUNCH(__bf16, 0, true); else BTX_LAUNCH(__bf16, 0, false); }
-    else           { if (gen) BTX_LAUNCH(__bf16, 1, true); else BTX_LAUNCH(__bf16, 1, false); }
+    if (kind == 0)      { if (gen) BTX_LAUNCH(__bf16, 0, true); else BTX_LAUNCH(__bf16, 0, false); }
+    else if (kind == 1) { if (gen) BTX_LAUNCH(__bf16, 1, true); else BTX_LAUNCH(__bf16, 1, false); }
+    else                { if (gen) BTX_LAUNCH(__bf16, 2, true); else BTX_LAUNCH(__bf16, 2, false); }
   }
 #undef BTX_LAUNCH
   return (int)hipGetLastError();

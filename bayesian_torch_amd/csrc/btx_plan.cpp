@@ -355,13 +355,34 @@ size_t plan_ws(const Plan& pl, const BtxGeom* g, int lanes) {
 
 int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint32_t flags, bool unaligned, const BtxNoise* noise,
                const BtxEpilogue* ep, FwdSel* s) {
-  if (kind != BTX_KIND_REPARAM && kind != BTX_KIND_FLIPOUT) return BTX_E_UNSUPPORTED;
+  if (kind != BTX_KIND_REPARAM && kind != BTX_KIND_FLIPOUT && kind != BTX_KIND_LRT) return BTX_E_UNSUPPORTED;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   memset(s, 0, sizeof(*s));
   const int lanes = (int)plan_lanes(flags);
   Plan& pl = s->pl;
   int rc = make_plan(g, prec, flags, BM, &pl);
   if (rc) return rc;
+  // Local reparameterization (BTX-LRT v1): the register-staged kernel or the gather kernel, nothing else.  The
+  // store takes the root of the variance sum, and sqrt is not linear: K is never split (a small-M launch is mtiles * ntiles * groups
+  // workgroups per lane, however long K is).  No weight noise exists, so there is nothing to pre-sample, to pass in or to pool.
+  if (kind == BTX_KIND_LRT) {
+    if (prec == BTX_PREC_BF16X3) return BTX_E_UNSUPPORTED;
+    if (flags & (BTX_FLAG_ROWFUSE | BTX_FLAG_OUT_F32 | BTX_FLAG_OUT_BF16)) return BTX_E_UNSUPPORTED;
+    if (ep && ep->pool) return BTX_E_UNSUPPORTED;
+    if (noise && (noise->sampled_w || noise->eps_w || noise->eps_b || noise->sign_in || noise->sign_out)) return BTX_E_UNSUPPORTED;
+    const int G2 = (prec == BTX_PREC_BF16) ? 8 : 4;
+    const bool gen2 = (pl.Cg % G2 != 0) || unaligned || (flags & BTX_FLAG_GATHER) != 0;
+    pl.ksplits = 1; pl.kper = pl.K;
+    const long long nwg = (long long)pl.mtiles * pl.ntiles * g->groups;
+    if (nwg * lanes > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+    pl.nwg = (int)nwg;
+    s->family = gen2 ? BTX_FAMILY_GATHER : BTX_FAMILY_REGSTAGE;
+    s->out_bf16 = (act_dtype == BTX_ACT_BF16) ? 1 : 0;
+    s->g8_pairs = 1;
+    s->pt.kg = 1;
+    s->need = 0;
+    return 0;
+  }
 
   // fast (granule) paths need whole 16-byte granules everywhere; otherwise the element-wise gather path
   const int G = (prec == BTX_PREC_BF16) ? 8 : 4;
@@ -562,7 +583,7 @@ int btx_contract_pool_shape(const BtxGeom* g, int act_dtype, int prec, uint32_t 
 size_t btx_contract_workspace_bytes(const BtxGeom* g, int kind, int act_dtype, int prec, uint32_t flags) {
   Plan a, b;
   if (!g || make_plan(g, prec, flags, BM, &a) || make_plan(g, prec, flags, DBM, &b)) return 0;
-  (void)kind;
+  if (kind == BTX_KIND_LRT) return 0;  // no weight tiles, K never split: no partial sums either
   const int lanes = (int)plan_lanes(flags);
   // which kernel runs also depends on pointer alignment: the largest need of every plan the request can take
   auto with_tiles = [&](const Plan& pl) {

@@ -53,8 +53,10 @@ class BaseVariationalLayer_(nn.Module):
 
 
 class _VariationalNd(BaseVariationalLayer_):
-    """family: "reparam" | "flipout".  nd: 0 Linear, 1/2/3 Conv.  Draw orders:
-    reparam: eps_w, eps_b ; linear flipout: eps_w, eps_b, s_in, s_out ; conv flipout: s_in, s_out, eps_w, eps_b."""
+    """family: "reparam" | "flipout" | "lrt".  nd: 0 Linear, 1/2/3 Conv.  Draw orders:
+    reparam: eps_w, eps_b ; linear flipout: eps_w, eps_b, s_in, s_out ; conv flipout: s_in, s_out, eps_w, eps_b.
+    "lrt" (local reparameterization, BTX-LRT v1; not in the reference) draws no weight noise: one normal per
+    output element, `zeta`, the only draw of a forward."""
 
     _family = "reparam"
     _nd = 0
@@ -290,13 +292,72 @@ class _VariationalNd(BaseVariationalLayer_):
             return out, kl
         return out
 
+    def _kind(self):
+        return {"reparam": _lib.KIND_REPARAM, "flipout": _lib.KIND_FLIPOUT, "lrt": _lib.KIND_LRT}[self._family]
+
+    @staticmethod
+    def _lrt_root(v):
+        """sqrt(v) of the LRT composite with a finite gradient at v == 0: the value there is 0 (as sqrtf gives in the kernel) and the
+        gradient is DEFINED as 0 — an output element whose variance sum is exactly zero (all-zero activations, no bias) carries no
+        noise, and d sqrt / dv = inf there would turn 0 * inf into NaN in every parameter gradient it touches."""
+        pos = v > 0
+        return torch.where(pos, torch.sqrt(torch.where(pos, v, torch.ones_like(v))), torch.zeros_like(v))
+
+    def _lrt_composite(self, x, zeta_of, return_kl=False):
+        """BTX-LRT v1 as differentiable ATen ops (CPU tensors, backend "torch", GPU training): m = x (*) mu + mu_b,
+        v = x^2 (*) sigma^2 + sigma_b^2, out = m + sqrt(v) * zeta; zeta_of(m) returns zeta in m's shape (no gradient)."""
+        mu, rho = self._w()
+        mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
+        sigma_w = BF.softplus_naive(rho)
+        kl = self.kl_div(mu, sigma_w, self.prior_weight_mu, self.prior_weight_sigma) if return_kl else None
+        mb = vb = None
+        if self.mu_bias is not None:
+            sigma_b = BF.softplus_naive(self.rho_bias)
+            mb, vb = self.mu_bias, sigma_b * sigma_b
+            if return_kl:
+                kl = kl + self.kl_div(self.mu_bias, sigma_b, self.prior_bias_mu, self.prior_bias_sigma)
+        xf = x if x.dtype == mu.dtype else x.to(mu.dtype)
+        m = BF.contract_aten(xf, mu, mb, self._op)
+        v = BF.contract_aten(xf * xf, sigma_w * sigma_w, vb, self._op)
+        out = m + self._lrt_root(v) * zeta_of(m)
+        return (out if out.dtype == x.dtype else out.to(x.dtype)), kl
+
+    def _lrt_zeta_hip(self, shape, device, sample_idx, sample_dev=None):
+        """the zeta of MC sample `sample_idx` (or of the device word `sample_dev`) for an output of logical shape `shape`: stream
+        BTX_STREAM_OUT_NOISE at the element's index in the channels-last tensor the kernel writes — what the kind-2 launch draws"""
+        shape = tuple(shape)
+        n = 1
+        for d in shape:
+            n *= int(d)
+        flat = BF.fill_eps_hip(n, device, _rng.seed(), sample_idx, self._btx_layer_id, _lib.STREAM_OUT_NOISE, sample_dev=sample_dev)
+        nd = self._op.nd
+        if nd == 0:
+            return flat.reshape(shape)
+        t = flat.reshape((shape[0],) + shape[2:] + (shape[1],))
+        return t.permute((0, nd + 1) + tuple(range(1, nd + 1)))
+
+    def _forward_lrt_train(self, x):
+        """GPU forward that needs gradients: the composite on the device, zeta fetched with btx_fill_eps — training draws exactly
+        the noise inference draws at the same (seed, layer id, sample index).  (A fused HIP backward is the follow-up: DESIGN.md §8.)"""
+        if self.__dict__.get("_btx_lanes", 1) > 1:
+            raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
+        s_idx = self._btx_sample
+        self.__dict__["_btx_sample"] = s_idx + 1
+        unbatched = self._op.nd > 0 and x.dim() == self._op.nd + 1
+        sdev = getattr(self, "_btx_sample_dev", None)
+        out, _ = self._lrt_composite(x.unsqueeze(0) if unbatched else x,
+                                     lambda m: self._lrt_zeta_hip(m.shape, m.device, s_idx, sdev))
+        return out.squeeze(0) if unbatched else out
+
     def forward(self, input, return_kl=True):
         if self.dnn_to_bnn_flag:
             return_kl = False
         if self.quant_prepare:
             return self._forward_calibrate(input, return_kl)
         if self._use_hip(input):
-            if self._needs_grad(input):
+            if self._needs_grad(input) and self._family == "lrt":
+                out = self._forward_lrt_train(input)
+            elif self._needs_grad(input):
                 if self.__dict__.get("_btx_lanes", 1) > 1:
                     raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
                 from .. import autograd as _ag
@@ -319,6 +380,8 @@ class _VariationalNd(BaseVariationalLayer_):
         shape = getattr(self, "_btx_last_xshape", None)
         if shape is None or self.__dict__.get("_btx_fused_seq"):
             return None  # (the inner layers of a fused LSTM sample inside btx_lstm_fwd: a tile here would never be read)
+        if self._family == "lrt":
+            return None  # no weight noise: nothing to sample
         mu, rho = self._w()
         op0 = self._op
         mu_p, rho_p = BF.gemm_major_view(mu, op0), BF.gemm_major_view(rho, op0)
@@ -373,6 +436,9 @@ class _VariationalNd(BaseVariationalLayer_):
         return None
 
     def _forward_hip(self, x, noise=None, sample_idx=None, epilogue=None, gather=False):
+        if self._family == "lrt" and (self.precision or BF.get_precision()) == "bf16x3":
+            raise _lib.BtxError("%s: precision 'bf16x3' is not available for local reparameterization (BTX-LRT v1 defines f32 and "
+                                "bf16); set layer.precision or functional.set_precision" % type(self).__name__)
         if self._op.nd > 0 and x.dim() == self._op.nd + 1:  # unbatched [C,*sp], as ATen's convolutions accept
             if epilogue is not None and epilogue.get("residual") is not None:
                 epilogue = dict(epilogue, residual=epilogue["residual"].unsqueeze(0))
@@ -385,7 +451,9 @@ class _VariationalNd(BaseVariationalLayer_):
         if sample_idx is None:
             sample_idx = self._btx_sample
             self.__dict__["_btx_sample"] = sample_idx + lanes
-        kind = _lib.KIND_FLIPOUT if self._family == "flipout" else _lib.KIND_REPARAM
+        kind = self._kind()
+        if kind == _lib.KIND_LRT and noise is not None:
+            raise _lib.BtxError("local reparameterization has no explicit-noise mode: its zeta is materialize_noise()['zeta']")
         mb = self.mu_bias.detach() if self.mu_bias is not None else None
         rb = self.rho_bias.detach() if self.rho_bias is not None else None
         op = self._op
@@ -420,7 +488,7 @@ class _VariationalNd(BaseVariationalLayer_):
             rho_p = torch.nn.functional.pad(rho_p, (0, extra))
             op = self._op_pad
         pre = None
-        if noise is None:
+        if noise is None and kind != _lib.KIND_LRT:  # (LRT samples per launch, in the store: no tiles, no caches)
             tag = ("cpad", self._btx_cpad) if self._btx_cpad is not None else ("plain",)
             pre = self._take_presampled(sample_idx, self.precision or BF.get_precision(), tag)
         return BF.contract_hip(kind, x, mu_p, rho_p, mb, rb, op, _rng.seed(), sample_idx,
@@ -493,8 +561,8 @@ class _VariationalNd(BaseVariationalLayer_):
         return BF.apply_act_aten(out, relu)
 
     def _rowfuse_plan(self, x):
-        if self._op.nd != 2 or self._op.in_channels > 4 or not x.is_cuda:
-            return None
+        if self._op.nd != 2 or self._op.in_channels > 4 or not x.is_cuda or self._family == "lrt":
+            return None  # (LRT: register-staged / gather kernels only — a small-C stem runs channel-padded)
         cache = self.__dict__.setdefault("_btx_plans", {})  # geometry only: one plan (and one OpDesc) per input shape
         key = tuple(x.shape)
         if key not in cache:
@@ -511,6 +579,10 @@ class _VariationalNd(BaseVariationalLayer_):
         mu, _ = self._w()
         op, seed, lid = self._op, _rng.seed(), self._btx_layer_id
         cin, cpad = op.in_channels, self._btx_cpad
+        if self._family == "lrt":  # the one draw of the family: dict(zeta) in the logical layout of the output
+            if out_shape is None:
+                raise _lib.BtxError("materialize_noise of a LocalReparameterization layer needs out_shape")
+            return {"zeta": self._lrt_zeta_hip(out_shape, mu.device, sample_idx, sample_dev)}
         # sample_dev (captured training steps): the index lives in a device word; eps follows it, the sign TENSORS (padded
         # layouts only) are keyed on the host and cannot
         if sample_dev is not None and signs and self._family == "flipout" and x_shape is not None:
@@ -584,6 +656,9 @@ class _VariationalNd(BaseVariationalLayer_):
         eps_w_buf = getattr(self, "eps_" + self._wn)
         has_b = self.mu_bias is not None
         kl = None
+        if self._family == "lrt":  # one draw from torch's generator (keyed per MC sample by mc.mc_forward, as for the other kinds)
+            out, kl = self._lrt_composite(x, lambda m: torch.empty(m.shape, dtype=m.dtype, device=m.device).normal_(), return_kl)
+            return (out, kl) if return_kl else out
         if self._family == "reparam":
             sigma_w = BF.softplus_naive(rho)
             weight = mu + (sigma_w * eps_w_buf.data.normal_())

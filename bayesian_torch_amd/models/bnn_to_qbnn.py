@@ -107,6 +107,9 @@ def bnn_to_qbnn(m, fuse_conv_bn=False, flipout=False):
     for name, child in list(mods.items()):
         if child is None or getattr(child, "_btx_q8", False):
             continue
+        if getattr(child, "_family", None) == "lrt" and hasattr(child, "_btx_layer_id"):
+            from .._lib import BtxError
+            raise BtxError("bnn_to_qbnn: %r is a %s; local reparameterization layers have no INT8 twin" % (name, type(child).__name__))
         if _convertible(child, flipout):
             setattr(m, name, qbnn_linear_layer(child) if child._nd == 0 else qbnn_conv_layer(child))
         elif hasattr(child, "ih") and hasattr(child, "hh") and hasattr(child, "fused_sequence"):

@@ -22,8 +22,19 @@ def _moped(bnn_layer, d, params, wname):
         bnn_layer.rho_bias.data.copy_(get_rho(d.bias.data, delta))
 
 
+def _layer_class(params, d):
+    """`<ClassName><type>` in bayesian_torch_amd.layers; a type that does not cover the module's class (LocalReparameterization has
+    no ConvTranspose* / LSTM form) fails with the module's class in the message"""
+    name = d.__class__.__name__ + params["type"]
+    fn = getattr(bayesian_layers, name, None)
+    if fn is None:
+        raise AttributeError("dnn_to_bnn: no Bayesian layer class %r: type=%r does not cover %s modules"
+                             % (name, params["type"], d.__class__.__name__))
+    return fn
+
+
 def bnn_linear_layer(params, d):
-    layer_fn = getattr(bayesian_layers, d.__class__.__name__ + params["type"])
+    layer_fn = _layer_class(params, d)
     bnn_layer = layer_fn(in_features=d.in_features, out_features=d.out_features,
                          prior_mean=params["prior_mu"], prior_variance=params["prior_sigma"],
                          posterior_mu_init=params["posterior_mu_init"],
@@ -35,7 +46,7 @@ def bnn_linear_layer(params, d):
 
 
 def bnn_conv_layer(params, d):
-    layer_fn = getattr(bayesian_layers, d.__class__.__name__ + params["type"])
+    layer_fn = _layer_class(params, d)
     bnn_layer = layer_fn(in_channels=d.in_channels, out_channels=d.out_channels, kernel_size=d.kernel_size,
                          stride=d.stride, padding=d.padding, dilation=d.dilation, groups=d.groups,
                          prior_mean=params["prior_mu"], prior_variance=params["prior_sigma"],
@@ -50,7 +61,7 @@ def bnn_conv_layer(params, d):
 def bnn_lstm_layer(params, d):
     """reference models/dnn_to_bnn.py:106-122: nn.LSTM(input_size, hidden_size) -> LSTM<type>(in, out); MOPED is not
     defined for LSTM layers (the reference prints the same warning and converts with the default init)."""
-    layer_fn = getattr(bayesian_layers, d.__class__.__name__ + params["type"])
+    layer_fn = _layer_class(params, d)
     bnn_layer = layer_fn(in_features=d.input_size, out_features=d.hidden_size, prior_mean=params["prior_mu"],
                          prior_variance=params["prior_sigma"], posterior_mu_init=params["posterior_mu_init"],
                          posterior_rho_init=params["posterior_rho_init"], bias=d.bias is not None)

@@ -51,6 +51,13 @@ extern "C" {
 /* kind */
 #define BTX_KIND_REPARAM 0
 #define BTX_KIND_FLIPOUT 1
+#define BTX_KIND_LRT     2 /* local reparameterization (BTX-LRT v1): y = m + sqrt(v) * zeta with m = x (*) mu_w + mu_b,
+                              v = x^2 (*) sigma_w^2 + sigma_b^2 and one standard normal zeta per OUTPUT element, stream
+                              BTX_STREAM_OUT_NOISE at the element's linear index in the (lane's own) channels-last output tensor:
+                              btx_fill_eps(out_numel, rng, BTX_STREAM_OUT_NOISE) returns the zeta of a launch bit for bit.  Forward
+                              entry points only (btx_contract_fwd, _ex, _lanes), on BTX_FAMILY_REGSTAGE / _GATHER with K never split.
+                              BTX_E_UNSUPPORTED: BTX_PREC_BF16X3, BTX_FLAG_ROWFUSE, BTX_FLAG_OUT_*, BtxEpilogue.pool and every
+                              BtxNoise field (no weight noise exists; there is no explicit-noise mode). */
 /* activation dtype */
 #define BTX_ACT_F32  0
 #define BTX_ACT_BF16 1
@@ -104,6 +111,7 @@ extern "C" {
 #define BTX_STREAM_EPS_B    1u
 #define BTX_STREAM_SIGN_IN  2u
 #define BTX_STREAM_SIGN_OUT 3u
+#define BTX_STREAM_OUT_NOISE 4u /* BTX_KIND_LRT: the per-output-element normal zeta */
 
 /* Geometry of one variational contraction.  Linear is the 1x1x1 case: NB=batch, D=H=W=1, C=in_features,
  * KD=KH=KW=1, N=out_features.  Conv1d uses H only... by convention lower-rank convs put their axes last
