@@ -77,6 +77,11 @@ class LstmGrads(ctypes.Structure):
     _fields_ = [("dmu_w", ctypes.c_void_p), ("drho_w", ctypes.c_void_p), ("dmu_b", ctypes.c_void_p), ("drho_b", ctypes.c_void_p)]
 
 
+class LrtGrads(ctypes.Structure):  # BtxLrtGrads: every member nullable
+    _fields_ = [("dmu_w", ctypes.c_void_p), ("drho_w", ctypes.c_void_p), ("dmu_b", ctypes.c_void_p), ("drho_b", ctypes.c_void_p),
+                ("dx", ctypes.c_void_p)]
+
+
 class KlItem(ctypes.Structure):
     _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("prior_mu_t", ctypes.c_void_p),
                 ("prior_sigma_t", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("drho", ctypes.c_void_p),
@@ -140,7 +145,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_bucket_pack", "btx_bucket_unpack",
            "btx_mc_eval_state_doubles", "btx_mc_eval_workspace_bytes", "btx_mc_eval",
            "btx_mc_moments_lanes", "btx_mc_gnll_workspace_bytes", "btx_mc_gnll_fwd", "btx_mc_gnll_bwd",
-           "btx_reg_eval_workspace_bytes", "btx_reg_eval_update")
+           "btx_reg_eval_workspace_bytes", "btx_reg_eval_update",
+           "btx_lrt_fwd_train", "btx_lrt_bwd_workspace_bytes", "btx_lrt_bwd")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -334,6 +340,13 @@ def lib():
     L.btx_reg_eval_workspace_bytes.argtypes = [i32, i32]
     L.btx_reg_eval_update.restype = i32
     L.btx_reg_eval_update.argtypes = [vp, vp, i32, i32, f64, f64, vp, i32, vp, sz, vp, ctypes.c_int64, vp, sz, vp]
+    L.btx_lrt_fwd_train.restype = i32
+    L.btx_lrt_fwd_train.argtypes = [ctypes.POINTER(Geom), vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Rng), i32, i32, u32, vp]
+    L.btx_lrt_bwd_workspace_bytes.restype = i32
+    L.btx_lrt_bwd_workspace_bytes.argtypes = [ctypes.POINTER(Geom), i32, i32, ctypes.POINTER(sz)]
+    L.btx_lrt_bwd.restype = i32
+    L.btx_lrt_bwd.argtypes = [ctypes.POINTER(Geom), vp, vp, vp, vp, vp, vp, ctypes.POINTER(LrtGrads), ctypes.POINTER(Rng), i32, i32,
+                              vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -203,6 +203,71 @@ class ContractFn(torch.autograd.Function):
         return None, None, dx, dmu, drho, dmu_b, drho_b
 
 
+class LrtFn(torch.autograd.Function):
+    """y = layer(x) of a LocalReparameterization layer on the HIP backend with gradients w.r.t. x, mu, rho, mu_b, rho_b: the forward is
+    btx_lrt_fwd_train (the kind-2 launch of inference, bit for bit, plus the f32 root: 4 bytes of saved state per output element), the
+    backward ONE btx_lrt_bwd call (DESIGN.md §21 "Backward").  Channel-padded layers (the C = 3 stem) run both on the padded geometry
+    the inference forward runs on; zeta indexes the output only, so padding does not move it."""
+
+    @staticmethod
+    def forward(ctx, layer, sample_idx, x, mu, rho, mu_b, rho_b):
+        op = layer._op
+        with torch.no_grad():
+            mu_p, rho_p = BF.gemm_major_view(mu, op), BF.gemm_major_view(rho, op)
+            xin = x
+            if layer._btx_cpad is not None:
+                extra = layer._btx_cpad - op.in_channels
+                xin = BF.pad_channels(x, op, extra)
+                mu_p = torch.nn.functional.pad(mu_p, (0, extra))   # zero weights meet zero activations
+                rho_p = torch.nn.functional.pad(rho_p, (0, extra))
+                op = layer._op_pad
+            layer.__dict__["_btx_last_xshape"] = tuple(x.shape)
+            sdev = getattr(layer, "_btx_sample_dev", None)
+            out, root = BF.lrt_fwd_train_hip(xin, mu_p, rho_p, mu_b.detach() if mu_b is not None else None,
+                                             rho_b.detach() if rho_b is not None else None, op, _rng.seed(), sample_idx,
+                                             layer._btx_layer_id, prec=layer.precision, sample_dev=sdev)
+        ctx.layer, ctx.sample_idx, ctx.sample_dev = layer, sample_idx, sdev  # the device word THIS forward read (num_mc > 1)
+        ctx.save_for_backward(x, root, mu, rho, rho_b)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        layer, s = ctx.layer, ctx.sample_idx
+        x, root, mu, rho, rho_b = ctx.saved_tensors
+        op0 = layer._op
+        need = ctx.needs_input_grad
+        with torch.no_grad():
+            mu_p, rho_p = BF.gemm_major_view(mu, op0), BF.gemm_major_view(rho, op0)
+            op, xin, extra = op0, x, 0
+            if layer._btx_cpad is not None:
+                extra = layer._btx_cpad - op0.in_channels
+                xin = BF.pad_channels(x, op0, extra)
+                mu_p = torch.nn.functional.pad(mu_p, (0, extra))
+                rho_p = torch.nn.functional.pad(rho_p, (0, extra))
+                op = layer._op_pad
+            want_w = need[3] or need[4]
+            want_b = rho_b is not None and (need[5] or need[6])
+            dx, dmu_f, drho_f, dmu_b, drho_b = BF.lrt_bwd_hip(xin, dy, root, mu_p, rho_p,
+                                                              rho_b.detach() if rho_b is not None else None, op, _rng.seed(), s,
+                                                              layer._btx_layer_id, prec=layer.precision, sample_dev=ctx.sample_dev,
+                                                              want_x=need[2], want_w=want_w, want_b=want_b)
+            dmu = drho = None
+            if want_w:
+                w_shape = tuple(rho.shape)
+                if extra:  # the padded geometry's [N][tap][cpad] buffers: the real channels, as logical views
+                    wp = (w_shape[0], layer._btx_cpad) + w_shape[2:]
+                    dmu = BF.gemm_major_logical_view(dmu_f, wp, op)[:, :op0.in_channels]
+                    drho = BF.gemm_major_logical_view(drho_f, wp, op)[:, :op0.in_channels]
+                else:
+                    dmu = BF.gemm_major_logical_view(dmu_f, w_shape, op)
+                    drho = BF.gemm_major_logical_view(drho_f, w_shape, op)
+            if dx is not None and extra:
+                dx = dx[..., :op0.in_channels] if op0.nd == 0 else dx[:, :op0.in_channels]
+        return (None, None, dx, dmu if need[3] else None, drho if need[4] else None, dmu_b if need[5] else None,
+                drho_b if need[6] else None)
+
+
 class KlFn(torch.autograd.Function):
     """sum of the per-tensor mean KLs of `n` (mu, rho) pairs on the HIP backend, with gradients"""
 

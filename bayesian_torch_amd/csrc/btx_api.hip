@@ -15,17 +15,19 @@ using namespace btx;
 static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w,
                              const float* mu_b, const float* rho_b, void* out, const BtxRng* rng, const BtxNoise* noise,
                              int act_dtype, int prec, uint32_t flags, void* ws, size_t ws_bytes, void* stream,
-                             const BtxEpilogue* ep, const BtxLanes* ln) {
+                             const BtxEpilogue* ep, const BtxLanes* ln, int var = 0, float* root = nullptr) {
   if (!g || !x || !mu_w || !rho_w || !out || !rng) return BTX_E_NULL;
+  if (var == 1 && !root) return BTX_E_NULL;
   const int lanes = ln ? ln->n : 1;
   if ((mu_b == nullptr) != (rho_b == nullptr)) return BTX_E_NULL;
   // every pointer some fast family reads or writes in 16-byte granules (the residual: btx_epilogue.h stage 2).  The bias, the
   // scale / shift vectors, eps_b and the explicit sign arrays are read element by element in every family: no requirement.
   const uintptr_t al = (uintptr_t)x | (uintptr_t)mu_w | (uintptr_t)rho_w | (uintptr_t)out |
                        (uintptr_t)(noise && noise->eps_w ? noise->eps_w : nullptr) |
-                       (uintptr_t)(ep && ep->residual ? ep->residual : nullptr);
+                       (uintptr_t)(ep && ep->residual ? ep->residual : nullptr) | (uintptr_t)root;
   FwdSel sel;
-  int rc = select_fwd(kind, g, act_dtype, prec, flags, (al & 15) != 0, noise, ep, &sel);
+  // var 2 (noise-free kind-0 contraction of the LRT backward): planned as kind 2 — register-staged or gather kernel, one K range
+  int rc = select_fwd(var == 2 ? BTX_KIND_LRT : kind, g, act_dtype, prec, flags, (al & 15) != 0, noise, ep, &sel);
   if (rc) return rc;
   const Plan& pl = sel.pl;
   const void* sampled_w = (noise && noise->sampled_w) ? noise->sampled_w : nullptr;
@@ -34,7 +36,7 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
 
   ContractParams p;
   memset(&p, 0, sizeof(p));
-  p.x = x; p.mu = mu_w; p.rho = rho_w; p.mu_b = mu_b; p.rho_b = rho_b; p.out = out;
+  p.x = x; p.mu = mu_w; p.rho = rho_w; p.mu_b = mu_b; p.rho_b = rho_b; p.out = out; p.root = root;
   p.partial = pl.ksplits > 1 ? (float*)ws : nullptr;
   p.lanes = lanes; p.lane_nwg = pl.nwg; p.fd_lane_nwg = make_fastdiv((uint32_t)(pl.nwg > 0 ? pl.nwg : 1));
   if (lanes > 1) {
@@ -165,8 +167,12 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
       // the LDS-DMA family above (pre-pass sampling, packed sign words) or the gather kernel
       // (BTX_PREC_BF16X3 has no register-staged form: such shapes run on the exact-f32 kernel, which is at least as accurate)
       const bool gen2 = sel.family == BTX_FAMILY_GATHER || (noise && (noise->eps_w || noise->sign_in));
-      rc = (prec == BTX_PREC_BF16) ? launch_contract_bf16(kind, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st)
-                                   : launch_contract_f32(kind, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st);
+      if (var)  // the training variants of local reparameterization (contract_kernel VAR)
+        rc = (prec == BTX_PREC_BF16) ? launch_contract_var_bf16(var, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st)
+                                     : launch_contract_var_f32(var, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st);
+      else
+        rc = (prec == BTX_PREC_BF16) ? launch_contract_bf16(kind, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st)
+                                     : launch_contract_f32(kind, act_dtype == BTX_ACT_BF16, gen2, p, pl.nwg * lanes, st);
     }
   }
   if (rc) return rc;
@@ -190,6 +196,14 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
     }
   }
   return rc;
+}
+
+int btx::contract_var(int var, const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w, const float* mu_b,
+                      const float* rho_b, void* out, float* root, const BtxRng* rng, int act_dtype, int prec, uint32_t flags,
+                      void* stream) {
+  if (var != 1 && var != 2) return BTX_E_UNSUPPORTED;
+  return contract_fwd_impl(var == 1 ? BTX_KIND_LRT : BTX_KIND_REPARAM, g, x, mu_w, rho_w, mu_b, rho_b, out, rng, nullptr, act_dtype,
+                           prec, flags & ~BTX_FLAG_LANES_MASK, nullptr, 0, stream, nullptr, nullptr, var, root);
 }
 
 extern "C" {

@@ -160,6 +160,7 @@ struct ContractParams {
   long long lane_x, lane_out, lane_res, lane_wt, lane_partial;
   int lane_wt_delta;  // 1 (Flipout): the lanes share the mu tiles at wt, lane l's delta tiles sit at wt_delta_off + l*lane_wt
   int reverse;        // BTX_FLAG_REVERSE: the grid's tiles in descending order
+  float* root;        // VAR == 1 (btx_lrt_fwd_train): r = sqrtf(v + sigma_b^2) of every output element, f32, in the layout of `out`
 };
 
 // the MC sample word of a launch whose index lives in device memory, as a SCALAR load: the word does not change while the
@@ -393,8 +394,14 @@ __device__ __forceinline__ uint32_t sign_word_explicit(const int8_t* __restrict_
 __device__ __forceinline__ int ws_bit(int e) { return ((e & 1) ? 31 : 15) - (e >> 1); }
 
 // =========================================================================================================
-template <int PREC, typename ACT, int KIND, bool GEN>
+// VAR: compile-time variants of the training path of local reparameterization (btx_lrt.hip, DESIGN.md §21 "Backward"); the inference
+// instantiations are VAR == 0 and keep their code.
+//   1  (KIND == 2) the training forward: the store also writes the root r to p.root
+//   2  (KIND == 0) a noise-free contraction: the weight operand is p.mu as it stands — no rho load, no softplus, no Philox, no
+//      Box-Muller, no bias (the two contractions of the data gradient, on mu^T and (sigma^2)^T)
+template <int PREC, typename ACT, int KIND, bool GEN, int VAR = 0>
 __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractParams pk) {
+  static_assert(VAR == 0 || (VAR == 1 && KIND == 2) || (VAR == 2 && KIND == 0), "VAR 1 goes with kind 2, VAR 2 with kind 0");
   int logical = xcd_logical();
   const ContractParams p = lane_view(pk, logical);
   const RngLive rl = rng_live<KIND>(p);
@@ -518,9 +525,13 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
         w_ok = (col < p.Ng) && (w_k < k_end);
         const long long li = w_ok ? w_idx : 0ll;  // clamped, branch-free
         const f32x4 a = *(const f32x4*)(p.mu + li);
-        const f32x4 b = *(const f32x4*)(p.rho + li);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { wmu_r[e] = a[e]; wrho_r[e] = b[e]; }
+        for (int e = 0; e < 4; ++e) wmu_r[e] = a[e];
+        if constexpr (VAR != 2) {
+          const f32x4 b = *(const f32x4*)(p.rho + li);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) wrho_r[e] = b[e];
+        }
       } else {
         w_ok = (col < p.Ng);
 #pragma unroll
@@ -528,7 +539,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
           const bool ok = w_ok && (w_k + e < k_end);
           const long long li = ok ? w_idx + e : 0ll;
           wmu_r[e] = p.mu[li];
-          wrho_r[e] = p.rho[li];
+          if constexpr (VAR != 2) wrho_r[e] = p.rho[li];
         }
       }
     }
@@ -588,8 +599,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
     unsigned char* sb = smem + buf * STAGE_BYTES;
     if (w_thread) {
       float eps[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (KIND == 2) {
-        // local reparameterization: no weight noise, nothing to draw in the K loop
+      if constexpr (KIND == 2 || VAR == 2) {
+        // local reparameterization, noise-free contraction: no weight noise, nothing to draw in the K loop
       } else if constexpr (!GEN) {
         btx_normal4((uint32_t)(w_idx >> 2), rl.sample, p.layer, 0u, p.seed_lo, p.seed_hi, eps);
       } else {
@@ -605,10 +616,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
       float wm[4], wd[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float sg = btx_softplus_fast(wrho_r[e]);
+        float sg = 0.f;
+        if constexpr (VAR != 2) sg = btx_softplus_fast(wrho_r[e]);
         bool ok = w_ok;
         if constexpr (GEN) ok = ok && (w_k + e < k_end);
-        if constexpr (KIND == 0) {
+        if constexpr (VAR == 2) {
+          wm[e] = ok ? wmu_r[e] : 0.f;
+          wd[e] = 0.f;
+        } else if constexpr (KIND == 0) {
           wm[e] = ok ? __builtin_fmaf(sg, eps[e], wmu_r[e]) : 0.f;
           wd[e] = 0.f;
         } else if constexpr (KIND == 1) {
@@ -751,7 +766,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
   // =================== epilogue ===========================================================================
   // lane owns pixel (lane&31) of each 32-pixel tile; register r = 4q+rr holds channel 32*wv_n + 8q + 4h + rr.
   const bool to_partial = p.ksplits > 1;
-  const bool has_bias = (split == 0) && (p.mu_b != nullptr);  // uniform
+  const bool has_bias = (VAR != 2) && (split == 0) && (p.mu_b != nullptr);  // uniform
   float* bias_lds = (float*)smem;  // [0..63] mean part, [64..127] perturbation part (stage buffers are dead now)
   if (has_bias) {
     if (tid < BN) {
@@ -790,6 +805,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
   // is then not aligned to its own width and goes element by element
   bool io_al = true;
   if constexpr (GEN) io_al = ((((uintptr_t)p.out) | ((uintptr_t)p.ep_res)) & (4 * sizeof(ACT) - 1)) == 0;
+  bool root_al = true;  // VAR == 1: the f32 root leaves in 16-byte runs where its own pointer allows it
+  if constexpr (VAR == 1 && GEN) root_al = (((uintptr_t)p.root) & 15) == 0;
   if (colbase < p.Ng) {
 #pragma unroll
     for (int mi = 0; mi < 2; ++mi) {
@@ -807,6 +824,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
         const int c0 = ntile * BN + cl;
         if (c0 >= p.Ng) continue;
         float v[4];
+        float rootv[4] = {0.f, 0.f, 0.f, 0.f};
         float zeta[4] = {0.f, 0.f, 0.f, 0.f};
         if constexpr (KIND == 2) {
           // zeta = eps(stream 4, linear index of the element in the lane's own output tensor): one Philox call for a run that is
@@ -833,7 +851,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
           if constexpr (KIND == 2) {  // sqrt is not linear: the planner never splits K for this kind
             float var = accd[mi][4 * q + rr];
             if (has_bias) var += bias_lds[BN + cl + rr];
-            val = __builtin_fmaf(__builtin_sqrtf(var), zeta[rr], val);
+            if constexpr (VAR == 1) {
+              rootv[rr] = __builtin_sqrtf(var);
+              val = __builtin_fmaf(rootv[rr], zeta[rr], val);
+            } else {
+              val = __builtin_fmaf(__builtin_sqrtf(var), zeta[rr], val);
+            }
           }
           if constexpr (KIND == 1) {
             float dl = accd[mi][4 * q + rr];
@@ -856,6 +879,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void contract_kernel(const ContractPar
           v[rr] = val;
         }
         const bool vec = (c0 + 3 < p.Ng) && (((orow + c0) & 3) == 0) && io_al;
+        if constexpr (VAR == 1) {
+          float* rdst = p.root + orow + c0;
+          if ((c0 + 3 < p.Ng) && (((orow + c0) & 3) == 0) && root_al) {
+            *(f32x4*)rdst = (f32x4){rootv[0], rootv[1], rootv[2], rootv[3]};
+          } else {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) if (c0 + rr < p.Ng) rdst[rr] = rootv[rr];
+          }
+        }
         if (to_partial) {
           float* dst = p.partial + (long long)split * p.M * p.N + orow + c0;
           if (vec) {
@@ -976,5 +1008,40 @@ static int launch_contract_impl(int kind, int act_bf16, bool gen, const Contract
 #undef BTX_LAUNCH
   return (int)hipGetLastError();
 }
+
+// the training variants of local reparameterization (contract_kernel VAR): 1 = kind-2 forward with the root store, 2 = noise-free
+// kind-0 contraction
+int launch_contract_var_f32(int var, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st);
+int launch_contract_var_bf16(int var, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st);
+template <int PREC>
+static int launch_contract_var_impl(int var, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {
+#define BTX_LAUNCH_V(ACT, KIND, GENF, VAR)                                                                        \
+  do {                                                                                                            \
+    auto kfn = contract_kernel<PREC, ACT, KIND, GENF, VAR>;                                                       \
+    static bool attr_done = false;                                                                                \
+    if (!attr_done) {                                                                                             \
+      hipError_t e = hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES); \
+      if (e != hipSuccess) return (int)e;                                                                         \
+      attr_done = true;                                                                                           \
+    }                                                                                                             \
+    hipLaunchKernelGGL(kfn, dim3(nwg), dim3(NTHREADS), LDS_BYTES, st, p);                                         \
+  } while (0)
+  if (!act_bf16) {
+    if (var == 1) { if (gen) BTX_LAUNCH_V(float, 2, true, 1); else BTX_LAUNCH_V(float, 2, false, 1); }
+    else          { if (gen) BTX_LAUNCH_V(float, 0, true, 2); else BTX_LAUNCH_V(float, 0, false, 2); }
+  } else {
+    if (var == 1) { if (gen) BTX_LAUNCH_V(__bf16, 2, true, 1); else BTX_LAUNCH_V(__bf16, 2, false, 1); }
+    else          { if (gen) BTX_LAUNCH_V(__bf16, 0, true, 2); else BTX_LAUNCH_V(__bf16, 0, false, 2); }
+  }
+#undef BTX_LAUNCH_V
+  return (int)hipGetLastError();
+}
+
+// contract_fwd_impl of btx_api.hip for the library's own callers (btx_lrt.hip).  var 1: `kind` is BTX_KIND_LRT and `root` the
+// f32 tensor the store fills; var 2: planned as kind 2 plans (register-staged or gather kernel, K never split, no workspace),
+// launched as the noise-free kind-0 kernel on mu_w alone.
+int contract_var(int var, const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w, const float* mu_b,
+                 const float* rho_b, void* out, float* root, const BtxRng* rng, int act_dtype, int prec, uint32_t flags,
+                 void* stream);
 
 }  // namespace btx

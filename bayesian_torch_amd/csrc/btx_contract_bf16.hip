@@ -6,6 +6,9 @@ namespace btx {
 int launch_contract_bf16(int kind, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {
   return launch_contract_impl<1>(kind, act_bf16, gen, p, nwg, st);
 }
+int launch_contract_var_bf16(int var, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {
+  return launch_contract_var_impl<1>(var, act_bf16, gen, p, nwg, st);
+}
 int launch_contract_dma_bf16(int kind, const ContractParams& p, int nwg, hipStream_t st) {
   return launch_contract_dma_impl<1>(kind, p, nwg, st);
 }

@@ -6,6 +6,9 @@ namespace btx {
 int launch_contract_f32(int kind, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {
   return launch_contract_impl<0>(kind, act_bf16, gen, p, nwg, st);
 }
+int launch_contract_var_f32(int var, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {
+  return launch_contract_var_impl<0>(var, act_bf16, gen, p, nwg, st);
+}
 int launch_contract_dma_f32(int kind, const ContractParams& p, int nwg, hipStream_t st) {
   return launch_contract_dma_impl<0>(kind, p, nwg, st);
 }

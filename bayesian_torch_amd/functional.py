@@ -985,6 +985,126 @@ def dgrad_weights_hip(mu_p, rho_p, n, taps, c, flip, seed, sample_idx, layer_id,
     return outs
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# fused training of the local reparameterization layers (csrc/btx_lrt.hip; DESIGN.md §21 "Backward")
+# --------------------------------------------------------------------------------------------------------------------
+def _lrt_geom(op, nb, spatial):
+    g = _lib.Geom()
+    g.NB, (g.D, g.H, g.W), g.C, g.N = nb, spatial, op.in_channels, op.out_channels
+    g.KD, g.KH, g.KW = op.kernel
+    g.sd, g.sh, g.sw = op.stride
+    g.pd, g.ph, g.pw = op.padding
+    g.dd, g.dh, g.dw = op.dilation
+    g.groups = op.groups
+    return g
+
+
+_LRT_OK_CACHE = {}
+
+
+def lrt_bwd_workspace_bytes(op, nb, spatial, act, prec_c):
+    """(return code, bytes) of btx_lrt_bwd_workspace_bytes for the plain geometry `op` on `nb` images of extent `spatial`"""
+    need = ctypes.c_size_t(0)
+    rc = _lib.lib().btx_lrt_bwd_workspace_bytes(ctypes.byref(_lrt_geom(op, nb, spatial)), act, prec_c, ctypes.byref(need))
+    return rc, int(need.value)
+
+
+def lrt_train_ok(layer, x):
+    """True when a forward of the LocalReparameterization `layer` on `x` that needs gradients goes through autograd.LrtFn (the fused
+    HIP forward + backward, btx_lrt_fwd_train / btx_lrt_bwd): `layer.fused_training` is on, x is a CUDA f32 / bf16 tensor on the HIP
+    backend, the precision is f32 or bf16, and the geometry is covered — Linear, or Conv2d with groups == 1 whose stride-1 padding
+    does not exceed the dilated kernel extent (channel-padded small-C stems run on their padded geometry).  False: the ATen
+    composite (_forward_lrt_train), as before."""
+    if getattr(layer, "_family", None) != "lrt" or not getattr(layer, "fused_training", False):
+        return False
+    if not (layer._use_hip(x) and layer._needs_grad(x)) or x.dtype not in (torch.float32, torch.bfloat16):
+        return False
+    prec = layer.precision or _PRECISION
+    op = layer._op_pad if layer._btx_cpad is not None else layer._op
+    if prec == "bf16x3" or op.nd not in (0, 2) or op.transposed or x.numel() == 0:
+        return False
+    if op.nd == 0:
+        nb, spatial = x.numel() // x.shape[-1], (1, 1, 1)
+    else:
+        if x.dim() not in (3, 4):
+            return False
+        nb, spatial = (x.shape[0] if x.dim() == 4 else 1), (1, x.shape[-2], x.shape[-1])
+    act = _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32
+    key = (id(op), nb, spatial, act, prec)
+    hit = _LRT_OK_CACHE.get(key)
+    if hit is None or hit[1] is not op:
+        if len(_LRT_OK_CACHE) > 4096:
+            _LRT_OK_CACHE.clear()
+        hit = _LRT_OK_CACHE[key] = (lrt_bwd_workspace_bytes(op, nb, spatial, act, _lib.PREC_CODE[prec])[0] == 0, op)
+    return hit[0]
+
+
+def lrt_fwd_train_hip(x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_id, prec=None, sample_dev=None):
+    """btx_lrt_fwd_train: (out, root) — `out` what contract_hip(KIND_LRT, ...) returns for the same arguments, bit for bit, and
+    root = sqrtf(v + sigma_b^2) as a flat f32 tensor in the channels-last element order of `out`"""
+    L = _lib.lib()
+    act = _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32
+    prec_c = _lib.PREC_CODE[prec or _PRECISION]
+    xp, nb, spatial, restore = _to_channels_last(x, op)
+    out_sp = op.out_spatial(spatial)
+    if min(out_sp) <= 0:
+        raise ValueError("output size is too small")
+    out = _alloc_out(op, nb, out_sp, x.dtype, x.device)
+    root = torch.empty(out.numel(), dtype=torch.float32, device=x.device)
+    flags = _lib.FLAG_CONCURRENT if _CONCURRENT else 0
+    if _ALT_ORDER:
+        _ORDER_TOGGLE[0] ^= 1
+        flags |= _lib.FLAG_REVERSE if _ORDER_TOGGLE[0] else 0
+    r = _lib.Rng(int(seed), int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    _lib.check(L.btx_lrt_fwd_train(ctypes.byref(_lrt_geom(op, nb, spatial)), xp.data_ptr(), mu_p.data_ptr(), rho_p.data_ptr(),
+                                   mu_b.data_ptr() if mu_b is not None else None, rho_b.data_ptr() if rho_b is not None else None,
+                                   out.data_ptr(), root.data_ptr(), ctypes.byref(r), act, prec_c, flags,
+                                   torch.cuda.current_stream(x.device).cuda_stream))
+    res = restore(out, out_sp)
+    return (res.contiguous() if (_OUT_LAYOUT == "contiguous" and op.nd > 0) else res), root
+
+
+def lrt_bwd_hip(x, dy, root, mu_p, rho_p, rho_b, op, seed, sample_idx, layer_id, prec=None, sample_dev=None, want_x=True,
+                want_w=True, want_b=True, out_dx=None):
+    """btx_lrt_bwd: (dx | None, dmu_flat | None, drho_flat | None, dmu_b | None, drho_b | None) of one LRT layer from the gradient `dy`
+    of its output and the forward's `root`.  dmu / drho: flat GEMM-major f32 buffers (gemm_major_logical_view gives the logical views);
+    dx in x's dtype, channels-last.  All in one host call; the scratch is the stream's workspace."""
+    L = _lib.lib()
+    act = _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32
+    prec_c = _lib.PREC_CODE[prec or _PRECISION]
+    xp, nb, spatial, _ = _to_channels_last(x, op)
+    yop = OpDesc(op.nd, op.out_channels, op.out_channels)
+    dy2 = dy.reshape(-1, op.out_channels) if op.nd == 0 else dy
+    dyp, _, _, _ = _to_channels_last(dy2 if dy2.dtype == x.dtype else dy2.to(x.dtype), yop)
+    if dyp.numel() != root.numel():
+        raise _lib.BtxError("lrt_bwd_hip: dy does not match the saved root (%d != %d elements)" % (dyp.numel(), root.numel()))
+    dev = x.device
+    g = _lrt_geom(op, nb, spatial)
+    need = ctypes.c_size_t(0)
+    _lib.check(L.btx_lrt_bwd_workspace_bytes(ctypes.byref(g), act, prec_c, ctypes.byref(need)))
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = _workspace(dev, int(need.value), stream)
+    n, kred = op.out_channels, op.kernel[0] * op.kernel[1] * op.kernel[2] * op.in_channels
+    dmu = torch.empty(n * kred, dtype=torch.float32, device=dev) if want_w else None
+    drho = torch.empty(n * kred, dtype=torch.float32, device=dev) if want_w else None
+    has_b = rho_b is not None and want_b
+    dmu_b = torch.empty(n, dtype=torch.float32, device=dev) if has_b else None
+    drho_b = torch.empty(n, dtype=torch.float32, device=dev) if has_b else None
+    dx = None
+    if want_x:
+        dx = out_dx if out_dx is not None else torch.empty_like(xp)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    grads = _lib.LrtGrads(ptr(dmu), ptr(drho), ptr(dmu_b), ptr(drho_b), ptr(dx))
+    r = _lib.Rng(int(seed), int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    _lib.check(L.btx_lrt_bwd(ctypes.byref(g), xp.data_ptr(), dyp.data_ptr(), root.data_ptr(), mu_p.data_ptr(), rho_p.data_ptr(),
+                             ptr(rho_b), ctypes.byref(grads), ctypes.byref(r), act, prec_c, ws.data_ptr(), ws.numel(), stream))
+    if dx is not None and op.nd == 0:
+        dx = dx.reshape(x.shape)
+    return dx, dmu, drho, dmu_b, drho_b
+
+
 def fill_sign_hip(n, device, seed, sample_idx, layer_id, rng_stream):
     L = _lib.lib()
     out = torch.empty(int(n), dtype=torch.int8, device=device)

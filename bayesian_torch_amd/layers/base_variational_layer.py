@@ -125,6 +125,9 @@ class _VariationalNd(BaseVariationalLayer_):
         self._btx_layer_id = _rng.next_layer_id()
         self._btx_sample = 0
         self.precision = None  # None -> functional.get_precision(); or "f32" / "bf16"
+        # LocalReparameterization layers, opt-in (models.fuse_model(model, lrt_training=True) sets it): GPU forwards that need gradients
+        # run btx_lrt_fwd_train / btx_lrt_bwd (autograd.LrtFn) where the geometry is covered (functional.lrt_train_ok)
+        self.fused_training = False
         self.init_parameters()
         self.quant_prepare = False
 
@@ -337,14 +340,22 @@ class _VariationalNd(BaseVariationalLayer_):
         return t.permute((0, nd + 1) + tuple(range(1, nd + 1)))
 
     def _forward_lrt_train(self, x):
-        """GPU forward that needs gradients: the composite on the device, zeta fetched with btx_fill_eps — training draws exactly
-        the noise inference draws at the same (seed, layer id, sample index).  (A fused HIP backward is the follow-up: DESIGN.md §8.)"""
+        """GPU forward that needs gradients.  With `fused_training` on and a covered geometry (functional.lrt_train_ok: Linear, Conv2d
+        with groups == 1, f32 / bf16): autograd.LrtFn — btx_lrt_fwd_train, which also saves the root (4 bytes per output element),
+        and btx_lrt_bwd for the whole backward (DESIGN.md §21 "Backward").  Otherwise (the default): the composite on the device, zeta
+        fetched with btx_fill_eps, differentiated by autograd.  Either way training draws exactly the noise inference draws at the same
+        (seed, layer id, sample index)."""
         if self.__dict__.get("_btx_lanes", 1) > 1:
             raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
         s_idx = self._btx_sample
         self.__dict__["_btx_sample"] = s_idx + 1
         unbatched = self._op.nd > 0 and x.dim() == self._op.nd + 1
         sdev = getattr(self, "_btx_sample_dev", None)
+        if BF.lrt_train_ok(self, x):
+            from .. import autograd as _ag
+            mu, rho = self._w()
+            out = _ag.LrtFn.apply(self, s_idx, x.unsqueeze(0) if unbatched else x, mu, rho, self.mu_bias, self.rho_bias)
+            return out.squeeze(0) if unbatched else out
         out, _ = self._lrt_composite(x.unsqueeze(0) if unbatched else x,
                                      lambda m: self._lrt_zeta_hip(m.shape, m.device, s_idx, sdev))
         return out.squeeze(0) if unbatched else out

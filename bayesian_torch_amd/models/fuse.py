@@ -686,7 +686,14 @@ def _lstm_training(model, on):
                 m.fused_training = True
 
 
-def fuse_model(model, lstm_training=False):
+def _lrt_training(model, on):
+    if on:
+        for m in model.modules():
+            if getattr(m, "_family", None) == "lrt" and hasattr(m, "_btx_layer_id"):
+                m.fused_training = True
+
+
+def fuse_model(model, lstm_training=False, lrt_training=False):
     """Fold eval-mode BatchNorm, residual adds and ReLU / ReLU6 into the store of the variational layers of ANY model converted
     by dnn_to_bnn (its variational layers return a tensor), in place.  The model's forward is traced with torch.fx (variational
     layers and torch.nn modules as leaves) and every chain
@@ -710,7 +717,10 @@ def fuse_model(model, lstm_training=False):
     its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd call.  Returns the number of fused sites plus
     the number of LSTMs switched; a second call returns 0.  lstm_training=True also sets fused_training on every Bayesian LSTM:
     its training forwards on the GPU then run btx_lstm_fwd_train and their backward btx_lstm_bwd (also inside
-    autograd.GraphedTrainStep); it changes neither the count nor what the default call does."""
+    autograd.GraphedTrainStep); it changes neither the count nor what the default call does.  lrt_training=True does the same for
+    every ...LocalReparameterization layer (and for no other layer): GPU forwards that need gradients run btx_lrt_fwd_train /
+    btx_lrt_bwd where functional.lrt_train_ok holds, the ATen composite elsewhere."""
+    _lrt_training(model, lrt_training)
     if model.__dict__.get("_btx_fuse_model"):
         _lstm_training(model, lstm_training)
         return 0

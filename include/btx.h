@@ -381,6 +381,40 @@ int btx_dgrad_weights(const float* mu_w, const float* rho_w, float* out_mu, floa
 int btx_rho_grad(const float* dw, const float* rho, float* drho, size_t n, const BtxRng* rng, uint32_t rng_stream,
                  void* stream);
 
+/* Training of the local reparameterization layers (BTX-LRT v1, DESIGN.md section 21 "Backward"; additive, the ABI number stays 9).
+ *
+ * btx_lrt_fwd_train: the BTX_KIND_LRT launch of btx_contract_fwd_ex without an epilogue — `out` is bit-identical to what that call
+ * writes for the same arguments — plus root[i] = sqrtf(v_i + sigma_b^2), f32, in the layout of `out` (4 bytes of saved state per output
+ * element).  flags: BTX_FLAG_GATHER, _REVERSE, _CONCURRENT; anything else BTX_E_UNSUPPORTED (as is BTX_PREC_BF16X3).
+ *
+ * btx_lrt_bwd: the whole backward of one layer on `stream`, from g = dy (the gradient of `out`, activation dtype, layout of `out`),
+ * the saved root and the forward's BtxRng (zeta is regenerated: stream BTX_STREAM_OUT_NOISE at the element's index in `out`;
+ * sample_idx_dev is honoured):
+ *   c = root > 0 ? zeta / (2 root) : 0,  gv = act(g * c)            (gradient DEFINED as 0 where the variance sum is 0)
+ *   dmu_w = corr(x, g)        drho_w = corr(act(x * x), gv) * 2 sigma sigmoid(rho_w)       GEMM-major f32, as btx_contract_wgrad_ws
+ *   dmu_b = sum_p g           drho_b = (sum_p gv) * 2 sigma_b sigmoid(rho_b)               f32 [N], fixed summation order
+ *   dx    = act(A + 2 x (.) B),  A = act(op^T(g, mu_w)),  B = act(op^T(gv, sigma^2))       activation dtype, layout of x; the two
+ *           contractions run noise-free in precision `prec` on the geometry of the data gradient
+ * Every member of BtxLrtGrads is nullable and skipped when NULL (drho_b needs rho_b).  Covered: Linear, and 2-D convolutions (D == KD
+ * == 1) with groups == 1 whose stride-1 padding does not exceed the dilated kernel extent; everything else, and BTX_PREC_BF16X3,
+ * returns BTX_E_UNSUPPORTED from both calls before anything is launched, as every argument error does (BTX_E_NULL, _SHAPE, _DTYPE,
+ * _WORKSPACE).  No host read, no allocation, no memset: all scratch comes from `ws` (btx_lrt_bwd_workspace_bytes; any alignment).
+ * Pointers off the 16-byte grid take element-wise paths; BTX_E_ALIGN is never returned. */
+typedef struct BtxLrtGrads {
+  float* dmu_w;
+  float* drho_w;
+  float* dmu_b;
+  float* drho_b;
+  void*  dx;
+} BtxLrtGrads;
+int btx_lrt_fwd_train(const BtxGeom* g, const void* x, const float* mu_w, const float* rho_w, const float* mu_b /* nullable */,
+                      const float* rho_b /* nullable */, void* out, float* root, const BtxRng* rng, int act_dtype, int prec,
+                      uint32_t flags, void* stream);
+int btx_lrt_bwd_workspace_bytes(const BtxGeom* g, int act_dtype, int prec, size_t* bytes);
+int btx_lrt_bwd(const BtxGeom* g, const void* x, const void* dy, const float* root, const float* mu_w, const float* rho_w,
+                const float* rho_b /* nullable */, const BtxLrtGrads* out, const BtxRng* rng, int act_dtype, int prec, void* ws,
+                size_t ws_bytes, void* stream);
+
 /* §8(f): the data format in front of the path.  Small-C stems (BTX_FLAG_ROWFUSE) take channels-last [NB][Hp][Wp][cp]
  * activations with the conv padding materialised and the channels zero-padded to cp (4 or 8), in the MFMA dtype.
  * btx_rowfuse_pack writes that tensor in ONE pass from the caller's logical [N,C,H,W] activations of any layout:
