@@ -4,6 +4,8 @@ Drop-in surface (same names as the reference package `bayesian_torch`):
     bayesian_torch_amd.layers.{Linear,Conv1d,Conv2d,Conv3d,ConvTranspose1d,...}{Reparameterization,Flipout}
     bayesian_torch_amd.models.dnn_to_bnn.{dnn_to_bnn, get_kl_loss}
     bayesian_torch_amd.utils.util.get_rho
+Beyond the reference: bayesian_torch_amd.priors (scale-mixture, Laplace and Student-t weight priors with a sampled KL; layer.set_prior,
+models.set_prior).
 `install_alias()` registers this package under the name `bayesian_torch` so existing imports resolve here.
 
 GPU tensors run through hand-written gfx950 kernels in libbtx.so (C-ABI: include/btx.h); see DESIGN.md.
@@ -14,6 +16,7 @@ from . import _lib, functional, rng  # noqa: F401
 from . import layers, models, utils  # noqa: F401
 from . import optim  # noqa: F401
 from . import parallel  # noqa: F401
+from . import priors  # noqa: F401
 from .functional import set_precision, get_precision, set_output_layout  # noqa: F401
 from .layers.base_variational_layer import set_backend  # noqa: F401
 from .models.dnn_to_bnn import dnn_to_bnn, get_kl_loss  # noqa: F401

@@ -14,6 +14,8 @@ FLAG_TRANSPOSED, FLAG_KL_ACCUM, FLAG_ROWFUSE, FLAG_OUT_F32, FLAG_OUT_BF16, FLAG_
 FLAG_REVERSE = 256
 E_UNSUPPORTED = -3
 STREAM_EPS_W, STREAM_EPS_B, STREAM_SIGN_IN, STREAM_SIGN_OUT, STREAM_OUT_NOISE = 0, 1, 2, 3, 4
+STREAM_KL_W, STREAM_KL_B = 5, 6   # BTX-KLMC v1: the sampled KL's own draws (draw j: stream | j << 8)
+PRIOR_GAUSS_MIX2, PRIOR_LAPLACE, PRIOR_STUDENT_T = 1, 2, 3
 ABI_VERSION = 9
 FLAG_LANES_SHIFT = 16
 FLAG_LANES_MASK = 0xff << FLAG_LANES_SHIFT
@@ -88,6 +90,17 @@ class KlItem(ctypes.Structure):
                 ("prior_mu", ctypes.c_float), ("prior_sigma", ctypes.c_float), ("n", ctypes.c_size_t)]
 
 
+class Prior(ctypes.Structure):  # BtxPrior
+    _fields_ = [("type", ctypes.c_int32), ("loc", ctypes.c_float), ("p0", ctypes.c_float), ("p1", ctypes.c_float),
+                ("p2", ctypes.c_float)]
+
+
+class KlMcItem(ctypes.Structure):  # BtxKlMcItem
+    _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("loc_t", ctypes.c_void_p), ("dmu", ctypes.c_void_p),
+                ("drho", ctypes.c_void_p), ("n", ctypes.c_size_t), ("prior", Prior), ("layer_id", ctypes.c_uint32),
+                ("rng_stream", ctypes.c_uint32), ("sample_idx", ctypes.c_uint32), ("sample_idx_dev", ctypes.c_void_p)]
+
+
 class Q8Chain(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("s_sigma", "s_mu", "s_eps", "inv_s_eps", "s_d", "inv_s_d", "inv_s_w")] + \
                [("bias_div", ctypes.c_double)]
@@ -146,7 +159,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_mc_eval_state_doubles", "btx_mc_eval_workspace_bytes", "btx_mc_eval",
            "btx_mc_moments_lanes", "btx_mc_gnll_workspace_bytes", "btx_mc_gnll_fwd", "btx_mc_gnll_bwd",
            "btx_reg_eval_workspace_bytes", "btx_reg_eval_update",
-           "btx_lrt_fwd_train", "btx_lrt_bwd_workspace_bytes", "btx_lrt_bwd")
+           "btx_lrt_fwd_train", "btx_lrt_bwd_workspace_bytes", "btx_lrt_bwd",
+           "btx_kl_mc_workspace_bytes", "btx_kl_mc_model", "btx_kl_mc_model_bwd")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -347,6 +361,12 @@ def lib():
     L.btx_lrt_bwd.restype = i32
     L.btx_lrt_bwd.argtypes = [ctypes.POINTER(Geom), vp, vp, vp, vp, vp, vp, ctypes.POINTER(LrtGrads), ctypes.POINTER(Rng), i32, i32,
                               vp, sz, vp]
+    L.btx_kl_mc_workspace_bytes.restype = sz
+    L.btx_kl_mc_workspace_bytes.argtypes = [i32]
+    L.btx_kl_mc_model.restype = i32
+    L.btx_kl_mc_model.argtypes = [ctypes.POINTER(KlMcItem), i32, ctypes.c_uint64, i32, vp, u32, vp, sz, vp]
+    L.btx_kl_mc_model_bwd.restype = i32
+    L.btx_kl_mc_model_bwd.argtypes = [ctypes.POINTER(KlMcItem), i32, ctypes.c_uint64, i32, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -377,14 +377,96 @@ def kl_pairs(layer):
     return pairs
 
 
+class KlMcFn(torch.autograd.Function):
+    """sum of the per-tensor sampled mean KLs (BTX-KLMC v1) of `n` (mu, rho) pairs against their non-Gaussian priors on
+    the HIP backend, with gradients: btx_kl_mc_model forward, btx_kl_mc_model_bwd backward (eps regenerated, nothing saved but the
+    parameters).  meta: per pair (prior, loc_t | None, op | None, layer_id, rng_stream, sample_idx, sample_dev | None)."""
+
+    @staticmethod
+    def forward(ctx, meta, seed, draws, *params):
+        ctx.meta, ctx.seed, ctx.draws = meta, seed, draws
+        ctx.save_for_backward(*params)
+        return BF.kl_mc_model_hip(_mc_entries(meta, params), seed, draws)
+
+    @staticmethod
+    def backward(ctx, g):
+        params, meta = ctx.saved_tensors, ctx.meta
+        entries = _mc_entries(meta, params)
+        grads = []
+        for mu_e, _rho_e, *_ in entries:  # gradients in the element order the kernel reads: GEMM-major buffers for the weights
+            grads.append((torch.empty_like(mu_e), torch.empty_like(mu_e)))
+        BF.kl_mc_model_bwd_hip(entries, grads, ctx.seed, ctx.draws, g)
+        res = []
+        for i, (gm, gr) in enumerate(grads):  # handed back as logical-shape views (unpacked copies where the layout has no view)
+            op = meta[i][2]
+            if op is not None:
+                shape = tuple(params[2 * i].shape)
+                gm, gr = BF.gemm_major_logical_view(gm, shape, op), BF.gemm_major_logical_view(gr, shape, op)
+            res += [gm, gr]
+        return (None, None, None) + tuple(res)
+
+
+def _mc_entries(meta, params):
+    """the kernel's items: every tensor in its unpadded GEMM-major element order (the index space of the KL draws), biases as they are"""
+    out = []
+    for i, (prior, loc_t, op, layer_id, rng_stream, sample_idx, sample_dev) in enumerate(meta):
+        mu, rho = params[2 * i].detach(), params[2 * i + 1].detach()
+        if op is not None:
+            mu, rho = BF.gemm_major_view(mu, op), BF.gemm_major_view(rho, op)
+            loc_t = BF.gemm_major_view(loc_t, op) if loc_t is not None else None
+        else:
+            mu, rho = mu.contiguous(), rho.contiguous()
+            loc_t = loc_t.detach().contiguous() if loc_t is not None else None
+        out.append((mu, rho, loc_t, prior, layer_id, rng_stream, sample_idx, sample_dev))
+    return out
+
+
+def kl_mc_pairs(layer):
+    """[(mu, rho, meta)] of one variational layer with a non-Gaussian prior for KlMcFn / kl_mc_model_hip"""
+    mu, rho = layer._w()
+    prior = layer._btx_prior
+    loc_w, loc_b = layer._kl_locations()
+    s_idx, sdev = layer._kl_sample_index(), getattr(layer, "_btx_sample_dev", None)
+    if sdev is not None and sdev.numel() != 1:
+        raise _lib.BtxError("the sampled KL reads ONE device sample word; MC sample lanes are an inference feature")
+    pairs = [(mu, rho, (prior, loc_w, layer._op, layer._btx_layer_id, _lib.STREAM_KL_W, s_idx, sdev))]
+    if layer.mu_bias is not None:
+        pairs.append((layer.mu_bias, layer.rho_bias, (prior, loc_b, None, layer._btx_layer_id, _lib.STREAM_KL_B, s_idx, sdev)))
+    return pairs
+
+
+def _kl_mc_of_layers(layers):
+    """the sampled KL of the layers with a non-Gaussian prior: one launch per distinct kl_samples (one, unless the model mixes them)"""
+    total = None
+    for draws in sorted({layer._btx_kl_samples for layer in layers}):
+        pairs = [pr for layer in layers if layer._btx_kl_samples == draws for pr in kl_mc_pairs(layer)]
+        params = [t for mu, rho, _ in pairs for t in (mu, rho)]
+        meta = tuple(m for _, _, m in pairs)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+            kl = KlMcFn.apply(meta, _rng.seed(), draws, *params)
+        else:
+            kl = BF.kl_mc_model_hip(_mc_entries(meta, params), _rng.seed(), draws)
+        total = kl if total is None else total + kl
+    return total
+
+
 def kl_of_layers(layers):
-    """get_kl_loss on the HIP backend: one launch for every tensor of every layer; differentiable when needed"""
+    """get_kl_loss on the HIP backend: one launch for every tensor of every layer; differentiable when needed.  Layers with a
+    non-Gaussian prior (layer.set_prior) go through the sampled KL in one launch of their own, and the two scalars are added."""
+    mc = [layer for layer in layers if layer.__dict__.get("_btx_prior") is not None]
+    if mc:
+        kl_mc = _kl_mc_of_layers(mc)
+        layers = [layer for layer in layers if layer.__dict__.get("_btx_prior") is None]
+        if not layers:
+            return kl_mc
     pairs = [pr for layer in layers for pr in kl_pairs(layer)]
     params = [t for mu, rho, _ in pairs for t in (mu, rho)]
     meta = tuple(m for _, _, m in pairs)
     if torch.is_grad_enabled() and any(t.requires_grad for t in params):
-        return KlFn.apply(meta, *params)
-    return BF.kl_model_hip(_entries(meta, params))
+        kl = KlFn.apply(meta, *params)
+    else:
+        kl = BF.kl_model_hip(_entries(meta, params))
+    return kl + kl_mc if mc else kl
 
 
 # --------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ BASELINE.json config 0, "plumbing, no GPU"); a CUDA tensor NEVER does: if the li
 unsupported the call raises.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -688,6 +689,59 @@ def kl_model_bwd_hip(entries, grads, grad_out):
     g = grad_out.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
     _lib.check(L.btx_kl_gauss_model_bwd(_kl_items(entries, grads), len(entries), g.data_ptr(),
                                         torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _kl_mc_items(entries, grads=None):
+    """entries = [(mu, rho, loc_t | None, prior, layer_id, rng_stream, sample_idx, sample_dev | None)]: same-order contiguous f32 tensors,
+    a priors.* prior, and the BTX-RNG coordinates of the tensor's draws"""
+    arr = (_lib.KlMcItem * len(entries))()
+    for i, (mu, rho, loc_t, prior, layer_id, rng_stream, sample_idx, sample_dev) in enumerate(entries):
+        it = arr[i]
+        it.mu, it.rho, it.n = mu.data_ptr(), rho.data_ptr(), mu.numel()
+        it.loc_t = loc_t.data_ptr() if loc_t is not None else None
+        pp = tuple(prior.params()) + (0.0, 0.0, 0.0)
+        it.prior.type, it.prior.loc = int(prior.code), float(prior.mu)
+        it.prior.p0, it.prior.p1, it.prior.p2 = float(pp[0]), float(pp[1]), float(pp[2])
+        it.layer_id, it.rng_stream, it.sample_idx = int(layer_id) & 0xFFFFFFFF, int(rng_stream), int(sample_idx) & 0xFFFFFFFF
+        it.sample_idx_dev = sample_dev.data_ptr() if sample_dev is not None else None
+        if grads is not None:
+            it.dmu, it.drho = grads[i][0].data_ptr(), grads[i][1].data_ptr()
+    return arr
+
+
+def kl_mc_model_hip(entries, seed, draws, out=None, accumulate=False):
+    """sum over tensors of the sampled mean KL against their non-Gaussian priors (BTX-KLMC v1), ONE launch + one final reduce
+    (btx_kl_mc_model) -> 0-d f32.  `out` / accumulate: add to an existing scalar (BTX_FLAG_KL_ACCUM)."""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = _workspace(dev, L.btx_kl_mc_workspace_bytes(len(entries)), stream)
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=dev)
+    _lib.check(L.btx_kl_mc_model(_kl_mc_items(entries), len(entries), int(seed), int(draws), out.data_ptr(),
+                                 _lib.FLAG_KL_ACCUM if accumulate else 0, ws.data_ptr(), ws.numel(), stream))
+    return out
+
+
+def kl_mc_model_bwd_hip(entries, grads, seed, draws, grad_out):
+    """d(kl)/d(mu, rho) of every tensor into `grads` [(dmu, drho)] (same element order, every element written), scaled by the device
+    scalar `grad_out`; eps is regenerated (btx_kl_mc_model_bwd)"""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    g = grad_out.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
+    _lib.check(L.btx_kl_mc_model_bwd(_kl_mc_items(entries, grads), len(entries), int(seed), int(draws), g.data_ptr(),
+                                     torch.cuda.current_stream(dev).cuda_stream))
+
+
+def kl_mc_aten(mu, sigma, eps, prior, loc=None):
+    """BTX-KLMC v1 as differentiable ATen ops on EXPLICIT noise: eps [S, *mu.shape] -> the mean over elements of
+    -log sigma - (1 + log 2 pi) / 2 - (1 / S) sum_j log p(mu + sigma eps_j); loc: a tensor location in place of prior.mu.
+    The CPU route and backend "torch" (eps from torch's generator), and what the tests model."""
+    if eps.dim() != mu.dim() + 1 or tuple(eps.shape[1:]) != tuple(mu.shape):
+        raise ValueError("eps must be [S, *mu.shape] (got %s for mu %s)" % (tuple(eps.shape), tuple(mu.shape)))
+    w = mu.unsqueeze(0) + sigma.unsqueeze(0) * eps
+    cross = prior.log_prob(w, None if loc is None else loc.unsqueeze(0)).mean(0)
+    return (-torch.log(sigma) - 0.5 * (1.0 + math.log(2.0 * math.pi)) - cross).mean()
 
 
 def rowfuse_plan(op, x_shape):

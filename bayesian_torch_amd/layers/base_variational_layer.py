@@ -128,6 +128,10 @@ class _VariationalNd(BaseVariationalLayer_):
         # LocalReparameterization layers, opt-in (models.fuse_model(model, lrt_training=True) sets it): GPU forwards that need gradients
         # run btx_lrt_fwd_train / btx_lrt_bwd (autograd.LrtFn) where the geometry is covered (functional.lrt_train_ok)
         self.fused_training = False
+        # the weight prior: None = the reference's Gaussian N(prior_mean, prior_variance) with its closed-form KL; set_prior() installs a
+        # non-Gaussian one (priors.py), whose KL is sampled with `_btx_kl_samples` draws per call (BTX-KLMC v1)
+        self._btx_prior = None
+        self._btx_kl_samples = 1
         self.init_parameters()
         self.quant_prepare = False
 
@@ -178,6 +182,7 @@ class _VariationalNd(BaseVariationalLayer_):
 
     def refresh_priors(self):
         self.__dict__["_btx_prior_state"] = None
+        self.__dict__["_btx_loc_state"] = None
 
     def __deepcopy__(self, memo):
         """copies draw their OWN noise (the reference's copies advance the global generator independently): a deep copy
@@ -188,7 +193,7 @@ class _VariationalNd(BaseVariationalLayer_):
         for k, v in self.__dict__.items():
             new.__dict__[k] = copy.deepcopy(v, memo)
         new.__dict__["_btx_layer_id"] = _rng.next_layer_id()
-        for k in ("_btx_pre", "_btx_sample_dev", "_btx_prior_state", "_btx_plans", "_btx_lanes", "_btx_lane_batch"):
+        for k in ("_btx_pre", "_btx_sample_dev", "_btx_prior_state", "_btx_loc_state", "_btx_plans", "_btx_lanes", "_btx_lane_batch"):
             new.__dict__.pop(k, None)
         return new
 
@@ -207,8 +212,81 @@ class _VariationalNd(BaseVariationalLayer_):
                                             (self.mu_bias is not None and self.mu_bias.requires_grad) or
                                             (t is not None and t.is_floating_point() and t.requires_grad))
 
+    # ---- non-Gaussian priors (BTX-KLMC v1) ------------------------------------------------------------------
+    def set_prior(self, prior, kl_samples=1):
+        """Install a weight prior from bayesian_torch_amd.priors (ScaleMixturePrior, LaplacePrior, StudentTPrior): kl_loss(),
+        forward(return_kl=True) and get_kl_loss(model) then return the SAMPLED KL of BTX-KLMC v1 — closed-form entropy, the cross term
+        estimated from `kl_samples` weight draws per call with the estimator's own noise streams (not the forward's draw).  The
+        location is the prior's scalar `mu`, or the prior_weight_mu / prior_bias_mu buffers once they no longer hold the constructor's
+        prior_mean (MOPED writes the deterministic weights there).  None or GaussianPrior restores the closed-form Gaussian KL against
+        prior_mean / prior_variance.  Configuration, not state: state_dict() is unchanged.  Returns the layer."""
+        from .. import priors as _priors
+        refused = self.__dict__.get("_btx_no_prior")
+        prior = _priors.check_prior(prior)
+        if refused and prior is not None:
+            raise _lib.BtxError(refused)
+        kl_samples = int(kl_samples)
+        if not 1 <= kl_samples < (1 << 24):
+            raise ValueError("kl_samples must be in [1, 2^24) (got %r)" % (kl_samples,))
+        self.__dict__["_btx_prior"] = prior
+        self.__dict__["_btx_kl_samples"] = kl_samples if prior is not None else 1
+        return self
+
+    def extra_repr(self):
+        prior = self.__dict__.get("_btx_prior")
+        return "" if prior is None else "prior=%r, kl_samples=%d" % (prior, self._btx_kl_samples)
+
+    def _kl_locations(self):
+        """(weight location, bias location) of the non-Gaussian prior: None = the prior's scalar mu; a tensor (the prior_*_mu buffer)
+        once that buffer no longer holds the constructor's prior_mean.  Verified against the buffers when their identity / version
+        changed (as _priors_are_scalar; call refresh_priors() after a `.data` write)."""
+        key = self._prior_key()
+        st = self.__dict__.get("_btx_loc_state")
+        if st is None or st[0] != key:
+            w_scalar = bool((self.prior_weight_mu == self.prior_mean).all())
+            b_scalar = self.prior_bias_mu is None or bool((self.prior_bias_mu == self.prior_mean).all())
+            st = (key, w_scalar, b_scalar)
+            self.__dict__["_btx_loc_state"] = st
+        return (None if st[1] else self.prior_weight_mu), (None if st[2] else self.prior_bias_mu)
+
+    def _kl_sample_index(self):
+        """the MC sample index the sampled KL draws at: the index the layer's last forward consumed — the KL of a step belongs to the
+        step's sample, in an eager step as in a captured one, whose kernels read the device word — or, when no forward has run since
+        set_sample_index(), the pinned index"""
+        s = self.__dict__.get("_btx_kl_sample")
+        return self._btx_sample if s is None else s
+
+    def materialize_kl_noise(self, sample_idx, sample_dev=None):
+        """The draws of the sampled KL (BTX-KLMC v1) at MC sample `sample_idx` (or the device word `sample_dev`): dict(eps_w
+        [S, *logical weight shape], eps_b [S, out]) with S = kl_samples — draw j is btx_fill_eps at stream BTX_STREAM_KL_W | j << 8
+        over the unpadded GEMM-major order of the weight (BTX_STREAM_KL_B over the bias)."""
+        mu, _ = self._w()
+        seed, lid, S = _rng.seed(), self._btx_layer_id, self._btx_kl_samples
+        ew = [BF.unpack_gemm_major(BF.fill_eps_hip(mu.numel(), mu.device, seed, sample_idx, lid, _lib.STREAM_KL_W | (j << 8),
+                                                   sample_dev=sample_dev), tuple(mu.shape), self._op) for j in range(S)]
+        d = {"eps_w": torch.stack(ew)}
+        if self.mu_bias is not None:
+            d["eps_b"] = torch.stack([BF.fill_eps_hip(self.mu_bias.numel(), mu.device, seed, sample_idx, lid, _lib.STREAM_KL_B | (j << 8),
+                                                      sample_dev=sample_dev) for j in range(S)])
+        return d
+
+    def _kl_mc_aten(self):
+        """the sampled KL as ATen ops (CPU tensors, backend "torch"): eps from torch's generator, differentiable by autograd"""
+        mu, rho = self._w()
+        mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
+        prior, S = self._btx_prior, self._btx_kl_samples
+        loc_w, loc_b = self._kl_locations()
+        eps = torch.empty((S,) + tuple(mu.shape), dtype=mu.dtype, device=mu.device).normal_()
+        kl = BF.kl_mc_aten(mu, BF.softplus_naive(rho), eps, prior, loc_w)
+        if self.mu_bias is not None:
+            eps_b = torch.empty((S,) + tuple(self.mu_bias.shape), dtype=mu.dtype, device=mu.device).normal_()
+            kl = kl + BF.kl_mc_aten(self.mu_bias, BF.softplus_naive(self.rho_bias), eps_b, prior, loc_b)
+        return kl
+
     def kl_loss(self):
         mu, rho = self._w()
+        if self.__dict__.get("_btx_prior") is not None and not self._use_hip(mu):
+            return self._kl_mc_aten()
         if not self._use_hip(mu):
             mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
             kl = self.kl_div(mu, BF.softplus_naive(rho), self.prior_weight_mu, self.prior_weight_sigma)
@@ -349,6 +427,7 @@ class _VariationalNd(BaseVariationalLayer_):
             raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
         s_idx = self._btx_sample
         self.__dict__["_btx_sample"] = s_idx + 1
+        self.__dict__["_btx_kl_sample"] = s_idx
         unbatched = self._op.nd > 0 and x.dim() == self._op.nd + 1
         sdev = getattr(self, "_btx_sample_dev", None)
         if BF.lrt_train_ok(self, x):
@@ -363,6 +442,9 @@ class _VariationalNd(BaseVariationalLayer_):
     def forward(self, input, return_kl=True):
         if self.dnn_to_bnn_flag:
             return_kl = False
+        if return_kl and self.__dict__.get("_btx_prior") is not None and (self.quant_prepare or not self._use_hip(input)):
+            # the ATen routes spell the Gaussian KL inline: run them without it and add the sampled KL
+            return self.forward(input, return_kl=False), self.kl_loss()
         if self.quant_prepare:
             return self._forward_calibrate(input, return_kl)
         if self._use_hip(input):
@@ -374,6 +456,7 @@ class _VariationalNd(BaseVariationalLayer_):
                 from .. import autograd as _ag
                 s_idx = self._btx_sample
                 self.__dict__["_btx_sample"] = s_idx + 1
+                self.__dict__["_btx_kl_sample"] = s_idx
                 mu, rho = self._w()
                 out = _ag.ContractFn.apply(self, s_idx, input, mu, rho, self.mu_bias, self.rho_bias)
             else:
@@ -462,6 +545,7 @@ class _VariationalNd(BaseVariationalLayer_):
         if sample_idx is None:
             sample_idx = self._btx_sample
             self.__dict__["_btx_sample"] = sample_idx + lanes
+            self.__dict__["_btx_kl_sample"] = sample_idx
         kind = self._kind()
         if kind == _lib.KIND_LRT and noise is not None:
             raise _lib.BtxError("local reparameterization has no explicit-noise mode: its zeta is materialize_noise()['zeta']")
@@ -739,6 +823,17 @@ class _VariationalLSTM(BaseVariationalLayer_):
                   posterior_rho_init=posterior_rho_init, bias=bias)
         self.ih = self._linear_cls(in_features=in_features, out_features=out_features * 4, **kw)
         self.hh = self._linear_cls(in_features=out_features, out_features=out_features * 4, **kw)
+        for lin in (self.ih, self.hh):
+            lin.__dict__["_btx_no_prior"] = self._NO_PRIOR
+
+    _NO_PRIOR = ("non-Gaussian priors are not supported on the Bayesian LSTM classes: the fused sequence counts ONE KL term times the "
+                 "number of steps, while the eager loop would draw a new estimate per step")
+
+    def set_prior(self, prior, kl_samples=1):
+        from .. import priors as _priors
+        if _priors.check_prior(prior) is not None:
+            raise _lib.BtxError(self._NO_PRIOR)
+        return self
 
     def kl_loss(self):
         return self.ih.kl_loss() + self.hh.kl_loss()

@@ -138,6 +138,13 @@ class _QuantizedReparameterization(_base.BaseVariationalLayer_):
     def kl_loss(self):
         return 0
 
+    def set_prior(self, prior, kl_samples=1):
+        from ... import priors as _priors
+        if _priors.check_prior(prior) is not None:
+            raise _lib.BtxError("non-Gaussian priors are not supported on the quantized layers: they are inference only (kl_loss() is 0); "
+                                "set the prior on the float model before bnn_to_qbnn")
+        return self
+
     def _out_ch(self):
         return self.out_features if self._nd == 0 else self.out_channels
 

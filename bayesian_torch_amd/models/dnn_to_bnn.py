@@ -6,6 +6,8 @@ looked up as `<ClassName><params["type"]>` in `bayesian_torch_amd.layers`; the r
 prior_mu, prior_sigma, posterior_mu_init, posterior_rho_init, type, moped_enable (KeyError if absent), moped_delta;
 `output_padding` / `padding_mode` are NOT forwarded; converted layers get `dnn_to_bnn_flag = True` (forward returns
 only `out`).  nn.LSTM children become LSTM<type> (two Bayesian Linear layers per time step).
+Beyond the reference: the optional keys "prior" (a bayesian_torch_amd.priors prior) and "kl_samples" install a non-Gaussian weight
+prior on every converted layer (layer.set_prior); without them nothing changes.
 """
 import torch
 
@@ -71,6 +73,12 @@ def bnn_lstm_layer(params, d):
     return bnn_layer
 
 
+def _with_prior(bnn_layer, params):
+    if "prior" in params:
+        bnn_layer.set_prior(params["prior"], params.get("kl_samples", 1))
+    return bnn_layer
+
+
 def dnn_to_bnn(m, bnn_prior_parameters):
     for name, child in list(m._modules.items()):
         if child is None:
@@ -79,12 +87,31 @@ def dnn_to_bnn(m, bnn_prior_parameters):
         if child._modules:
             dnn_to_bnn(child, bnn_prior_parameters)
         elif "Conv" in cname:
-            setattr(m, name, bnn_conv_layer(bnn_prior_parameters, child).to(child.weight.device))
+            setattr(m, name, _with_prior(bnn_conv_layer(bnn_prior_parameters, child), bnn_prior_parameters).to(child.weight.device))
         elif "Linear" in cname:
-            setattr(m, name, bnn_linear_layer(bnn_prior_parameters, child).to(child.weight.device))
+            setattr(m, name, _with_prior(bnn_linear_layer(bnn_prior_parameters, child), bnn_prior_parameters).to(child.weight.device))
         elif "LSTM" in cname:
-            setattr(m, name, bnn_lstm_layer(bnn_prior_parameters, child).to(next(child.parameters()).device))
+            setattr(m, name, _with_prior(bnn_lstm_layer(bnn_prior_parameters, child), bnn_prior_parameters)
+                    .to(next(child.parameters()).device))
     return
+
+
+def set_prior(model, prior, kl_samples=1):
+    """layer.set_prior(prior, kl_samples) on every variational layer of `model` (priors.py; None / GaussianPrior: back to the closed-form
+    Gaussian KL).  A model that holds a Bayesian LSTM or a quantized layer is refused for a non-Gaussian prior, before any layer is
+    changed.  Returns the model."""
+    from ..layers.base_variational_layer import _VariationalLSTM, _VariationalNd
+    from ..priors import check_prior
+    mods = [mod for mod in model.modules() if hasattr(mod, "set_prior")]
+    if check_prior(prior) is not None:
+        for mod in mods:  # the refusing classes first: nothing is half-set
+            if not isinstance(mod, _VariationalNd):
+                mod.set_prior(prior, kl_samples)
+    inner = {id(lin) for mod in mods if isinstance(mod, _VariationalLSTM) for lin in (mod.ih, mod.hh)}
+    for mod in mods:
+        if isinstance(mod, _VariationalNd) and id(mod) not in inner:
+            mod.set_prior(prior, kl_samples)
+    return model
 
 
 def get_kl_loss(m):

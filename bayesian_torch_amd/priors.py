@@ -1,0 +1,156 @@
+"""Weight priors for the variational layers (BTX-KLMC v1).
+
+A layer's prior is `GaussianPrior` — the reference's only choice, N(prior_mean, prior_variance) with the closed-form KL of
+`kl_div` — unless `layer.set_prior(prior, kl_samples)` / `models.set_prior(model, prior, kl_samples)` installs one of
+
+    ScaleMixturePrior(pi, sigma1, sigma2, mu=0.)   pi N(mu, sigma1^2) + (1 - pi) N(mu, sigma2^2)   (Blundell et al. 2015)
+    LaplacePrior(b, mu=0.)                         exp(-|w - mu| / b) / (2 b)
+    StudentTPrior(nu, scale, mu=0.)                Student-t with nu degrees of freedom, location mu, scale `scale`
+
+for which KL(q || p) has no closed form and is estimated from `kl_samples` weight draws per step (entropy in closed form, the
+cross term sampled: functional.kl_mc_aten on the CPU, btx_kl_mc_model on the GPU).  `log_prob(w)` and `score(w)` = d log p / dw
+are plain torch and accept a tensor location (`loc=`: the MOPED `prior_weight_mu` buffer) in place of the scalar `mu`.
+Priors are configuration, not state: plain picklable objects that never enter a state_dict.
+"""
+import math
+
+import torch
+
+PRIOR_GAUSS_MIX2, PRIOR_LAPLACE, PRIOR_STUDENT_T = 1, 2, 3  # BTX_PRIOR_* of include/btx.h
+
+
+def _finite(name, v):
+    v = float(v)
+    if not math.isfinite(v):
+        raise ValueError("%s must be finite (got %r)" % (name, v))
+    return v
+
+
+def _positive(name, v):
+    v = _finite(name, v)
+    if not v > 0.0:
+        raise ValueError("%s must be > 0 (got %r)" % (name, v))
+    return v
+
+
+class Prior:
+    """base of the priors: `mu` is the scalar location; `code` / `params` are what the C entry points take (BtxPrior)"""
+
+    code = 0
+    mu = 0.0
+
+    def params(self):
+        return ()
+
+    def _d(self, w, loc):
+        return w - (self.mu if loc is None else loc)
+
+    def __eq__(self, other):
+        return type(self) is type(other) and self.__dict__ == other.__dict__
+
+    def __hash__(self):
+        return hash((type(self).__name__,) + tuple(sorted(self.__dict__.items())))
+
+
+class GaussianPrior(Prior):
+    """N(mu, sigma^2): today's behaviour.  `layer.set_prior(GaussianPrior())` (or None) returns a layer to the closed-form KL against
+    its own prior_mean / prior_variance buffers; mu / sigma here only serve log_prob / score."""
+
+    def __init__(self, mu=0.0, sigma=1.0):
+        self.mu, self.sigma = _finite("mu", mu), _positive("sigma", sigma)
+
+    def log_prob(self, w, loc=None):
+        d = self._d(w, loc)
+        return -math.log(self.sigma) - 0.5 * math.log(2.0 * math.pi) - d * d / (2.0 * self.sigma ** 2)
+
+    def score(self, w, loc=None):
+        return -self._d(w, loc) / self.sigma ** 2
+
+    def __repr__(self):
+        return "GaussianPrior(mu=%g, sigma=%g)" % (self.mu, self.sigma)
+
+
+class ScaleMixturePrior(Prior):
+    code = PRIOR_GAUSS_MIX2
+
+    def __init__(self, pi, sigma1, sigma2, mu=0.0):
+        self.pi = _finite("pi", pi)
+        if not 0.0 < self.pi < 1.0:
+            raise ValueError("pi must lie in (0, 1) (got %r)" % (pi,))
+        self.sigma1, self.sigma2, self.mu = _positive("sigma1", sigma1), _positive("sigma2", sigma2), _finite("mu", mu)
+
+    def params(self):
+        return (self.pi, self.sigma1, self.sigma2)
+
+    def _ab(self, d):
+        q = d * d
+        a = math.log(self.pi) - math.log(self.sigma1) - q / (2.0 * self.sigma1 ** 2)
+        b = math.log1p(-self.pi) - math.log(self.sigma2) - q / (2.0 * self.sigma2 ** 2)
+        return a, b
+
+    def log_prob(self, w, loc=None):
+        a, b = self._ab(self._d(w, loc))
+        return torch.logaddexp(a, b) - 0.5 * math.log(2.0 * math.pi)
+
+    def score(self, w, loc=None):
+        d = self._d(w, loc)
+        a, b = self._ab(d)
+        r1 = torch.sigmoid(a - b)  # the first component's responsibility
+        return -d * (r1 / self.sigma1 ** 2 + (1.0 - r1) / self.sigma2 ** 2)
+
+    def __repr__(self):
+        return "ScaleMixturePrior(pi=%g, sigma1=%g, sigma2=%g, mu=%g)" % (self.pi, self.sigma1, self.sigma2, self.mu)
+
+
+class LaplacePrior(Prior):
+    code = PRIOR_LAPLACE
+
+    def __init__(self, b, mu=0.0):
+        self.b, self.mu = _positive("b", b), _finite("mu", mu)
+
+    def params(self):
+        return (self.b,)
+
+    def log_prob(self, w, loc=None):
+        return -math.log(2.0 * self.b) - self._d(w, loc).abs() / self.b
+
+    def score(self, w, loc=None):
+        return -torch.sign(self._d(w, loc)) / self.b
+
+    def __repr__(self):
+        return "LaplacePrior(b=%g, mu=%g)" % (self.b, self.mu)
+
+
+class StudentTPrior(Prior):
+    code = PRIOR_STUDENT_T
+
+    def __init__(self, nu, scale, mu=0.0):
+        self.nu, self.scale, self.mu = _positive("nu", nu), _positive("scale", scale), _finite("mu", mu)
+
+    def params(self):
+        return (self.nu, self.scale)
+
+    def log_norm(self):
+        nu = self.nu
+        return math.lgamma(0.5 * (nu + 1.0)) - math.lgamma(0.5 * nu) - 0.5 * math.log(nu * math.pi) - math.log(self.scale)
+
+    def log_prob(self, w, loc=None):
+        d = self._d(w, loc)
+        return self.log_norm() - 0.5 * (self.nu + 1.0) * torch.log1p(d * d / (self.nu * self.scale ** 2))
+
+    def score(self, w, loc=None):
+        d = self._d(w, loc)
+        return -(self.nu + 1.0) * d / (self.nu * self.scale ** 2 + d * d)
+
+    def __repr__(self):
+        return "StudentTPrior(nu=%g, scale=%g, mu=%g)" % (self.nu, self.scale, self.mu)
+
+
+def is_gaussian(prior):
+    return prior is None or isinstance(prior, GaussianPrior)
+
+
+def check_prior(prior):
+    if not (prior is None or isinstance(prior, Prior)):
+        raise TypeError("prior must be None or a bayesian_torch_amd.priors prior (got %s)" % type(prior).__name__)
+    return None if is_gaussian(prior) else prior

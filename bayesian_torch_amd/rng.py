@@ -58,6 +58,7 @@ def set_sample_index(model, idx, presample=False):
     for m in model.modules():
         if hasattr(m, "_btx_layer_id"):
             m._btx_sample = int(idx)
+            m.__dict__.pop("_btx_kl_sample", None)  # the sampled KL (BTX-KLMC v1) draws at the pinned index until a forward consumes one
             sdev = getattr(m, "_btx_sample_dev", None)  # a live mc.GraphedMC keeps the index on the device: keep it in step
             if sdev is not None:
                 devs[sdev.data_ptr()] = sdev
@@ -106,6 +107,7 @@ def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=Non
         m.__dict__["_btx_lane_batch"] = int(batch)
         m.__dict__["_btx_sample_dev"] = sample_dev
         m._btx_sample = int(indices[0])
+        m.__dict__.pop("_btx_kl_sample", None)
     if presample:
         _presample(model, int(indices[0]))
     return sample_dev

@@ -190,6 +190,53 @@ size_t btx_kl_model_workspace_bytes(int n_items);
 int btx_kl_gauss_model(const BtxKlItem* items_host, int n_items, float* kl_out, void* ws, size_t ws_bytes, void* stream);
 int btx_kl_gauss_model_bwd(const BtxKlItem* items_host, int n_items, const float* grad_out, void* stream);
 
+/* K1c. Sampled KL against a non-Gaussian weight prior (BTX-KLMC v1; csrc/btx_klmc.hip).
+ * Per tensor of n elements, sigma = log1p(exp(rho)), `draws` = S >= 1:
+ *   eps_j[i] = BTX-RNG v1 normal at element index i, stream rng_stream | (j << 8)   (BTX_STREAM_KL_W weights, _KL_B biases)
+ *   w_j[i]   = mu[i] + sigma[i] eps_j[i]
+ *   kl       = (1 / n) sum_i [ -log sigma[i] - (1 + log 2 pi) / 2 - (1 / S) sum_j log p(w_j[i]) ]     summed over the items
+ * The entropy of q is closed-form, only E_q[-log p] is sampled; btx_fill_eps(n, rng, rng_stream | (j << 8)) returns eps_j bit
+ * for bit.  i is the index in the order of mu / rho as handed over (the Python face hands over the unpadded GEMM-major order).
+ * Backward, with s = d log p / dw and g = *grad_out:
+ *   dmu[i]  = -(g / n) (1 / S) sum_j s(w_j[i])        drho[i] = (g / n) [ -1 / sigma[i] - (1 / S) sum_j s(w_j[i]) eps_j[i] ] sigmoid(rho[i])
+ * Priors, d = w - loc (loc_t[i] when loc_t is given, else prior.loc):
+ *   BTX_PRIOR_GAUSS_MIX2  p0 = pi in (0, 1), p1 = sigma1 > 0, p2 = sigma2 > 0:  pi N(loc, sigma1^2) + (1 - pi) N(loc, sigma2^2)
+ *   BTX_PRIOR_LAPLACE     p0 = b > 0:                                           exp(-|d| / b) / (2 b)
+ *   BTX_PRIOR_STUDENT_T   p0 = nu > 0, p1 = scale t > 0:                        Student-t density of d / t, over t
+ * The host derives every constant in double.  One launch per 48 items plus one fixed-order final reduce (kl_out overwritten, or
+ * += with BTX_FLAG_KL_ACCUM); the backward is one element-wise launch per 48 items that writes every element of dmu / drho, no
+ * atomics, nothing saved.  sample_idx_dev (nullable) wins over sample_idx and is read by the kernels (captured steps).
+ * Parameter and gradient pointers on any 4-byte boundary are accepted (off the 16-byte grid: scalar accesses); ws: 8-byte aligned
+ * (BTX_E_ALIGN), btx_kl_mc_workspace_bytes(n_items) bytes.  Before any launch: BTX_E_NULL (a required pointer), BTX_E_SHAPE
+ * (n == 0, n_items < 1, draws < 1 or >= 2^24, rng_stream >= 256, a prior parameter out of range), BTX_E_UNSUPPORTED (unknown
+ * prior type, n > 0xfffffffc), BTX_E_WORKSPACE. */
+#define BTX_STREAM_KL_W 5u
+#define BTX_STREAM_KL_B 6u
+#define BTX_PRIOR_GAUSS_MIX2 1
+#define BTX_PRIOR_LAPLACE    2
+#define BTX_PRIOR_STUDENT_T  3
+typedef struct BtxPrior {
+  int32_t type;
+  float   loc, p0, p1, p2;
+} BtxPrior;
+typedef struct BtxKlMcItem {
+  const float* mu;
+  const float* rho;
+  const float* loc_t;          /* nullable */
+  float*       dmu;            /* backward only */
+  float*       drho;           /* backward only */
+  size_t       n;
+  BtxPrior     prior;
+  uint32_t     layer_id, rng_stream;
+  uint32_t     sample_idx;
+  const uint32_t* sample_idx_dev;  /* nullable; wins */
+} BtxKlMcItem;
+size_t btx_kl_mc_workspace_bytes(int n_items);
+int btx_kl_mc_model(const BtxKlMcItem* items_host, int n_items, uint64_t seed, int draws, float* kl_out, uint32_t flags,
+                    void* ws, size_t ws_bytes, void* stream);
+int btx_kl_mc_model_bwd(const BtxKlMcItem* items_host, int n_items, uint64_t seed, int draws, const float* grad_out,
+                        void* stream);
+
 /* K2-K5. Fused sample-and-contract forward of one variational layer.
  * Replaces the whole body of
  *   LinearReparameterization.forward   layers/variational_layers/linear_variational.py:157-178
