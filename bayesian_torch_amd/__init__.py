@@ -5,7 +5,7 @@ Drop-in surface (same names as the reference package `bayesian_torch`):
     bayesian_torch_amd.models.dnn_to_bnn.{dnn_to_bnn, get_kl_loss}
     bayesian_torch_amd.utils.util.get_rho
 Beyond the reference: bayesian_torch_amd.priors (scale-mixture, Laplace and Student-t weight priors with a sampled KL; layer.set_prior,
-models.set_prior).
+models.set_prior), priors.LogUniformPrior and bayesian_torch_amd.sparsity (sparse variational dropout: log-alpha statistics, pruning).
 `install_alias()` registers this package under the name `bayesian_torch` so existing imports resolve here.
 
 GPU tensors run through hand-written gfx950 kernels in libbtx.so (C-ABI: include/btx.h); see DESIGN.md.
@@ -17,6 +17,7 @@ from . import layers, models, utils  # noqa: F401
 from . import optim  # noqa: F401
 from . import parallel  # noqa: F401
 from . import priors  # noqa: F401
+from . import sparsity  # noqa: F401
 from .functional import set_precision, get_precision, set_output_layout  # noqa: F401
 from .layers.base_variational_layer import set_backend  # noqa: F401
 from .models.dnn_to_bnn import dnn_to_bnn, get_kl_loss  # noqa: F401

@@ -16,6 +16,10 @@ E_UNSUPPORTED = -3
 STREAM_EPS_W, STREAM_EPS_B, STREAM_SIGN_IN, STREAM_SIGN_OUT, STREAM_OUT_NOISE = 0, 1, 2, 3, 4
 STREAM_KL_W, STREAM_KL_B = 5, 6   # BTX-KLMC v1: the sampled KL's own draws (draw j: stream | j << 8)
 PRIOR_GAUSS_MIX2, PRIOR_LAPLACE, PRIOR_STUDENT_T = 1, 2, 3
+# BTX-SVD v1: reduction codes, the log-alpha clamp, the rho of a pruned weight, the layout of the statistics words
+REDUCE_MEAN, REDUCE_SUM = 0, 1
+LOGALPHA_MAX, RHO_PRUNED = 20.0, -40.0
+LOGALPHA_MAX_THRESHOLDS, LOGALPHA_MAX_BINS, LOGALPHA_STATS_WORDS, LOGALPHA_ZERO_MU = 8, 4096, 16, 8
 ABI_VERSION = 9
 FLAG_LANES_SHIFT = 16
 FLAG_LANES_MASK = 0xff << FLAG_LANES_SHIFT
@@ -101,6 +105,15 @@ class KlMcItem(ctypes.Structure):  # BtxKlMcItem
                 ("rng_stream", ctypes.c_uint32), ("sample_idx", ctypes.c_uint32), ("sample_idx_dev", ctypes.c_void_p)]
 
 
+class KlLogUItem(ctypes.Structure):  # BtxKlLogUItem
+    _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("dmu", ctypes.c_void_p), ("drho", ctypes.c_void_p),
+                ("n", ctypes.c_size_t), ("reduction", ctypes.c_int32)]
+
+
+class LogAlphaItem(ctypes.Structure):  # BtxLogAlphaItem
+    _fields_ = [("mu", ctypes.c_void_p), ("rho", ctypes.c_void_p), ("n", ctypes.c_size_t)]
+
+
 class Q8Chain(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("s_sigma", "s_mu", "s_eps", "inv_s_eps", "s_d", "inv_s_d", "inv_s_w")] + \
                [("bias_div", ctypes.c_double)]
@@ -160,7 +173,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_mc_moments_lanes", "btx_mc_gnll_workspace_bytes", "btx_mc_gnll_fwd", "btx_mc_gnll_bwd",
            "btx_reg_eval_workspace_bytes", "btx_reg_eval_update",
            "btx_lrt_fwd_train", "btx_lrt_bwd_workspace_bytes", "btx_lrt_bwd",
-           "btx_kl_mc_workspace_bytes", "btx_kl_mc_model", "btx_kl_mc_model_bwd")
+           "btx_kl_mc_workspace_bytes", "btx_kl_mc_model", "btx_kl_mc_model_bwd",
+           "btx_kl_logu_workspace_bytes", "btx_kl_logu_model", "btx_kl_logu_model_bwd", "btx_logalpha_stats", "btx_logalpha_prune")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -367,6 +381,16 @@ def lib():
     L.btx_kl_mc_model.argtypes = [ctypes.POINTER(KlMcItem), i32, ctypes.c_uint64, i32, vp, u32, vp, sz, vp]
     L.btx_kl_mc_model_bwd.restype = i32
     L.btx_kl_mc_model_bwd.argtypes = [ctypes.POINTER(KlMcItem), i32, ctypes.c_uint64, i32, vp, vp]
+    L.btx_kl_logu_workspace_bytes.restype = sz
+    L.btx_kl_logu_workspace_bytes.argtypes = [i32]
+    L.btx_kl_logu_model.restype = i32
+    L.btx_kl_logu_model.argtypes = [ctypes.POINTER(KlLogUItem), i32, vp, vp, u32, vp, sz, vp]
+    L.btx_kl_logu_model_bwd.restype = i32
+    L.btx_kl_logu_model_bwd.argtypes = [ctypes.POINTER(KlLogUItem), i32, vp, vp]
+    L.btx_logalpha_stats.restype = i32
+    L.btx_logalpha_stats.argtypes = [ctypes.POINTER(LogAlphaItem), i32, ctypes.POINTER(ctypes.c_float), i32, i32, vp, vp, vp]
+    L.btx_logalpha_prune.restype = i32
+    L.btx_logalpha_prune.argtypes = [ctypes.POINTER(LogAlphaItem), i32, ctypes.c_float, vp, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

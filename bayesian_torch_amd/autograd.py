@@ -450,9 +450,80 @@ def _kl_mc_of_layers(layers):
     return total
 
 
+class KlLogUFn(torch.autograd.Function):
+    """sum of the per-tensor KLs against the log-uniform prior (BTX-SVD v1) of `n` (mu, rho) pairs on the HIP backend,
+    with gradients: btx_kl_logu_model forward, btx_kl_logu_model_bwd backward (nothing saved but the parameters).  The kernels are
+    element-wise, so every (mu, rho) pair that shares one dense element order is read through its storage in place, and the gradients
+    are written in that order and handed back as logical (strided) views; a pair whose layouts differ (a `.data` replacement, a
+    non-dense view) is read through row-major copies and its gradients come back as plain reshapes.  meta: per pair the reduction,
+    "mean" | "sum"."""
+
+    @staticmethod
+    def forward(ctx, meta, *params):
+        ctx.meta = meta
+        ctx.save_for_backward(*params)
+        return BF.kl_logu_model_hip(_logu_entries(meta, params))
+
+    @staticmethod
+    def backward(ctx, g):
+        params, meta = ctx.saved_tensors, ctx.meta
+        entries = _logu_entries(meta, params)
+        grads = [(torch.empty_like(mu_e), torch.empty_like(mu_e)) for mu_e, _rho_e, _ in entries]
+        BF.kl_logu_model_bwd_hip(entries, grads, g)
+        res = []
+        for i, (gm, gr) in enumerate(grads):
+            mu, rho = params[2 * i], params[2 * i + 1]
+            in_place = BF.same_dense_order(mu, rho)
+            res += [_logical_like(gm, mu, in_place), _logical_like(gr, rho, in_place)]
+        return (None,) + tuple(res)
+
+
+def _logical_like(flat, p, in_place):
+    """the logical-shape tensor over a gradient buffer of parameter `p`: a strided view in p's own element order when the entry was
+    p's storage in place, a plain reshape when the entry was a contiguous (row-major) copy"""
+    if in_place:
+        return flat.as_strided(tuple(p.shape), tuple(p.stride()))
+    return flat.reshape(p.shape)
+
+
+def _logu_entries(meta, params):
+    """the kernel's items: (mu, rho) through their dense storage in place where the two share ONE dense element order
+    (functional.same_dense_order), else row-major copies of both — a `.data` replacement may leave the two in different layouts"""
+    out = []
+    for i, reduction in enumerate(meta):
+        mu, rho = params[2 * i], params[2 * i + 1]
+        if not BF.same_dense_order(mu, rho):
+            mu, rho = mu.detach().contiguous(), rho.detach().contiguous()
+        out.append((BF.flat_f32(mu), BF.flat_f32(rho), reduction))
+    return out
+
+
+def _kl_logu_of_layers(layers):
+    """the KL of the layers with a log-uniform prior: ONE launch group for all their tensors"""
+    params, meta = [], []
+    for layer in layers:
+        mu, rho = layer._w()
+        params += [mu, rho]
+        meta.append(layer._btx_prior.reduction)
+        if layer.mu_bias is not None:
+            params += [layer.mu_bias, layer.rho_bias]
+            meta.append(layer._btx_prior.reduction)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in params):
+        return KlLogUFn.apply(tuple(meta), *params)
+    return BF.kl_logu_model_hip(_logu_entries(meta, params))
+
+
 def kl_of_layers(layers):
     """get_kl_loss on the HIP backend: one launch for every tensor of every layer; differentiable when needed.  Layers with a
-    non-Gaussian prior (layer.set_prior) go through the sampled KL in one launch of their own, and the two scalars are added."""
+    non-Gaussian prior (layer.set_prior) go through a launch group of their own — the sampled KL (KlMcFn) or the log-uniform prior's
+    (KlLogUFn) — and the scalars are added in a fixed order: (Gaussian + sampled) + log-uniform, each group in module order."""
+    logu = [layer for layer in layers if getattr(layer.__dict__.get("_btx_prior"), "deterministic", False)]
+    if logu:
+        kl_logu = _kl_logu_of_layers(logu)
+        layers = [layer for layer in layers if not getattr(layer.__dict__.get("_btx_prior"), "deterministic", False)]
+        if not layers:
+            return kl_logu
+        return kl_of_layers(layers) + kl_logu
     mc = [layer for layer in layers if layer.__dict__.get("_btx_prior") is not None]
     if mc:
         kl_mc = _kl_mc_of_layers(mc)

@@ -744,6 +744,140 @@ def kl_mc_aten(mu, sigma, eps, prior, loc=None):
     return (-torch.log(sigma) - 0.5 * (1.0 + math.log(2.0 * math.pi)) - cross).mean()
 
 
+# ---- BTX-SVD v1: the log-uniform prior's KL, log-alpha statistics, pruning -----------------------------------------
+SVD_EPS, SVD_K1, SVD_K2, SVD_K3 = 1e-8, 0.63576, 1.87320, 1.48695
+
+
+def dense_flat(t):
+    """the 1-D view of a tensor's storage when its elements fill one dense block in SOME order (contiguous tensors, the permuted views
+    of gemm_major_param), else None.  The element-wise kernels of BTX-SVD v1 read and write parameters through it, in place."""
+    t = t.detach()
+    dims = sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1)
+    run = 1
+    for st, sz in dims:
+        if st != run:
+            return None
+        run *= sz
+    return t.as_strided((t.numel(),), (1,), t.storage_offset())
+
+
+def same_dense_order(a, b):
+    """True when a and b (same shape) are both dense and stored in ONE common element order: element k of dense_flat(a) and of
+    dense_flat(b) is then the same logical element, which is what the element-wise kernels of BTX-SVD v1 need of (mu, rho)"""
+    return tuple(a.stride()) == tuple(b.stride()) and dense_flat(a) is not None and dense_flat(b) is not None
+
+
+def flat_f32(t):
+    """the storage-order view of a parameter for the element-wise kernels; a contiguous copy where the tensor is not dense"""
+    if t.dtype != torch.float32:
+        raise _lib.BtxError("variational parameters must be float32 (got %s)" % t.dtype)
+    v = dense_flat(t)
+    return v if v is not None else t.detach().contiguous().reshape(-1)
+
+
+def _reduce_code(reduction):
+    try:
+        return {"mean": _lib.REDUCE_MEAN, "sum": _lib.REDUCE_SUM}[reduction]
+    except KeyError:
+        raise ValueError("reduction must be 'mean' or 'sum' (got %r)" % (reduction,)) from None
+
+
+def _kl_logu_items(entries, grads=None):
+    """entries = [(mu, rho, reduction)]: same-order dense f32 tensors (any 4-byte boundary) and 'mean' | 'sum'"""
+    arr = (_lib.KlLogUItem * len(entries))()
+    for i, (mu, rho, reduction) in enumerate(entries):
+        it = arr[i]
+        it.mu, it.rho, it.n, it.reduction = mu.data_ptr(), rho.data_ptr(), mu.numel(), _reduce_code(reduction)
+        if grads is not None:
+            it.dmu, it.drho = grads[i][0].data_ptr(), grads[i][1].data_ptr()
+    return arr
+
+
+def kl_logu_model_hip(entries, out=None, accumulate=False, terms=False):
+    """sum over tensors of the KL against the log-uniform prior (BTX-SVD v1), one launch + one fold per 48 tensors
+    (btx_kl_logu_model) -> 0-d f32; terms=True: -> (kl, the per-tensor terms as an f64 device tensor).  `out` / accumulate: add to
+    an existing scalar (BTX_FLAG_KL_ACCUM)."""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    ws = _workspace(dev, L.btx_kl_logu_workspace_bytes(len(entries)), stream)
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=dev)
+    t = torch.empty(len(entries), dtype=torch.float64, device=dev) if terms else None
+    _lib.check(L.btx_kl_logu_model(_kl_logu_items(entries), len(entries), out.data_ptr(), t.data_ptr() if terms else None,
+                                   _lib.FLAG_KL_ACCUM if accumulate else 0, ws.data_ptr(), ws.numel(), stream))
+    return (out, t) if terms else out
+
+
+def kl_logu_model_bwd_hip(entries, grads, grad_out):
+    """d(kl)/d(mu, rho) of every tensor into `grads` [(dmu, drho)] (same element order, every element written), scaled by the device
+    scalar `grad_out` (btx_kl_logu_model_bwd)"""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    g = grad_out.detach().reshape(()).to(device=dev, dtype=torch.float32).contiguous()
+    _lib.check(L.btx_kl_logu_model_bwd(_kl_logu_items(entries, grads), len(entries), g.data_ptr(),
+                                       torch.cuda.current_stream(dev).cuda_stream))
+
+
+def log_alpha_aten(mu, sigma):
+    """-> (la, inside): la = clamp(2 log sigma - log(mu^2 + EPS), -LA_MAX, LA_MAX) as differentiable ATen ops, with the clamp
+    semantics of BTX-SVD v1 — where the raw value lies STRICTLY outside the clamp (sigma that underflowed to 0 included) la is the
+    constant bound and both gradients are exactly 0, never 0 * inf; a raw value on a bound passes its gradient."""
+    lim = _lib.LOGALPHA_MAX
+    with torch.no_grad():
+        raw = 2.0 * torch.log(sigma) - torch.log(mu * mu + SVD_EPS)
+        inside = (raw >= -lim) & (raw <= lim)
+        bound = torch.where(raw > lim, torch.full_like(raw, lim), torch.full_like(raw, -lim))  # NaN: the kernel's fmax / fmin give -LA_MAX
+    one = torch.ones_like(mu)
+    mu_s, sig_s = torch.where(inside, mu, one), torch.where(inside, sigma, one)
+    la = torch.where(inside, 2.0 * torch.log(sig_s) - torch.log(mu_s * mu_s + SVD_EPS), bound)
+    return la, inside
+
+
+def kl_logu_terms_aten(la):
+    """kl_i of BTX-SVD v1 from the clamped log alpha (Molchanov et al. 2017, eq. 14)"""
+    return SVD_K1 - SVD_K1 * torch.sigmoid(SVD_K2 + SVD_K3 * la) + 0.5 * torch.log1p(torch.exp(-la))
+
+
+def kl_logu_aten(mu, sigma, reduction="mean"):
+    """BTX-SVD v1 as differentiable ATen ops: the mean ("mean") or the sum ("sum") over elements of kl_i.  The CPU route and backend
+    "torch", and what the tests model."""
+    _reduce_code(reduction)
+    t = kl_logu_terms_aten(log_alpha_aten(mu, sigma)[0])
+    return t.mean() if reduction == "mean" else t.sum()
+
+
+def _la_items(entries):
+    arr = (_lib.LogAlphaItem * len(entries))()
+    for i, (mu, rho) in enumerate(entries):
+        arr[i].mu, arr[i].rho, arr[i].n = mu.data_ptr(), rho.data_ptr(), mu.numel()
+    return arr
+
+
+def logalpha_stats_hip(entries, thresholds, bins=0):
+    """entries = [(mu, rho)] dense f32 device tensors -> ONE int64 device tensor [n, LOGALPHA_STATS_WORDS + bins]: per tensor the
+    counts above each threshold (words 0..7), count(mu == 0) (word 8) and the histogram (btx_logalpha_stats)"""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    n, W = len(entries), _lib.LOGALPHA_STATS_WORDS
+    buf = torch.empty(n * (W + bins), dtype=torch.int64, device=dev)
+    th = (ctypes.c_float * max(len(thresholds), 1))(*[float(t) for t in thresholds])
+    _lib.check(L.btx_logalpha_stats(_la_items(entries), n, th, len(thresholds), int(bins), buf.data_ptr(),
+                                    buf.data_ptr() + n * W * 8 if bins else None, torch.cuda.current_stream(dev).cuda_stream))
+    return torch.cat([buf[:n * W].reshape(n, W), buf[n * W:].reshape(n, bins)], 1) if bins else buf.reshape(n, W)
+
+
+def logalpha_prune_hip(entries, threshold):
+    """mu = 0, rho = RHO_PRUNED wherever la > threshold, IN PLACE through the raw pointers (the caller bumps the versions) -> int64
+    device tensor [n]: the pruned count of each tensor (btx_logalpha_prune)"""
+    L = _lib.lib()
+    dev = entries[0][0].device
+    n, W = len(entries), _lib.LOGALPHA_STATS_WORDS
+    buf = torch.empty(n * W, dtype=torch.int64, device=dev)
+    _lib.check(L.btx_logalpha_prune(_la_items(entries), n, float(threshold), buf.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return buf.reshape(n, W)[:, 0]
+
+
 def rowfuse_plan(op, x_shape):
     """Geometry of the row-fused execution of a small-C 2-D stem conv (BTX_FLAG_ROWFUSE), or None.  Decided by the
     layer geometry ONLY (never by dtypes), because the BTX-RNG index space of the layer follows this layout.

@@ -219,7 +219,9 @@ class _VariationalNd(BaseVariationalLayer_):
         estimated from `kl_samples` weight draws per call with the estimator's own noise streams (not the forward's draw).  The
         location is the prior's scalar `mu`, or the prior_weight_mu / prior_bias_mu buffers once they no longer hold the constructor's
         prior_mean (MOPED writes the deterministic weights there).  None or GaussianPrior restores the closed-form Gaussian KL against
-        prior_mean / prior_variance.  Configuration, not state: state_dict() is unchanged.  Returns the layer."""
+        prior_mean / prior_variance.  priors.LogUniformPrior (sparse variational dropout, BTX-SVD v1) has a deterministic
+        KL of log alpha = log(sigma^2 / mu^2): nothing is sampled (kl_samples must be 1) and it has no location (the prior_*_mu buffers
+        are ignored).  Configuration, not state: state_dict() is unchanged.  Returns the layer."""
         from .. import priors as _priors
         refused = self.__dict__.get("_btx_no_prior")
         prior = _priors.check_prior(prior)
@@ -228,12 +230,16 @@ class _VariationalNd(BaseVariationalLayer_):
         kl_samples = int(kl_samples)
         if not 1 <= kl_samples < (1 << 24):
             raise ValueError("kl_samples must be in [1, 2^24) (got %r)" % (kl_samples,))
+        if prior is not None and prior.deterministic and kl_samples != 1:
+            raise ValueError("%r has a deterministic KL (BTX-SVD v1): kl_samples must be 1 (got %r)" % (prior, kl_samples))
         self.__dict__["_btx_prior"] = prior
         self.__dict__["_btx_kl_samples"] = kl_samples if prior is not None else 1
         return self
 
     def extra_repr(self):
         prior = self.__dict__.get("_btx_prior")
+        if prior is not None and prior.deterministic:
+            return "prior=%r" % (prior,)
         return "" if prior is None else "prior=%r, kl_samples=%d" % (prior, self._btx_kl_samples)
 
     def _kl_locations(self):
@@ -271,10 +277,16 @@ class _VariationalNd(BaseVariationalLayer_):
         return d
 
     def _kl_mc_aten(self):
-        """the sampled KL as ATen ops (CPU tensors, backend "torch"): eps from torch's generator, differentiable by autograd"""
+        """the KL against a non-Gaussian prior as ATen ops (CPU tensors, backend "torch"), differentiable by autograd: sampled with eps
+        from torch's generator, or functional.kl_logu_aten for the log-uniform prior"""
         mu, rho = self._w()
         mu, rho = BF.plain_layout(mu), BF.plain_layout(rho)
         prior, S = self._btx_prior, self._btx_kl_samples
+        if prior.deterministic:  # the log-uniform prior (BTX-SVD v1): a function of log alpha, no draws, no location
+            kl = BF.kl_logu_aten(mu, BF.softplus_naive(rho), prior.reduction)
+            if self.mu_bias is not None:
+                kl = kl + BF.kl_logu_aten(self.mu_bias, BF.softplus_naive(self.rho_bias), prior.reduction)
+            return kl
         loc_w, loc_b = self._kl_locations()
         eps = torch.empty((S,) + tuple(mu.shape), dtype=mu.dtype, device=mu.device).normal_()
         kl = BF.kl_mc_aten(mu, BF.softplus_naive(rho), eps, prior, loc_w)

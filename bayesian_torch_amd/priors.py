@@ -8,8 +8,12 @@ A layer's prior is `GaussianPrior` — the reference's only choice, N(prior_mean
     StudentTPrior(nu, scale, mu=0.)                Student-t with nu degrees of freedom, location mu, scale `scale`
 
 for which KL(q || p) has no closed form and is estimated from `kl_samples` weight draws per step (entropy in closed form, the
-cross term sampled: functional.kl_mc_aten on the CPU, btx_kl_mc_model on the GPU).  `log_prob(w)` and `score(w)` = d log p / dw
-are plain torch and accept a tensor location (`loc=`: the MOPED `prior_weight_mu` buffer) in place of the scalar `mu`.
+cross term sampled: functional.kl_mc_aten on the CPU, btx_kl_mc_model on the GPU), or
+
+    LogUniformPrior(reduction="mean")              p(|w|) ~ 1 / |w|, sparse variational dropout (BTX-SVD v1)
+
+whose KL is a deterministic function of log alpha = log(sigma^2 / mu^2) (functional.kl_logu_aten, btx_kl_logu_model): no samples.
+`log_prob(w)` and `score(w)` = d log p / dw are plain torch and accept a tensor location (`loc=`: the MOPED `prior_weight_mu` buffer) in place of the scalar `mu`.
 Priors are configuration, not state: plain picklable objects that never enter a state_dict.
 """
 import math
@@ -38,6 +42,7 @@ class Prior:
 
     code = 0
     mu = 0.0
+    deterministic = False  # True: the KL needs no weight samples (LogUniformPrior)
 
     def params(self):
         return ()
@@ -144,6 +149,32 @@ class StudentTPrior(Prior):
 
     def __repr__(self):
         return "StudentTPrior(nu=%g, scale=%g, mu=%g)" % (self.nu, self.scale, self.mu)
+
+
+class LogUniformPrior(Prior):
+    """p(|w|) proportional to 1 / |w|: the improper prior of sparse variational dropout (Molchanov, Ashukha & Vetrov 2017; BTX-SVD v1,
+    DESIGN.md §23).  The KL of a Gaussian posterior against it depends on alpha = sigma^2 / mu^2 alone and has a tight
+    deterministic approximation, so nothing is sampled: `deterministic` keeps such a layer off the sampled path, and
+    `set_prior(prior, kl_samples)` accepts kl_samples == 1 only.  It has no location: the MOPED prior_*_mu buffers are ignored.
+    reduction: "mean" (the project's convention: per-tensor means, summed) or "sum" (the ELBO's KL, which the method's sparsifying
+    pressure needs).  log_prob / score are UNNORMALISED (-log|w| and its derivative -1 / w): the density has no finite integral."""
+
+    deterministic = True
+    REDUCTIONS = ("mean", "sum")
+
+    def __init__(self, reduction="mean"):
+        if reduction not in self.REDUCTIONS:
+            raise ValueError("reduction must be 'mean' or 'sum' (got %r)" % (reduction,))
+        self.reduction = reduction
+
+    def log_prob(self, w, loc=None):
+        return -torch.log(w.abs())
+
+    def score(self, w, loc=None):
+        return -1.0 / w
+
+    def __repr__(self):
+        return "LogUniformPrior(reduction=%r)" % (self.reduction,)
 
 
 def is_gaussian(prior):

@@ -237,6 +237,60 @@ int btx_kl_mc_model(const BtxKlMcItem* items_host, int n_items, uint64_t seed, i
 int btx_kl_mc_model_bwd(const BtxKlMcItem* items_host, int n_items, uint64_t seed, int draws, const float* grad_out,
                         void* stream);
 
+/* K1d. Sparse variational dropout (BTX-SVD v1; csrc/btx_svd.hip): the KL of a variational Gaussian against
+ * the log-uniform prior p(|w|) ~ 1 / |w| in the approximation of Molchanov, Ashukha & Vetrov (2017, eq. 14), the log-alpha
+ * statistics of a model and pruning in place.  Per tensor of n elements, sigma = log1p(exp(rho)), every step in f32:
+ *   la_raw = 2 log(sigma) - log(mu^2 + 1e-8)          la = min(max(la_raw, -20), 20)          (log alpha, BTX_LOGALPHA_MAX)
+ *   kl_i   = k1 - k1 sigmoid(k2 + k3 la) + 0.5 log1p(exp(-la))        k1 = 0.63576, k2 = 1.87320, k3 = 1.48695
+ *   kl     = c sum_i kl_i,  c = 1 / n (BTX_REDUCE_MEAN) or 1 (BTX_REDUCE_SUM), summed over the items
+ * Backward, g = *grad_out, s = sigmoid(k2 + k3 la):
+ *   d      = -(k1 k3 s (1 - s) + 0.5 sigmoid(-la)), 0 where la_raw lies strictly outside [-20, 20] (NaN included)
+ *   dmu[i] = g c d (-2 mu / (mu^2 + 1e-8))             drho[i] = g c d (2 sigmoid(rho) / sigma)
+ * Nothing is sampled.  The terms are element-wise: mu / rho are the tensor's dense storage in any element order.  One launch per 48
+ * items (the f64 partial of each block, at most 256 blocks per item), then a one-wave fold per launch: each item's partials in a
+ * fixed order that depends on n alone, the items in index order, in f64; kl_out overwritten, or += with BTX_FLAG_KL_ACCUM.
+ * terms_out (nullable): n_items doubles, the per-item term c sum_i kl_i — the same bits whichever call the item sits in.
+ * The backward is one element-wise launch per 48 items that writes every element of dmu / drho: no atomics, nothing saved.
+ * Parameter and gradient pointers on any 4-byte boundary are accepted (off the 16-byte grid: scalar accesses, same bits); ws and
+ * terms_out: 8-byte aligned (BTX_E_ALIGN), btx_kl_logu_workspace_bytes(n_items) bytes.  Before any launch: BTX_E_NULL (a required
+ * pointer), BTX_E_SHAPE (n == 0, n_items < 1, an unknown reduction code), BTX_E_UNSUPPORTED (n > 0xfffffffc), BTX_E_WORKSPACE.
+ *
+ * btx_logalpha_stats: per item BTX_LOGALPHA_STATS_WORDS uint64 words — [k] = count(la > thresholds[k]) for k < n_thresholds <=
+ * BTX_LOGALPHA_MAX_THRESHOLDS (strict; the other words of [0, 8) are 0), [8] = count(mu == 0), the rest 0 — and, when bins > 0
+ * (<= BTX_LOGALPHA_MAX_BINS), hist_out[item][b], b = min(bins - 1, floor((la + 20) * bins / 40)).  Integer counters: exact.
+ * btx_logalpha_prune: mu = 0 and rho = BTX_RHO_PRUNED (-40: sigma = 4.2e-18, sigma^2 still a normal f32) wherever la > threshold;
+ * word [0] of the item = the number of elements pruned, the other words 0.  Both clear their outputs themselves (memset nodes), are
+ * capturable and accept any 4-byte boundary for mu / rho; stats_out / hist_out: 8-byte aligned (BTX_E_ALIGN).  Before any launch:
+ * BTX_E_NULL, BTX_E_SHAPE (n == 0, n_items < 1, n_thresholds outside [0, 8], bins outside [0, 4096], a NaN threshold),
+ * BTX_E_UNSUPPORTED (n > 0xfffffffc). */
+#define BTX_REDUCE_MEAN 0
+#define BTX_REDUCE_SUM  1
+#define BTX_LOGALPHA_MAX 20.0f
+#define BTX_RHO_PRUNED (-40.0f)
+#define BTX_LOGALPHA_MAX_THRESHOLDS 8
+#define BTX_LOGALPHA_MAX_BINS 4096
+#define BTX_LOGALPHA_STATS_WORDS 16
+typedef struct BtxKlLogUItem {
+  const float* mu;
+  const float* rho;
+  float*       dmu;            /* backward only */
+  float*       drho;           /* backward only */
+  size_t       n;
+  int32_t      reduction;      /* BTX_REDUCE_* */
+} BtxKlLogUItem;
+typedef struct BtxLogAlphaItem {
+  float* mu;                   /* written by btx_logalpha_prune only */
+  float* rho;
+  size_t n;
+} BtxLogAlphaItem;
+size_t btx_kl_logu_workspace_bytes(int n_items);
+int btx_kl_logu_model(const BtxKlLogUItem* items_host, int n_items, float* kl_out, double* terms_out, uint32_t flags, void* ws,
+                      size_t ws_bytes, void* stream);
+int btx_kl_logu_model_bwd(const BtxKlLogUItem* items_host, int n_items, const float* grad_out, void* stream);
+int btx_logalpha_stats(const BtxLogAlphaItem* items_host, int n_items, const float* thresholds, int n_thresholds, int bins,
+                       uint64_t* stats_out, uint64_t* hist_out, void* stream);
+int btx_logalpha_prune(const BtxLogAlphaItem* items_host, int n_items, float threshold, uint64_t* stats_out, void* stream);
+
 /* K2-K5. Fused sample-and-contract forward of one variational layer.
  * Replaces the whole body of
  *   LinearReparameterization.forward   layers/variational_layers/linear_variational.py:157-178
