@@ -14,6 +14,10 @@
  *     (a hipStream_t passed as void*; NULL = the legacy default stream).  The caller owns every
  *     buffer and keeps it alive until the stream has passed the call.
  *   - stateless => thread-safe for distinct streams/buffers.
+ *   - workspaces (`ws`, `workspace`) and outputs may hold ANYTHING on entry: every workspace byte a call reads was written or
+ *     cleared by that same call, and every output element is written — except where a declaration below says that an argument
+ *     is accumulated or updated in place (BTX_FLAG_KL_ACCUM, the packed MC sums, evaluator and optimizer state, the BatchNorm
+ *     running estimates); DESIGN.md §24 lists them, tests/test_gpu_poison.py holds the rule.
  *
  * Data layout:
  *   activations  channels-last: x[nb][d][h][w][c]   (f32 or bf16, `act_dtype`)

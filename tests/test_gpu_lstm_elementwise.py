@@ -11,7 +11,8 @@ alike, and every element is compared (no percentile, no mean, nothing excluded).
                 materialize_noise(s + t): pins eps_w element n*Kr + k, eps_b element n, s_in, s_out and the index s + t.
   2. gates      saved pre-activations, all (t, b, n): |got - ref| <= (K_i + K_h + 8) 2^-23 A.
   3. cell       saved f32 c_t, c_seq, hidden_seq from the saved gates and the saved c_{t-1}; the inference kernel (lstm_hip)
-                returns the same bits; `saved` is compared in full (it cannot be poisoned: the API allocates it).
+                returns the same bits; `saved` is compared in full (the API allocates it: tests/test_gpu_poison.py::test_lstm
+                runs CASES[0..2] with that allocation, and the workspace, pre-filled with 0xFF and 0x7F bytes).
   4. exact      rho = -200 (sigma = 0 exactly), small integers: the gates are integers and equal float64; drho == 0.
   5. backward   dx, dh0, dc0 and the eight parameter gradients against float64 BPTT from the saved buffers; the bound is the
                 propagated first-order error (envelope.Err), nothing fitted.
