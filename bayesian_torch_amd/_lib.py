@@ -15,6 +15,10 @@ FLAG_REVERSE = 256
 E_UNSUPPORTED = -3
 STREAM_EPS_W, STREAM_EPS_B, STREAM_SIGN_IN, STREAM_SIGN_OUT, STREAM_OUT_NOISE = 0, 1, 2, 3, 4
 STREAM_KL_W, STREAM_KL_B = 5, 6   # BTX-KLMC v1: the sampled KL's own draws (draw j: stream | j << 8)
+STREAM_DROP = 7                   # BTX-DROP v1 (include/btx_drop.h): the keep bits of the dropout layers
+DROP_ELEMENT, DROP_CHANNEL = 0, 1
+DROP_CL, DROP_NCS = 0, 1
+DROP_CHUNK, DROP_MAX_ELEMENTS = 8192, 1 << 35
 PRIOR_GAUSS_MIX2, PRIOR_LAPLACE, PRIOR_STUDENT_T = 1, 2, 3
 # BTX-SVD v1: reduction codes, the log-alpha clamp, the rho of a pruned weight, the layout of the statistics words
 REDUCE_MEAN, REDUCE_SUM = 0, 1
@@ -175,6 +179,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_lrt_fwd_train", "btx_lrt_bwd_workspace_bytes", "btx_lrt_bwd",
            "btx_kl_mc_workspace_bytes", "btx_kl_mc_model", "btx_kl_mc_model_bwd",
            "btx_kl_logu_workspace_bytes", "btx_kl_logu_model", "btx_kl_logu_model_bwd", "btx_logalpha_stats", "btx_logalpha_prune")
+# include/btx_drop.h: entry points added to ABI 9 in a header of their own (EXPORTS stays what include/btx.h declares)
+EXPORTS_DROP = ("btx_dropout_fwd", "btx_dropout_bwd")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -391,6 +397,10 @@ def lib():
     L.btx_logalpha_stats.argtypes = [ctypes.POINTER(LogAlphaItem), i32, ctypes.POINTER(ctypes.c_float), i32, i32, vp, vp, vp]
     L.btx_logalpha_prune.restype = i32
     L.btx_logalpha_prune.argtypes = [ctypes.POINTER(LogAlphaItem), i32, ctypes.c_float, vp, vp]
+    L.btx_dropout_fwd.restype = i32
+    L.btx_dropout_fwd.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, u32, f32, i32, i64, ctypes.POINTER(Rng), vp]
+    L.btx_dropout_bwd.restype = i32
+    L.btx_dropout_bwd.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, u32, f32, ctypes.POINTER(Rng), vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -268,6 +268,23 @@ class LrtFn(torch.autograd.Function):
                 drho_b if need[6] else None)
 
 
+class DropoutFn(torch.autograd.Function):
+    """y = MCDropout(x) on the HIP backend (BTX-DROP v1, btx_drop.hip).  Nothing is saved: the backward is the same launch on dy, its
+    mask regenerated from (seed, layer id) and the sample index — or the device sample word — the forward read."""
+
+    @staticmethod
+    def forward(ctx, layer, sample_idx, x):
+        # the device word THIS forward read (num_mc > 1 points the layer at another word before the next pass), as ContractFn keeps it
+        sdev = layer.__dict__.get("_btx_sample_dev")
+        ctx.meta = (layer._btx_T, layer._btx_scale, layer.mode, _rng.seed(), sample_idx, layer._btx_layer_id, sdev)
+        return BF.dropout_hip(x, *ctx.meta[:6], sample_dev=sdev)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        return None, None, BF.dropout_hip(dy, *ctx.meta[:6], sample_dev=ctx.meta[6], backward=True)
+
+
 class KlFn(torch.autograd.Function):
     """sum of the per-tensor mean KLs of `n` (mu, rho) pairs on the HIP backend, with gradients"""
 

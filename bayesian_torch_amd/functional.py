@@ -1411,3 +1411,182 @@ def avgpool_global_hip(x):
     _lib.check(L.btx_avgpool_global_cl(xp.data_ptr(), out.data_ptr(), _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32,
                                        n, h * w, c, torch.cuda.current_stream(x.device).cuda_stream))
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# Monte-Carlo dropout — BTX-DROP v1 (csrc/btx_drop.hip, include/btx_drop.h)
+# --------------------------------------------------------------------------------------------------------------------
+DROP_MODES = {"element": _lib.DROP_ELEMENT, "channel": _lib.DROP_CHANNEL}
+
+
+def dropout_params(p):
+    """(T, scale) of BTX-DROP v1 for the drop probability `p`: T = clamp(floor((1 - p) * 65536 + 0.5), 0, 65536) in double — an
+    element is kept iff its sixteen random bits are below T, so the effective keep probability is T / 65536 — and scale =
+    f32(65536.0 / T), divided in double and rounded once (0.0 when T = 0)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(p))
+    T = min(65536, max(0, int(math.floor((1.0 - p) * 65536.0 + 0.5))))
+    scale = float(torch.tensor(65536.0 / T, dtype=torch.float64).to(torch.float32)) if T else 0.0
+    return T, scale
+
+
+def _drop_geom(shape, mode):
+    """(N, C, S, logical) of a lane-stacked tensor of `shape`: the examples x channels x spatial positions BTX-DROP v1 indexes.
+    Element mode reads tensors of rank <= 3 as plain row-major ([B, F], [B, T, F]: S = 1); channel mode needs rank >= 3."""
+    shape = tuple(int(v) for v in shape)
+    if mode not in DROP_MODES:
+        raise ValueError("dropout mode must be 'element' or 'channel' (got %r)" % (mode,))
+    if mode == "channel" and len(shape) < 3:
+        raise _lib.BtxError("channel dropout (MCDropout1d/2d/3d) needs an input of rank >= 3, got shape %r" % (shape,))
+    if len(shape) == 0:
+        return 1, 1, 1
+    if mode == "channel" or len(shape) >= 4:
+        return shape[0], shape[1], math.prod(shape[2:])
+    return shape[0], math.prod(shape[1:]), 1
+
+
+def _mulhilo32(a, m):
+    """(high, low) 32-bit words of a * m for an int64 tensor a in [0, 2^32) and a Python constant m < 2^32, in 16-bit halves: no
+    intermediate leaves [0, 2^34)"""
+    m_lo, m_hi = m & 0xFFFF, m >> 16
+    a_lo, a_hi = a & 0xFFFF, a >> 16
+    p00 = a_lo * m_lo
+    mid = a_lo * m_hi + a_hi * m_lo + (p00 >> 16)
+    return a_hi * m_hi + (mid >> 16), ((mid & 0xFFFF) << 16) | (p00 & 0xFFFF)
+
+
+def philox4x32_10_aten(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (csrc/btx_rng.h) on int64 tensors / Python ints holding 32-bit words; returns the four output words"""
+    M0, M1, W0, W1, MASK = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
+    c0 = torch.as_tensor(c0, dtype=torch.int64)
+    c1, c2, c3 = (torch.as_tensor(v, dtype=torch.int64, device=c0.device) for v in (c1, c2, c3))
+    k0, k1 = int(k0) & MASK, int(k1) & MASK
+    for _ in range(10):
+        h0, l0 = _mulhilo32(c0, M0)
+        h1, l1 = _mulhilo32(c2, M1)
+        c0, c1, c2, c3 = h1 ^ c1 ^ k0, l1, h0 ^ c3 ^ k1, l0
+        k0, k1 = (k0 + W0) & MASK, (k1 + W1) & MASK
+    return c0, c1, c2, c3
+
+
+def dropout_index_aten(shape, mode, device="cpu"):
+    """the BTX-DROP v1 element index of every LOGICAL element of one lane's tensor of `shape` (int64, in the logical shape): the
+    position in channels-last order [n][spatial...][c] (rank <= 3: plain row-major), or n * C + c in channel mode"""
+    shape = tuple(int(v) for v in shape)
+    N, C, S = _drop_geom(shape, mode)
+    if mode == "channel":
+        return torch.arange(N * C, dtype=torch.int64, device=device).reshape((N, C) + (1,) * (len(shape) - 2)).expand(shape)
+    if len(shape) < 4:
+        return torch.arange(N * C * S, dtype=torch.int64, device=device).reshape(shape)
+    nd = len(shape) - 2
+    return torch.arange(N * C * S, dtype=torch.int64, device=device).reshape((N,) + shape[2:] + (C,)).permute(
+        (0, nd + 1) + tuple(range(1, nd + 1)))
+
+
+def dropout_mask_aten(shape, T, mode, seed, sample_idx, layer_id, device="cpu"):
+    """The bool KEEP mask of BTX-DROP v1 for one lane's logical tensor of `shape` from torch integer ops: the same bits as
+    btx_dropout_fwd draws, on any device (CPU tensors, backend "torch", dtypes other than f32 / bf16 — and the tests)."""
+    i = dropout_index_aten(shape, mode, device)
+    if i.numel() > _lib.DROP_MAX_ELEMENTS:
+        raise _lib.BtxError("dropout: a lane tensor of more than 2^35 elements")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    P = philox4x32_10_aten(i >> 3, int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF, _lib.STREAM_DROP,
+                           seed & 0xFFFFFFFF, seed >> 32)
+    w = (i >> 1) & 3
+    word = torch.where(w == 0, P[0], torch.where(w == 1, P[1], torch.where(w == 2, P[2], P[3])))
+    h = (word >> (16 * (i & 1))) & 0xFFFF
+    return h < int(T)
+
+
+def dropout_apply_aten(x, mask, scale):
+    """kept: x * scale as ONE f32 multiply rounded once to x's dtype (float64 tensors multiply in float64); dropped: +0.0 by
+    selection, so a dropped inf / NaN gives 0.  Differentiable: the gradient is where(mask, dy * scale, 0)."""
+    if x.dtype == torch.float64:
+        kept = x * float(scale)
+    else:
+        kept = (x.float() * float(scale)).to(x.dtype)
+    return torch.where(mask, kept, torch.zeros((), dtype=x.dtype, device=x.device))
+
+
+def _drop_lane_rows(x, lanes, lane_batch):
+    rows = int(x.shape[0]) if x.dim() else 1
+    if lanes <= 1:
+        return rows, False
+    if lane_batch is None or rows not in (int(lane_batch), lanes * int(lane_batch)):
+        raise _lib.BtxError("dropout with %d MC sample lanes of %r rows: the input has %d rows (expected the shared input of %r rows, "
+                            "or %d lanes back to back)" % (lanes, lane_batch, rows, lane_batch, lanes))
+    return int(lane_batch), rows == int(lane_batch)
+
+
+def dropout_aten(x, T, scale, mode, seed, sample_idx, layer_id, sample_dev=None, lanes=1, lane_batch=None):
+    """BTX-DROP v1 from torch ops (any device, any floating dtype): the masks of dropout_hip, bit for bit.  A device sample word is
+    read on the host here (this route is not capturable)."""
+    B, shared = _drop_lane_rows(x, lanes, lane_batch)
+    if sample_dev is not None:
+        idx = [int(v) for v in sample_dev.reshape(-1)[:max(1, lanes)].tolist()]
+    else:
+        idx = [int(sample_idx) + l for l in range(max(1, lanes))]
+    if lanes <= 1:
+        return dropout_apply_aten(x, dropout_mask_aten(tuple(x.shape), T, mode, seed, idx[0], layer_id, x.device), scale)
+    outs = []
+    for l in range(lanes):
+        xl = x if shared else x[l * B:(l + 1) * B]
+        outs.append(dropout_apply_aten(xl, dropout_mask_aten(tuple(xl.shape), T, mode, seed, idx[l], layer_id, x.device), scale))
+    return torch.cat(outs, 0)
+
+
+def _drop_layout(x, N, C, S):
+    """(tensor to read, layout code): channels-last and plain contiguous memory run as they are; anything else is made contiguous"""
+    if S == 1 or C == 1 or x.dim() < 3:
+        return (x if x.is_contiguous() else x.contiguous()), _lib.DROP_CL
+    if x.is_contiguous():
+        return x, _lib.DROP_NCS
+    nd = x.dim() - 2
+    if x.permute((0,) + tuple(range(2, nd + 2)) + (1,)).is_contiguous():
+        return x, _lib.DROP_CL
+    return x.contiguous(), _lib.DROP_NCS
+
+
+def dropout_hip(x, T, scale, mode, seed, sample_idx, layer_id, sample_dev=None, lanes=1, lane_batch=None, out=None, backward=False):
+    """btx_dropout_fwd on a CUDA tensor (f32 / bf16): out = drop(x) under the mask of BTX-DROP v1 at (seed, sample index, layer id) —
+    the backward is the same call on dy.  The mask belongs to the LOGICAL element: NCHW-contiguous and channels-last memory draw
+    the same one, and the output keeps the input's memory format.  sample_dev: the device word(s) the kernel reads instead of
+    sample_idx (captured steps; one int32 per lane).  lanes = L > 1 with lane_batch = B: x holds L tensors of B rows back to back,
+    or the B shared rows every lane reads (broadcast: the output has L * B rows).  out: x itself for an in-place call.  backward=True:
+    x is dy and the call is btx_dropout_bwd (one lane: lanes are an inference feature)."""
+    L = _lib.lib()
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.BtxError("dropout_hip: f32 and bf16 activations only (got %s)" % x.dtype)
+    lanes = max(1, int(lanes))
+    B, shared = _drop_lane_rows(x, lanes, lane_batch)
+    lane_shape = ((B,) + tuple(x.shape[1:])) if x.dim() else ()
+    N, C, S = _drop_geom(lane_shape, mode)
+    if N * C * S > _lib.DROP_MAX_ELEMENTS:
+        raise _lib.BtxError("dropout: a lane tensor of more than 2^35 elements")
+    xr, layout = _drop_layout(x, N, C, S)
+    if shared and lanes > 1:
+        oshape = (lanes * B,) + tuple(x.shape[1:])
+        if layout == _lib.DROP_CL and x.dim() >= 3 and not (S == 1 or C == 1):
+            nd = x.dim() - 2
+            out = torch.empty((lanes * B,) + tuple(x.shape[2:]) + (x.shape[1],), dtype=x.dtype, device=x.device).permute(
+                (0, nd + 1) + tuple(range(1, nd + 1)))
+        else:
+            out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+    elif out is None:
+        out = torch.empty_like(xr)  # preserve_format: the memory order of xr (dense)
+    if x.numel() == 0:
+        return out
+    r = _lib.Rng(int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
+                 sample_dev.data_ptr() if sample_dev is not None else None)
+    act = _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    if backward:
+        if lanes > 1:
+            raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
+        _lib.check(L.btx_dropout_bwd(xr.data_ptr(), out.data_ptr(), act, N, C, S, DROP_MODES[mode], layout, int(T), float(scale),
+                                     ctypes.byref(r), stream))
+        return out
+    _lib.check(L.btx_dropout_fwd(xr.data_ptr(), out.data_ptr(), act, N, C, S, DROP_MODES[mode], layout, int(T), float(scale),
+                                 lanes, B if (shared and lanes > 1) else lanes * B, ctypes.byref(r), stream))
+    return out

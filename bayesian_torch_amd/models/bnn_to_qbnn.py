@@ -94,6 +94,11 @@ def _foldable(conv, bn, flipout=False):
 
 
 def bnn_to_qbnn(m, fuse_conv_bn=False, flipout=False):
+    for name, sub in m.named_modules():  # before anything is converted: the model stays as it was
+        if getattr(sub, "_btx_dropout", False):
+            from .._lib import BtxError
+            raise BtxError("bnn_to_qbnn: %r is a %s; Monte-Carlo dropout has no INT8 twin (BTX-DROP v1 defines f32 and bf16)"
+                           % (name, type(sub).__name__))
     mods = m._modules
     if fuse_conv_bn:
         for c, b in (("conv1", "bn1"), ("conv2", "bn2"), ("conv3", "bn3")):

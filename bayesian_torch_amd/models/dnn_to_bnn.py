@@ -120,9 +120,12 @@ def get_kl_loss(m):
     layers = [layer for layer in m.modules() if hasattr(layer, "kl_loss")]
     if not layers:
         return None
-    if all(hasattr(layer, "_w") and layer._use_hip(layer._w()[0]) for layer in layers):
+    # MCDropout layers (no parameters, kl_loss() == 0) do not take a mixed model off the one-launch path: the sum runs over the
+    # layers that have a KL; a model whose only layers with a kl_loss are MCDropout sums its zeros below
+    var = [layer for layer in layers if not getattr(layer, "_btx_dropout", False)]
+    if var and all(hasattr(layer, "_w") and layer._use_hip(layer._w()[0]) for layer in var):
         from .. import autograd as _ag
-        return _ag.kl_of_layers(layers)
+        return _ag.kl_of_layers(var)
     terms = [layer.kl_loss() for layer in layers]
     if len(terms) == 1:
         return terms[0]

@@ -539,7 +539,8 @@ class _Tracer(torch.fx.Tracer):
     """variational layers and torch.nn modules (not containers) are leaves: their calls stay single nodes"""
 
     def is_leaf_module(self, m, qualname):
-        return _is_var(m) or _is_lstm(m) or _is_q8(m) or super().is_leaf_module(m, qualname)
+        # (an MCDropout is a leaf and no epilogue site: it stays where it is and nothing is folded across it)
+        return _is_var(m) or _is_lstm(m) or _is_q8(m) or getattr(m, "_btx_dropout", False) or super().is_leaf_module(m, qualname)
 
 
 def _inlined(module):

@@ -68,7 +68,7 @@ def set_sample_index(model, idx, presample=False):
         _presample(model, idx)
 
 
-def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=None):
+def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=None, device=None):
     """MC sample lanes: the NEXT forward of every variational layer of `model` evaluates len(indices) Monte-Carlo samples
     in one launch per layer (btx_contract_fwd_lanes).  Feed the model its input ONCE (`batch` images: the first layers
     read it for every lane) — every activation behind the first variational layer, and the model's output, hold the
@@ -78,7 +78,8 @@ def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=Non
     the f32 summation order of small-map layers can differ by rounding.  `indices=None` (or one index) returns to plain
     forwards.
     GPU-only; the indices live in a device tensor (`sample_dev`: an int32 tensor to (re)use — mc.GraphedMC keeps one
-    per graph and rewrites it between replays)."""
+    per graph and rewrites it between replays).  `device`: where to put them for a model whose stochastic layers have no
+    parameters (MCDropout only) and which has none elsewhere either."""
     import torch
     layers = [m for m in model.modules() if hasattr(m, "_btx_layer_id")]
     if indices is None or len(indices) <= 1:
@@ -96,7 +97,15 @@ def set_sample_lanes(model, indices, batch=None, presample=False, sample_dev=Non
     if batch is None:
         raise ValueError("set_sample_lanes needs the number of images per lane (batch)")
     n = len(indices)
-    dev = next(layers[0].parameters()).device
+    # where the sample words live: with the first layer that has parameters; a model whose only stochastic layers are MCDropout
+    # (no parameters) says so through `sample_dev` or `device`, else through the parameters of the model itself
+    dev = next((p.device for m in layers for p in m.parameters()), None)
+    if dev is None:
+        dev = sample_dev.device if sample_dev is not None else device
+    if dev is None:
+        dev = next((p.device for p in model.parameters()), None)
+    if dev is None:
+        raise ValueError("set_sample_lanes: no stochastic layer of the model has parameters; pass device= (or sample_dev=)")
     if sample_dev is None:
         sample_dev = torch.zeros(n, dtype=torch.int32, device=dev)
     if sample_dev.numel() != n or sample_dev.dtype != torch.int32:

@@ -116,6 +116,7 @@ extern "C" {
 #define BTX_STREAM_SIGN_IN  2u
 #define BTX_STREAM_SIGN_OUT 3u
 #define BTX_STREAM_OUT_NOISE 4u /* BTX_KIND_LRT: the per-output-element normal zeta */
+#define BTX_STREAM_DROP 7u      /* BTX-DROP v1: the keep bits of the dropout layers (include/btx_drop.h) */
 
 /* Geometry of one variational contraction.  Linear is the 1x1x1 case: NB=batch, D=H=W=1, C=in_features,
  * KD=KH=KW=1, N=out_features.  Conv1d uses H only... by convention lower-rank convs put their axes last
