@@ -20,12 +20,30 @@ device sample words, one per pass).  A layer's backward regenerates the noise of
 on different words can share one backward.  The loss head of the stack is utils.mc_loss (csrc/btx_mcloss.hip).
 """
 import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from . import functional as BF
 from . import rng as _rng
+
+
+def _first_order(backward):
+    """Every backward here runs its kernels on detached tensors: a second derivative through it would be a constant.
+    torch's once_differentiable turns that into an error only when the incoming gradient itself requires one; a gradient penalty
+    (`torch.autograd.grad(out.sum(), x, create_graph=True)`) hands in a plain tensor and would get constants back without a word.  So the
+    refusal is made here: a backward that autograd runs in grad mode (create_graph=True) raises."""
+    inner = torch.autograd.function.once_differentiable(backward)
+
+    @functools.wraps(backward)
+    def guarded(ctx, *grads):
+        if torch.is_grad_enabled():
+            raise RuntimeError("bayesian_torch_amd: %s is first-order only (once_differentiable): its backward runs HIP kernels on "
+                               "detached tensors, so create_graph=True would differentiate constants; use create_graph=False, or "
+                               "backend 'torch' for second-order terms" % type(ctx).__name__)
+        return inner(ctx, *grads)
+    return guarded
 
 
 def fast_dgrad_ok(layer):
@@ -43,9 +61,11 @@ def fast_dgrad_ok(layer):
     return False
 
 
-def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho, sdev=None):
+def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho, sdev=None, seed=None):
     """dx through libbtx: the contraction of dy with the (mu, sigma*eps) the FORWARD used (the tensors autograd saved) on
-    the transposed geometry.  sdev: the device sample word the forward read (None: the host index `sample_idx`)"""
+    the transposed geometry.  sdev: the device sample word the forward read (None: the host index `sample_idx`); seed: the
+    BTX-RNG seed the forward ran under (None: the current one)"""
+    seed = _rng.seed() if seed is None else seed
     op = layer._op
     kind = _lib.KIND_FLIPOUT if layer._family == "flipout" else _lib.KIND_REPARAM
     nd = op.nd
@@ -64,9 +84,9 @@ def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho, sd
             opT = BF.OpDesc(2, op.out_channels, op.in_channels, op.kernel[1:], op.stride[1:], op.padding[1:], op.dilation[1:], 1,
                             transposed=True, output_padding=outpad)
             taps, flip = op.kernel[1] * op.kernel[2], False
-        w_mu, w_rho, w_eps = BF.dgrad_weights_hip(mu_p, rho_p, op.out_channels, taps, op.in_channels, flip, _rng.seed(),
+        w_mu, w_rho, w_eps = BF.dgrad_weights_hip(mu_p, rho_p, op.out_channels, taps, op.in_channels, flip, seed,
                                                   sample_idx, layer._btx_layer_id, sample_dev=sdev)
-        dx = BF.contract_hip(kind, dy, w_mu, w_rho, None, None, opT, _rng.seed(), sample_idx, layer._btx_layer_id,
+        dx = BF.contract_hip(kind, dy, w_mu, w_rho, None, None, opT, seed, sample_idx, layer._btx_layer_id,
                              prec=layer.precision, noise={"eps_w_packed": w_eps}, sample_dev=sdev,
                              extra_flags=_lib.FLAG_SWAP_SIGNS if kind == _lib.KIND_FLIPOUT else 0)
         return dx.reshape(x_shape) if nd == 0 else dx
@@ -101,7 +121,7 @@ def _data_grad_hip(layer, dy, x_shape, nz, sample_idx, hashed_signs, mu, rho, sd
         else:  # padded forward layouts (C % 8 != 0, row-fused stems): the signs as tensors
             noise["sign_in"], noise["sign_out"] = nz["sign_out"], nz["sign_in"]
     dx = BF.contract_hip(kind, dy, BF.pack_gemm_major(w_mu.float(), opT), BF.pack_gemm_major(w_rho.float(), opT), None, None,
-                         opT, _rng.seed(), sample_idx, layer._btx_layer_id, prec=layer.precision, noise=noise,
+                         opT, seed, sample_idx, layer._btx_layer_id, prec=layer.precision, noise=noise,
                          extra_flags=flags, sample_dev=sdev)
     return dx.reshape(x_shape) if nd == 0 else dx
 
@@ -113,7 +133,8 @@ class ContractFn(torch.autograd.Function):
     def forward(ctx, layer, sample_idx, x, mu, rho, mu_b, rho_b):
         with torch.no_grad():
             out = layer._forward_hip(x, sample_idx=sample_idx)
-        ctx.layer, ctx.sample_idx = layer, sample_idx
+        # the seed THIS forward ran under: bt.manual_seed() between forward and backward must not change the noise the backward regenerates
+        ctx.layer, ctx.sample_idx, ctx.seed = layer, sample_idx, _rng.seed()
         # the device sample word THIS forward read: a step with several MC passes (num_mc > 1) points the layer at another word
         # before the next pass, and the backward must regenerate this pass's noise, not the last one's
         ctx.sample_dev = getattr(layer, "_btx_sample_dev", None)
@@ -121,8 +142,9 @@ class ContractFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    @_first_order
     def backward(ctx, dy):
-        layer, s = ctx.layer, ctx.sample_idx
+        layer, s, seed = ctx.layer, ctx.sample_idx, ctx.seed
         x, mu_s, rho, rho_b = ctx.saved_tensors
         op = layer._op
         flip = layer._family == "flipout"
@@ -144,8 +166,8 @@ class ContractFn(torch.autograd.Function):
             need_nz = ((ctx.needs_input_grad[2] and not fast_dx) or not plain_w or need_signs or
                        (rho_b is not None and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6])))
             sdev = ctx.sample_dev  # captured step: eps / signs follow the device word the forward read, not `s`
-            nz = layer.materialize_noise(s, tuple(x.shape), tuple(dy.shape), x.dtype, signs=need_signs,
-                                         sample_dev=sdev) if need_nz else {}
+            nz = layer.materialize_noise(s, tuple(x.shape), tuple(dy.shape), x.dtype, signs=need_signs, sample_dev=sdev,
+                                         seed=seed) if need_nz else {}   # under the forward's seed, not the process-wide one of NOW
             dx = dmu = drho = dmu_b = drho_b = None
             kind = _lib.KIND_FLIPOUT if flip else _lib.KIND_REPARAM
             want_w = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
@@ -155,7 +177,7 @@ class ContractFn(torch.autograd.Function):
                 if plan is not None and not op.transposed:
                     # row-fused stem: the gradient on the geometry the forward ran on (7 kernel rows x 32 elements instead of
                     # 49 taps x 3 channels of a 64-wide tile; the forward's hashed signs instead of sign tensors)
-                    dW, dWd, db, dbd = BF.wgrad_hip(kind, x, dy, op, _rng.seed(), s, layer._btx_layer_id, w_shape,
+                    dW, dWd, db, dbd = BF.wgrad_hip(kind, x, dy, op, seed, s, layer._btx_layer_id, w_shape,
                                                     bias=want_b, rowfuse=plan, sample_dev=sdev)
                 elif not op.transposed and not padded:
                     # plain layouts: the kernel's GEMM-major buffers ARE the gradients (strided logical views, as the
@@ -164,7 +186,7 @@ class ContractFn(torch.autograd.Function):
                     rho_f = BF.gemm_major_view(rho, op).reshape(-1) if want_w else None
                     if rho_f is not None and not rho_f.is_contiguous():
                         rho_f = rho_f.contiguous()
-                    res = BF.wgrad_hip(kind, x, dy, op, _rng.seed(), s, layer._btx_layer_id, w_shape, bias=want_b, raw=True,
+                    res = BF.wgrad_hip(kind, x, dy, op, seed, s, layer._btx_layer_id, w_shape, bias=want_b, raw=True,
                                        sample_dev=sdev, rho_flat=rho_f)
                     dWf, dWdf, db, dbd = res[:4]
                     if want_w:
@@ -173,7 +195,7 @@ class ContractFn(torch.autograd.Function):
                         drho = BF.gemm_major_logical_view(drho_f, w_shape, op)
                     fused_w = True
                 elif not op.transposed:
-                    dW, dWd, db, dbd = BF.wgrad_hip(kind, x, dy, op, _rng.seed(), s, layer._btx_layer_id, w_shape,
+                    dW, dWd, db, dbd = BF.wgrad_hip(kind, x, dy, op, seed, s, layer._btx_layer_id, w_shape,
                                                     signs=signs, bias=want_b, sample_dev=sdev)
                 else:
                     # y = convT(x, W): W is the weight of the plain convolution that maps y-space to x-space, so its
@@ -182,7 +204,7 @@ class ContractFn(torch.autograd.Function):
                     opc = BF.OpDesc(nd, op.out_channels, op.in_channels, op.kernel[3 - nd:], op.stride[3 - nd:],
                                     op.padding[3 - nd:], op.dilation[3 - nd:], op.groups)
                     sw = (signs[1], signs[0]) if signs is not None else None
-                    dW, dWd, _, _ = BF.wgrad_hip(kind, dy, x, opc, _rng.seed(), s, layer._btx_layer_id, w_shape, signs=sw,
+                    dW, dWd, _, _ = BF.wgrad_hip(kind, dy, x, opc, seed, s, layer._btx_layer_id, w_shape, signs=sw,
                                                  swap=True, sample_dev=sdev)
                     db = dbd = None
                     if want_b:
@@ -197,7 +219,7 @@ class ContractFn(torch.autograd.Function):
                     drho_b = (dbd if flip else db) * nz["eps_b"] * torch.sigmoid(rho_b.detach())
             if ctx.needs_input_grad[2]:
                 hashed = flip and not padded
-                dx = _data_grad_hip(layer, dy, tuple(x.shape), nz, s, hashed, mu_s, rho, sdev)
+                dx = _data_grad_hip(layer, dy, tuple(x.shape), nz, s, hashed, mu_s, rho, sdev, seed)
                 if dx.dtype != x.dtype:
                     dx = dx.to(x.dtype)
         return None, None, dx, dmu, drho, dmu_b, drho_b
@@ -223,15 +245,17 @@ class LrtFn(torch.autograd.Function):
                 op = layer._op_pad
             layer.__dict__["_btx_last_xshape"] = tuple(x.shape)
             sdev = getattr(layer, "_btx_sample_dev", None)
+            seed = _rng.seed()  # kept on ctx: the backward regenerates zeta under the seed THIS forward ran under
             out, root = BF.lrt_fwd_train_hip(xin, mu_p, rho_p, mu_b.detach() if mu_b is not None else None,
-                                             rho_b.detach() if rho_b is not None else None, op, _rng.seed(), sample_idx,
+                                             rho_b.detach() if rho_b is not None else None, op, seed, sample_idx,
                                              layer._btx_layer_id, prec=layer.precision, sample_dev=sdev)
+        ctx.seed = seed
         ctx.layer, ctx.sample_idx, ctx.sample_dev = layer, sample_idx, sdev  # the device word THIS forward read (num_mc > 1)
         ctx.save_for_backward(x, root, mu, rho, rho_b)
         return out
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_first_order
     def backward(ctx, dy):
         layer, s = ctx.layer, ctx.sample_idx
         x, root, mu, rho, rho_b = ctx.saved_tensors
@@ -249,7 +273,7 @@ class LrtFn(torch.autograd.Function):
             want_w = need[3] or need[4]
             want_b = rho_b is not None and (need[5] or need[6])
             dx, dmu_f, drho_f, dmu_b, drho_b = BF.lrt_bwd_hip(xin, dy, root, mu_p, rho_p,
-                                                              rho_b.detach() if rho_b is not None else None, op, _rng.seed(), s,
+                                                              rho_b.detach() if rho_b is not None else None, op, ctx.seed, s,
                                                               layer._btx_layer_id, prec=layer.precision, sample_dev=ctx.sample_dev,
                                                               want_x=need[2], want_w=want_w, want_b=want_b)
             dmu = drho = None
@@ -280,7 +304,7 @@ class DropoutFn(torch.autograd.Function):
         return BF.dropout_hip(x, *ctx.meta[:6], sample_dev=sdev)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
+    @_first_order
     def backward(ctx, dy):
         return None, None, BF.dropout_hip(dy, *ctx.meta[:6], sample_dev=ctx.meta[6], backward=True)
 
@@ -296,6 +320,7 @@ class KlFn(torch.autograd.Function):
         return BF.kl_model_hip(_entries(meta, params))
 
     @staticmethod
+    @_first_order
     def backward(ctx, g):
         params = ctx.saved_tensors
         meta = ctx.meta
@@ -347,6 +372,7 @@ class LstmTrainFn(torch.autograd.Function):
         return hs, cs, kl
 
     @staticmethod
+    @_first_order
     def backward(ctx, d_hs, d_cs, d_kl):
         kind, seed, prec, mi, mh = ctx.meta
         x, h0, c0, mu_i, rho_i, mub_i, rhob_i, mu_h, rho_h, mub_h, rhob_h, hs = ctx.saved_tensors
@@ -406,6 +432,7 @@ class KlMcFn(torch.autograd.Function):
         return BF.kl_mc_model_hip(_mc_entries(meta, params), seed, draws)
 
     @staticmethod
+    @_first_order
     def backward(ctx, g):
         params, meta = ctx.saved_tensors, ctx.meta
         entries = _mc_entries(meta, params)
@@ -482,6 +509,7 @@ class KlLogUFn(torch.autograd.Function):
         return BF.kl_logu_model_hip(_logu_entries(meta, params))
 
     @staticmethod
+    @_first_order
     def backward(ctx, g):
         params, meta = ctx.saved_tensors, ctx.meta
         entries = _logu_entries(meta, params)
@@ -630,7 +658,7 @@ class BatchNormTrainFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    @torch.autograd.function.once_differentiable  # first-order only: create_graph=True raises instead of returning constants
+    @_first_order
     def backward(ctx, dy):
         L = _lib.lib()
         x, w, save_mean, save_invstd, mask = ctx.saved_tensors
@@ -724,7 +752,7 @@ class MaxPool2dTrainFn(torch.autograd.Function):
         return y
 
     @staticmethod
-    @torch.autograd.function.once_differentiable  # first-order only: create_graph=True raises instead of returning constants
+    @_first_order
     def backward(ctx, dy):
         (idx,) = ctx.saved_tensors
         shape, k, s_, p_ = ctx.geom

@@ -210,6 +210,7 @@ class _VariationalNd(BaseVariationalLayer_):
         mu, rho = self._w()
         return torch.is_grad_enabled() and (mu.requires_grad or rho.requires_grad or
                                             (self.mu_bias is not None and self.mu_bias.requires_grad) or
+                                            (self.rho_bias is not None and self.rho_bias.requires_grad) or
                                             (t is not None and t.is_floating_point() and t.requires_grad))
 
     # ---- non-Gaussian priors (BTX-KLMC v1) ------------------------------------------------------------------
@@ -415,14 +416,15 @@ class _VariationalNd(BaseVariationalLayer_):
         out = m + self._lrt_root(v) * zeta_of(m)
         return (out if out.dtype == x.dtype else out.to(x.dtype)), kl
 
-    def _lrt_zeta_hip(self, shape, device, sample_idx, sample_dev=None):
+    def _lrt_zeta_hip(self, shape, device, sample_idx, sample_dev=None, seed=None):
         """the zeta of MC sample `sample_idx` (or of the device word `sample_dev`) for an output of logical shape `shape`: stream
         BTX_STREAM_OUT_NOISE at the element's index in the channels-last tensor the kernel writes — what the kind-2 launch draws"""
         shape = tuple(shape)
         n = 1
         for d in shape:
             n *= int(d)
-        flat = BF.fill_eps_hip(n, device, _rng.seed(), sample_idx, self._btx_layer_id, _lib.STREAM_OUT_NOISE, sample_dev=sample_dev)
+        flat = BF.fill_eps_hip(n, device, _rng.seed() if seed is None else seed, sample_idx, self._btx_layer_id, _lib.STREAM_OUT_NOISE,
+                               sample_dev=sample_dev)
         nd = self._op.nd
         if nd == 0:
             return flat.reshape(shape)
@@ -678,18 +680,19 @@ class _VariationalNd(BaseVariationalLayer_):
             cache[key] = BF.rowfuse_plan(self._op, key)
         return cache[key]
 
-    def materialize_noise(self, sample_idx, x_shape=None, out_shape=None, x_dtype=None, signs=True, sample_dev=None):
+    def materialize_noise(self, sample_idx, x_shape=None, out_shape=None, x_dtype=None, signs=True, sample_dev=None, seed=None):
         """The noise BTX-RNG v1 defines for MC sample `sample_idx` of this layer, in the reference's logical
         layouts: dict(eps_w, eps_b[, sign_in, sign_out]).  Also refreshes the eps_* buffers (the reference's
         observable side effect, conv_variational.py:362).  signs=False: skip the Flipout sign tensors (the backward
-        regenerates the hashed signs inside its kernels and only needs eps)."""
+        regenerates the hashed signs inside its kernels and only needs eps).  seed: the BTX-RNG seed to draw under (None: the
+        process-wide one; a backward passes the seed its forward ran under)."""
         mu, _ = self._w()
-        op, seed, lid = self._op, _rng.seed(), self._btx_layer_id
+        op, seed, lid = self._op, (_rng.seed() if seed is None else int(seed)), self._btx_layer_id
         cin, cpad = op.in_channels, self._btx_cpad
         if self._family == "lrt":  # the one draw of the family: dict(zeta) in the logical layout of the output
             if out_shape is None:
                 raise _lib.BtxError("materialize_noise of a LocalReparameterization layer needs out_shape")
-            return {"zeta": self._lrt_zeta_hip(out_shape, mu.device, sample_idx, sample_dev)}
+            return {"zeta": self._lrt_zeta_hip(out_shape, mu.device, sample_idx, sample_dev, seed=seed)}
         # sample_dev (captured training steps): the index lives in a device word; eps follows it, the sign TENSORS (padded
         # layouts only) are keyed on the host and cannot
         if sample_dev is not None and signs and self._family == "flipout" and x_shape is not None:

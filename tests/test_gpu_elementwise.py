@@ -29,6 +29,7 @@ import pytest
 import torch
 
 import envelope as E
+from autograd_cases import dev as _dev, make as _make, Log as _Log, grads64 as _grads64, scaled as _scaled  # moved there, unchanged
 from test_gpu_at_size import CPU_CASES
 from test_gpu_backward import CASES as BWD_CASES, CPU_BWD_CASES, RN18_SHAPES, _op_of
 from test_gpu_backward import test_hip_maxpool_under_autograd_equals_torch as _maxpool_test
@@ -47,22 +48,6 @@ def _params_of(test_fn):
     return [m for m in test_fn.pytestmark if m.name == "parametrize"][0].args[1]
 
 
-def _dev():
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    return torch.device("cuda:0")
-
-
-def _make(cls, kw, prec, seed=3, bt_seed=2024):
-    import bayesian_torch_amd as bt
-    from bayesian_torch_amd import layers as L
-    bt.manual_seed(bt_seed)
-    torch.manual_seed(seed)
-    layer = getattr(L, cls)(**kw).to(_dev())
-    layer.precision = prec
-    bt.assign_layer_ids(layer)  # the noise is keyed on the layer id: alone or inside the whole suite, a case sees the same noise
-    return layer
-
-
 def _refs(layer, x, out_shape, sample):
     """float64 value of the layer for MC sample `sample` on the CPU, with the noise BTX-RNG v1 defines, and its envelope parts:
     (ref, A, A_bias, K)"""
@@ -76,23 +61,6 @@ def _refs(layer, x, out_shape, sample):
     with torch.no_grad():
         ref, A, Ab = E.reference_forward(x, mu, rho, nz["eps_w"], layer.mu_bias, layer.rho_bias, nz.get("eps_b"), si, so, op)
     return ref, A, Ab, E.reduction_length(tuple(mu.shape), op)
-
-
-class _Log:
-    """collects the failures of a loop over cases so that ONE run names every bad element"""
-
-    def __init__(self):
-        self.bad = []
-
-    def check(self, name, prec, got, ref, bnd):
-        rep = E.check(got, ref, bnd)
-        print(rep.line(name, prec))
-        if not rep.ok:
-            self.bad.append("%s %s: %s" % (name, prec, rep))
-        return rep
-
-    def done(self):
-        assert not self.bad, "\n".join(self.bad)
 
 
 def _tag(cls, kw, xshape):
@@ -273,29 +241,6 @@ def test_impulse_data_gradient_reads_back_the_sampled_weights(cls, kw, xshape):
     log.done()
 
 
-def _grads64(layer, x, dy, sample, weights=True):
-    """float64 autograd through the reference chain on the CPU: (dx, dmu, A_dx, ddelta, noise)"""
-    with torch.no_grad():
-        nz = layer.materialize_noise(sample, tuple(x.shape), tuple(dy.shape), x.dtype)
-    mu, rho = layer._w()
-    op = _op_of(layer)
-    flip = layer._family == "flipout"
-    x64 = E.d64(x).requires_grad_(True)
-    mu64 = E.d64(mu).requires_grad_(True)
-    delta64 = (E.sigma64(rho) * E.d64(nz["eps_w"])).requires_grad_(True)
-    if flip:
-        ref = E.contract(x64, mu64, None, op) + E.contract(x64 * E.d64(nz["sign_in"].reshape(x.shape)), delta64, None, op) \
-            * E.d64(nz["sign_out"].reshape(dy.shape))
-    else:
-        ref = E.contract(x64, mu64 + delta64, None, op)
-    if weights:
-        dx, dmu, ddelta = torch.autograd.grad(ref, (x64, mu64, delta64), E.d64(dy))
-    else:
-        (dx,), dmu, ddelta = torch.autograd.grad(ref, (x64,), E.d64(dy)), None, None
-    A = E.dgrad_A(dy, tuple(x.shape), E.abs_weight(mu, rho, nz["eps_w"]), op)
-    return dx, dmu, A, ddelta, nz
-
-
 # =============================================================================================================================
 # 1. envelopes on the cases of the other files
 # =============================================================================================================================
@@ -468,13 +413,6 @@ def test_epilogue_bn_residual_relu_every_element(prec, act):
 
 
 # ---- backward: dx everywhere, dW / db on the small cases ------------------------------------------------------------------
-def _scaled(b_dw, ref_dw, factor):
-    """bound of dW * eps * sigmoid(rho) formed in f32 from a dW with bound b_dw: |factor| scales it, the two products and the
-    hardware sigmoid add relative roundings to the result"""
-    f = E._np(factor)
-    return b_dw * abs(f) + (E.DELTA_W + 4 * E.REF32_UNIT) * (abs(E._np(ref_dw)) + b_dw) * abs(f)
-
-
 @pytest.mark.parametrize("cls,kw,xshape", BWD_CASES, ids=[_tag(*c) for c in BWD_CASES])
 def test_small_case_gradients_every_element(cls, kw, xshape):
     """CASES of test_gpu_backward.py, f32 parity mode: dx, dmu, drho, dmu_b, drho_b element by element against float64 autograd
