@@ -159,6 +159,18 @@ static int contract_fwd_impl(int kind, const BtxGeom* g, const void* x, const fl
       p.fd_rtiles = make_fastdiv((uint32_t)sel.g8_pairs); p.fd_inner = make_fastdiv((uint32_t)(sel.g8_pairs * g->groups));
       rc = launch(launch_contract_gemm8_f32, launch_contract_gemm8_bf16, launch_contract_gemm8_x3);
       break;
+    case BTX_FAMILY_DEPTHWISE: {
+      const DwPlan& dw = sel.dw;
+      const int rw = (dw.TW + DW_R - 1) / DW_R;  // runs of DW_R pixels per tile row
+      p.pt_R = dw.TH; p.pt_Wt = dw.TW; p.pt_Rp = dw.PH; p.pt_Wp = dw.PW; p.pt_PP = dw.PH * dw.PW; p.pt_NI = rw;
+      p.pt_rtiles = dw.rtiles; p.pt_ncs = dw.ctiles; p.ntiles = dw.cblocks; p.pt_lds = dw.lds;
+      p.fd_ptWp = make_fastdiv((uint32_t)dw.PW); p.fd_ptR = make_fastdiv((uint32_t)rw); p.fd_rtiles = make_fastdiv((uint32_t)dw.rtiles);
+      p.fd_ncs = make_fastdiv((uint32_t)dw.ctiles); p.fd_ntiles = make_fastdiv((uint32_t)dw.cblocks);
+      p.fd_inner = make_fastdiv((uint32_t)(g->KH * g->KW));  // noise index -> (channel, tap)
+      p.dw_round = (prec == BTX_PREC_BF16) ? 1 : 0;
+      rc = launch_contract_dw(kind, act_dtype == BTX_ACT_BF16, p, pl.nwg * lanes, st);
+      break;
+    }
     case BTX_FAMILY_DMA:
       rc = launch(launch_contract_dma_f32, launch_contract_dma_bf16, launch_contract_dma_x3);
       break;

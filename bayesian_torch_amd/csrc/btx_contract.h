@@ -161,6 +161,7 @@ struct ContractParams {
   int lane_wt_delta;  // 1 (Flipout): the lanes share the mu tiles at wt, lane l's delta tiles sit at wt_delta_off + l*lane_wt
   int reverse;        // BTX_FLAG_REVERSE: the grid's tiles in descending order
   float* root;        // VAR == 1 (btx_lrt_fwd_train): r = sqrtf(v + sigma_b^2) of every output element, f32, in the layout of `out`
+  int dw_round;       // depthwise family (btx_contract_dw.h): the contraction is bf16 — sampled weights (and f32 activations) rounded once
 };
 
 // the MC sample word of a launch whose index lives in device memory, as a SCALAR load: the word does not change while the
@@ -982,6 +983,7 @@ int launch_contract_gemm8_bf16(int kind, const ContractParams& p, int nwg, hipSt
 int launch_contract_gemm8_f32(int kind, const ContractParams& p, int nwg, hipStream_t st);
 int launch_contract_gemm8_x3(int kind, const ContractParams& p, int nwg, hipStream_t st);
 int launch_presample_batch_x3(const PresampleBatch& b, hipStream_t st);
+int launch_contract_dw(int kind, int act_bf16, const ContractParams& p, int nwg, hipStream_t st);  // btx_contract_dw.h (btx_dw.hip)
 
 template <int PREC>
 static int launch_contract_impl(int kind, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {

@@ -339,6 +339,48 @@ static bool make_stem_pool_plan(const BtxGeom* g, int act_dtype, int prec, const
   return true;
 }
 
+// Depthwise family (btx_contract_dw.h, BTX-DW v1): what it takes (everything else keeps its route) and its tile.  `pl`: make_plan of
+// the request (any bm: only the output extent is read).
+static bool make_dw_plan(int kind, const BtxGeom* g, int act_dtype, uint32_t flags, bool unaligned, const BtxNoise* noise,
+                         const BtxEpilogue* ep, const Plan& pl, DwPlan* dw) {
+  if (kind != BTX_KIND_REPARAM && kind != BTX_KIND_FLIPOUT) return false;
+  if (unaligned || (flags & (BTX_FLAG_GATHER | BTX_FLAG_ROWFUSE)) || (ep && ep->pool)) return false;
+  if (noise && (noise->sign_in || noise->sign_out || noise->sampled_w)) return false;
+  if (g->D != 1 || g->KD != 1 || pl.Do != 1 || g->groups != g->C || g->N != g->C) return false;
+  const int T = g->KH * g->KW;
+  const int esz = (act_dtype == BTX_ACT_BF16) ? 2 : 4, G = 16 / esz, ngc = DW_CB / G, slots = 256 / ngc;
+  if (T > 49 || g->C % G) return false;
+  const long long in_elems = (long long)g->NB * g->H * g->W * g->C;
+  if (in_elems > 0x7fffffffLL || (long long)pl.M * g->N > 0x7fffffffLL || (long long)g->C * T > 0x7fffffffLL) return false;
+  const bool tr = (flags & BTX_FLAG_TRANSPOSED) != 0;
+  // patch extent of `t` output rows / columns: the stencil's footprint, or the input pixels a transposed tile gathers from
+  auto ext = [&](int t, int s, int k, int d) -> long long {
+    return tr ? ((long long)t - 1 + (long long)(k - 1) * d) / s + 2 : (long long)(t - 1) * s + (long long)(k - 1) * d + 1;
+  };
+  const long long fixed = (long long)T * DW_CB * 4 * (kind == BTX_KIND_FLIPOUT ? 2 : 1) + 4 * DW_CB * 4;
+  const long long pixb = DW_CB * esz + (kind == BTX_KIND_FLIPOUT ? ngc : 0);  // a patch pixel and its sign bytes
+  for (int nct = (pl.Wo + 31) / 32; nct <= pl.Wo; ++nct) {
+    const int TW = (pl.Wo + nct - 1) / nct, R = DW_R, rw = (TW + R - 1) / R;
+    const long long PW = ext(TW, g->sw, g->KW, g->dw);
+    int TH = slots * DW_TILE_PIX / (rw * R);
+    if (TH > pl.Ho) TH = pl.Ho;
+    if (TH < 1) TH = 1;
+    while (TH >= 1 && fixed + ext(TH, g->sh, g->KH, g->dh) * PW * pixb > DW_LDS_CAP) --TH;
+    if (TH < 1) continue;  // narrower column tiles
+    const int nrt = (pl.Ho + TH - 1) / TH;
+    TH = (pl.Ho + nrt - 1) / nrt;  // equal row tiles
+    const long long PH = ext(TH, g->sh, g->KH, g->dh);
+    const long long nwg = (long long)g->NB * nrt * nct * ((g->C + DW_CB - 1) / DW_CB);
+    if (nwg > 0x7fffffffLL) return false;
+    dw->TH = TH; dw->TW = TW; dw->PH = (int)PH; dw->PW = (int)PW; dw->rtiles = nrt; dw->ctiles = nct;
+    dw->cblocks = (g->C + DW_CB - 1) / DW_CB;
+    dw->lds = (int)((fixed + PH * PW * pixb + 15) & ~15LL);
+    dw->nwg = (int)nwg;
+    return true;
+  }
+  return false;  // (a dilation so long that one pixel's footprint outgrows the LDS budget)
+}
+
 // workspace of the patch variant: split-K partials (256-byte padded), then the pre-sampled weight tiles
 // Flipout: [mu tiles | delta tiles of lane 0 | lane 1 | ...] — the mu tiles do not depend on the MC sample, one set serves
 // every lane; Reparameterization: [W tiles of lane 0 | lane 1 | ...]
@@ -378,6 +420,20 @@ int select_fwd(int kind, const BtxGeom* g, int act_dtype, int prec, uint32_t fla
     pl.nwg = (int)nwg;
     s->family = gen2 ? BTX_FAMILY_GATHER : BTX_FAMILY_REGSTAGE;
     s->out_bf16 = (act_dtype == BTX_ACT_BF16) ? 1 : 0;
+    s->g8_pairs = 1;
+    s->pt.kg = 1;
+    s->need = 0;
+    return 0;
+  }
+
+  // Depthwise 2-D convolutions (groups == C == N): Cg = 1 fits no MFMA family — the gather kernel would spend a 64-channel MFMA tile
+  // per channel.  They run on the VALU stencil of btx_contract_dw.h: K (= taps) in one piece, weights sampled inside the launch.
+  if (make_dw_plan(kind, g, act_dtype, flags, unaligned, noise, ep, pl, &s->dw)) {
+    pl.ksplits = 1; pl.kper = pl.K; pl.mtiles = s->dw.rtiles * s->dw.ctiles * g->NB; pl.ntiles = s->dw.cblocks;
+    pl.nwg = s->dw.nwg;
+    if ((long long)pl.nwg * lanes > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
+    s->family = BTX_FAMILY_DEPTHWISE;
+    s->out_bf16 = (flags & BTX_FLAG_OUT_BF16) ? 1 : (flags & BTX_FLAG_OUT_F32) ? 0 : (act_dtype == BTX_ACT_BF16) ? 1 : 0;
     s->g8_pairs = 1;
     s->pt.kg = 1;
     s->need = 0;
@@ -584,6 +640,9 @@ size_t btx_contract_workspace_bytes(const BtxGeom* g, int kind, int act_dtype, i
   Plan a, b;
   if (!g || make_plan(g, prec, flags, BM, &a) || make_plan(g, prec, flags, DBM, &b)) return 0;
   if (kind == BTX_KIND_LRT) return 0;  // no weight tiles, K never split: no partial sums either
+  // depthwise family: no workspace — nor on the gather kernel an off-grid pointer sends the launch to (K = taps <= 49: never split)
+  DwPlan dw;
+  if (make_dw_plan(kind, g, act_dtype, flags, false, nullptr, nullptr, a, &dw)) return 0;
   const int lanes = (int)plan_lanes(flags);
   // which kernel runs also depends on pointer alignment: the largest need of every plan the request can take
   auto with_tiles = [&](const Plan& pl) {

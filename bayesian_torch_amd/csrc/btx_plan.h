@@ -54,19 +54,30 @@ struct StemPoolPlan {
   int PB, bands, Rp, astage, sbytes, lds, patch_bytes, nwg, Hq, Wq;
 };
 
+// Tile plan of the depthwise family (btx_contract_dw.h): a workgroup owns DW_CB channels x TH x TW output pixels of
+// one image; PH x PW: the input patch it keeps in LDS.  Grid per lane: NB x rtiles x ctiles x cblocks, channel blocks fastest.
+constexpr int DW_CB = 64;            // channels per workgroup: 128 bytes of bf16, one full line per pixel
+constexpr int DW_TILE_PIX = 16;      // output pixels of a tile per pixel slot of the workgroup: 512 (bf16) / 256 (f32) pixels at most
+constexpr int DW_LDS_CAP = 72 * 1024;  // two workgroups resident per CU (160 KiB LDS)
+struct DwPlan {
+  int TH, TW, PH, PW, rtiles, ctiles, cblocks, lds, nwg;
+};
+constexpr int DW_R = 4;  // adjacent output pixels along W per thread (R x G accumulators, twice for Flipout: 193 VGPRs at most)
+
 // What contract_fwd_impl launches for a request: the kernel family, its tile plan and the workspace it needs.  The ONE copy of
 // the routing rules — the launch and btx_contract_plan_info both call select_fwd, and both read the family it decided.
 struct FwdSel {
-  int family;     // BTX_FAMILY_*; every family from BTX_FAMILY_DMA on reads pre-sampled weight tiles (uses_tiles)
+  int family;     // BTX_FAMILY_*; every family from BTX_FAMILY_DMA on but _DEPTHWISE reads pre-sampled weight tiles (uses_tiles)
   Plan pl;        // the plan of that family
   int par_major;  // parity-major pixel order (ContractParams.par_major): BTX_FAMILY_DMA only
   int par_mqp, g8_pairs, out_bf16;
   StemPlan stp;      // BTX_FAMILY_STEM, _STEM_POOL
   StemPoolPlan spp;  // BTX_FAMILY_STEM_POOL, else zero
   PatchPlan pt;      // BTX_FAMILY_PATCH, _TAPS, _TAPS2, else zero with kg = 1
+  DwPlan dw;         // BTX_FAMILY_DEPTHWISE, else zero
   size_t need, wt_off, wt_one, wt_all;
 };
-static inline bool uses_tiles(int family) { return family >= BTX_FAMILY_DMA; }
+static inline bool uses_tiles(int family) { return family >= BTX_FAMILY_DMA && family != BTX_FAMILY_DEPTHWISE; }
 
 // `unaligned`: some pointer of the launch is not 16-byte aligned (granule paths refused); `noise` / `ep` as passed to the
 // launch (nullable).  Lanes: BTX_FLAG_LANES(n) in flags.

@@ -388,6 +388,8 @@ int btx_contract_fwd_lanes(int kind, const BtxGeom* g,
 #define BTX_FAMILY_TAPS2     6  /* tap-unrolled 3x3 stride-2 kernel (btx_contract_taps2.h) */
 #define BTX_FAMILY_STEM      7  /* row-fused stem (btx_contract_stem.h) */
 #define BTX_FAMILY_STEM_POOL 8  /* row-fused stem + max-pool (btx_contract_stempool.h) */
+#define BTX_FAMILY_DEPTHWISE 9  /* depthwise 2-D stencil on the VALU, no MFMA (btx_contract_dw.h, BTX-DW v1: DESIGN.md section 27):
+                                   groups == C == N, weights sampled once per workgroup, K never split, no workspace */
 typedef struct BtxPlanInfo {
   int32_t  family;     /* BTX_FAMILY_* */
   int32_t  ksplits;    /* K splits (> 1: partial sums in the workspace + one reduce launch) */
