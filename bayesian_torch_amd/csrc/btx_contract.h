@@ -984,6 +984,9 @@ int launch_contract_gemm8_f32(int kind, const ContractParams& p, int nwg, hipStr
 int launch_contract_gemm8_x3(int kind, const ContractParams& p, int nwg, hipStream_t st);
 int launch_presample_batch_x3(const PresampleBatch& b, hipStream_t st);
 int launch_contract_dw(int kind, int act_bf16, const ContractParams& p, int nwg, hipStream_t st);  // btx_contract_dw.h (btx_dw.hip)
+// the depthwise weight gradient (btx_contract_dw_wgrad.h, btx_dw.hip): partial sums into `slab`, or with one slab into dw_mu / dw_delta
+int launch_dw_wgrad(int kind, int act_bf16, const BtxGeom* g, const DwWgradPlan& w, const void* x, const void* dy, float* dw_mu,
+                    float* dw_delta, float* slab, const BtxRng* rng, int swap, hipStream_t st);
 
 template <int PREC>
 static int launch_contract_impl(int kind, int act_bf16, bool gen, const ContractParams& p, int nwg, hipStream_t st) {

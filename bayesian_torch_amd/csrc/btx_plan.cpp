@@ -381,6 +381,53 @@ static bool make_dw_plan(int kind, const BtxGeom* g, int act_dtype, uint32_t fla
   return false;  // (a dilation so long that one pixel's footprint outgrows the LDS budget)
 }
 
+// Weight gradient of the depthwise family (btx_contract_dw_wgrad.h): what it takes, its tile and its slabs.
+//   tile:  ctiles = ceil(Wo / 32), TW = ceil(Wo / ctiles); TH = the most rows <= min(Ho, slots * 8 / TW) whose staged patch fits the
+//          LDS cap (none: one more column tile), then equal row tiles: rtiles = ceil(Ho / TH), TH = ceil(Ho / rtiles);
+//   slabs: tiles = NB * rtiles * ctiles in (image, row tile, column tile) order; want = max(1, 512 / (cblocks * ngrp));
+//          tps = ceil(tiles / min(want, tiles)); slabs = ceil(tiles / tps)  — no slab is empty.
+bool make_dw_wgrad_plan(int kind, const BtxGeom* g, int act_dtype, uint32_t flags, DwWgradPlan* w) {
+  if (kind != BTX_KIND_REPARAM && kind != BTX_KIND_FLIPOUT) return false;
+  if (flags & (BTX_FLAG_GATHER | BTX_FLAG_ROWFUSE | BTX_FLAG_TRANSPOSED)) return false;
+  if (g->D != 1 || g->KD != 1 || g->groups != g->C || g->N != g->C) return false;
+  int32_t Do, Ho, Wo;
+  if (btx_out_shape(g, 0, &Do, &Ho, &Wo) || Do != 1) return false;
+  const int T = g->KH * g->KW;
+  const int esz = (act_dtype == BTX_ACT_BF16) ? 2 : 4, G = 16 / esz, ngc = DW_CB / G, slots = 256 / ngc;
+  const int nk = kind == BTX_KIND_FLIPOUT ? 2 : 1;
+  if (T > 49 || g->KW > 7 || g->KH > 49 || g->C % G) return false;
+  if ((long long)g->NB * g->H * g->W * g->C > 0x7fffffffLL || (long long)g->NB * Ho * Wo * g->C > 0x7fffffffLL) return false;
+  const int form = (g->KH == 3 && g->KW == 3 && g->dh == 1 && g->dw == 1) ? 1 : 0;
+  const int ngrp = form ? 1 : g->KH, nt = form ? 9 : 7;
+  // rows of the patch a tile of `th` output rows stages: the whole footprint (form 1), or the rows of ONE kernel row (form 0)
+  auto rows = [&](int th) -> long long { return form ? (long long)(th - 1) * g->sh + 3 : th; };
+  const long long pixb = DW_CB * esz + (nk == 2 ? ngc : 0);  // a patch pixel and its sign bytes
+  const long long red = ((long long)DWW_RED_TAPS * slots + nk * nt) * DW_CB * 4;  // the closing reduction reuses the patch
+  for (int nct = (Wo + DWW_TILE_W - 1) / DWW_TILE_W; nct <= Wo; ++nct) {
+    const int TW = (Wo + nct - 1) / nct;
+    const long long PW = (long long)(TW - 1) * g->sw + (long long)(g->KW - 1) * g->dw + 1;
+    int TH = slots * DWW_TILE_PIX / TW;
+    if (TH > Ho) TH = Ho;
+    if (TH < 1) TH = 1;
+    while (TH >= 1 && rows(TH) * PW * pixb > DWW_LDS_CAP) --TH;
+    if (TH < 1) continue;
+    const int nrt = (Ho + TH - 1) / TH;
+    TH = (Ho + nrt - 1) / nrt;
+    const long long tiles = (long long)g->NB * nrt * nct, cblocks = (g->C + DW_CB - 1) / DW_CB;
+    long long want = DWW_TARGET_WGS / (cblocks * ngrp);
+    if (want < 1) want = 1;
+    if (want > tiles) want = tiles;
+    const long long tps = (tiles + want - 1) / want, slabs = (tiles + tps - 1) / tps;
+    const long long nwg = slabs * cblocks * ngrp, patch = rows(TH) * PW * pixb;
+    if (tiles > 0x7fffffffLL || nwg > 0x7fffffffLL) return false;
+    w->form = form; w->ngrp = ngrp; w->TH = TH; w->TW = TW; w->PH = (int)rows(TH); w->PW = (int)PW; w->rtiles = nrt; w->ctiles = nct;
+    w->cblocks = (int)cblocks; w->tiles = (int)tiles; w->tps = (int)tps; w->slabs = (int)slabs; w->nwg = (int)nwg;
+    w->lds = (int)(((patch > red ? patch : red) + 15) & ~15LL);
+    return true;
+  }
+  return false;
+}
+
 // workspace of the patch variant: split-K partials (256-byte padded), then the pre-sampled weight tiles
 // Flipout: [mu tiles | delta tiles of lane 0 | lane 1 | ...] — the mu tiles do not depend on the MC sample, one set serves
 // every lane; Reparameterization: [W tiles of lane 0 | lane 1 | ...]

@@ -64,6 +64,20 @@ struct DwPlan {
 };
 constexpr int DW_R = 4;  // adjacent output pixels along W per thread (R x G accumulators, twice for Flipout: 193 VGPRs at most)
 
+// Plan of the depthwise weight gradient (btx_contract_dw_wgrad.h).  A workgroup owns one 64-channel block, one
+// tap group (all nine taps of a 3x3 / dilation-1 kernel: form 1; else one kernel row: form 0, KH groups) and one SLAB: a run of `tps`
+// consecutive TH x TW output tiles in (image, row tile, column tile) order.  The slab count follows from the geometry alone.
+constexpr int DWW_TILE_PIX = 8;          // output pixels of a tile per pixel slot: 256 (bf16) / 128 (f32) pixels at most
+constexpr int DWW_TILE_W = 32;           // widest tile
+constexpr int DWW_LDS_CAP = 64 * 1024;   // two workgroups resident per CU
+constexpr int DWW_TARGET_WGS = 512;      // about two workgroups per CU over all channel blocks and tap groups
+constexpr int DWW_RED_TAPS = 4;          // taps per round of the closing cross-slot reduction
+struct DwWgradPlan {
+  int form, ngrp, TH, TW, PH, PW, rtiles, ctiles, cblocks, tiles, tps, slabs, lds, nwg;
+};
+// false: the request stays on the generic weight-gradient kernel.  Pointer-free (btx_wgrad_workspace_bytes asks without pointers).
+bool make_dw_wgrad_plan(int kind, const BtxGeom* g, int act_dtype, uint32_t flags, DwWgradPlan* w);
+
 // What contract_fwd_impl launches for a request: the kernel family, its tile plan and the workspace it needs.  The ONE copy of
 // the routing rules — the launch and btx_contract_plan_info both call select_fwd, and both read the family it decided.
 struct FwdSel {

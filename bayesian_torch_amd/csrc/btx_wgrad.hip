@@ -683,9 +683,17 @@ int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float*
   // one dy tile for both (the kernel is bound by its loads per MFMA; profiles/r05_experiments.txt E16)
   p.pair = (!taps3 && fast_ok && p.Cg == 32 && p.T >= 2) ? 1 : 0;
   p.Tw = p.pair ? (p.T + 1) / 2 : p.T;
-  const long long base = taps3 ? (long long)p.ntiles * p.ctiles : (long long)p.groups * p.ntiles * p.ctiles * p.Tw;
+  // Depthwise 2-D layers (groups == C == N, Cg = Ng = 1) on the slab path: the stencil reduction of btx_contract_dw_wgrad.h.  Its
+  // "chunks" are the planner's slabs (btx_plan.cpp make_dw_wgrad_plan); the reduction and rho launches below are shared.  Everything
+  // the family declines (BTX_FLAG_GATHER among it) keeps the generic kernel.
+  DwWgradPlan dwp;
+  const bool dw_route = slab && !db_mu && !p.sign_in && !p.sign_out && ((((uintptr_t)x) | ((uintptr_t)dy)) % 16 == 0) &&
+                        make_dw_wgrad_plan(kind, g, act_dtype, flags, &dwp);
+  const long long base = dw_route ? (long long)dwp.cblocks * dwp.ngrp
+                                  : taps3 ? (long long)p.ntiles * p.ctiles : (long long)p.groups * p.ntiles * p.ctiles * p.Tw;
   long long chunks, cpx;
   wgrad_chunks(base, M, taps3 ? WGRAD_TAPS3_TARGET_WGS : wgrad_target_wgs(slab), slab, &chunks, &cpx);
+  if (dw_route) chunks = dwp.slabs;
   p.chunks = (int)chunks; p.chunk_px = (int)cpx;
   if (base * chunks > 0x7fffffffLL) return BTX_E_UNSUPPORTED;
   if (slab && (size_t)chunks * nk * E * sizeof(float) > ws_bytes) return BTX_E_WORKSPACE;
@@ -710,7 +718,10 @@ int wgrad_impl(int kind, const BtxGeom* g, const void* x, const void* dy, float*
     hipLaunchKernelGGL(wgrad_zero_kernel, dim3((g->N + 255) / 256), dim3(256), 0, st, db_mu,
                        kind == BTX_KIND_FLIPOUT ? db_delta : (float*)nullptr, g->N);
   const int nwg = (int)(base * chunks);
-  if (taps3) {
+  if (dw_route) {
+    rc = launch_dw_wgrad(kind, act_dtype == BTX_ACT_BF16, g, dwp, x, dy, dw_mu, dw_delta, (float*)ws, rng, swap ? 1 : 0, st);
+    if (rc) return rc;
+  } else if (taps3) {
 #define BTX_LAUNCH_T3(KIND)                                                                                       \
   do {                                                                                                            \
     auto kfn = wgrad_taps3_kernel<KIND>;                                                                           \
@@ -804,5 +815,7 @@ extern "C" size_t btx_wgrad_workspace_bytes(int kind, const BtxGeom* g, int act_
     wgrad_chunks((long long)p.ntiles * p.ctiles, p.M, WGRAD_TAPS3_TARGET_WGS, true, &chunks, &cpx);
     if (chunks > most) most = chunks;
   }
+  DwWgradPlan dwp;  // the depthwise family (pointers decide at launch: the size covers both routes)
+  if (make_dw_wgrad_plan(kind, g, act_dtype, flags, &dwp) && dwp.slabs > most) most = dwp.slabs;
   return (size_t)most * nk * E * sizeof(float);
 }

@@ -551,7 +551,10 @@ def wgrad_hip(kind, x, dy, op, seed, sample_idx, layer_id, w_shape, signs=None, 
     rowfuse_plan(): the gradient is taken on the row-fused geometry the forward ran on (hashed signs, a kernel row as the
     channel axis) and un-padded here.  `rho_flat` (with raw=True): the layer's rho in GEMM-major order — a fifth result, drho =
     dW * eps * sigmoid(rho) (dW = dW_delta, whose buffer then HOLDS drho, for Flipout; dW_mu for Reparameterization), formed by the
-    slab reduction launch itself (btx_contract_wgrad_ws) or, on the atomics path, by btx_rho_grad."""
+    slab reduction launch itself (btx_contract_wgrad_ws) or, on the atomics path, by btx_rho_grad.
+    Depthwise 2-D layers (groups == in_channels == out_channels) land on the stencil reduction of the depthwise family by themselves
+    (csrc/btx_contract_dw_wgrad.h; with a workspace, hashed signs, bias gradients from btx_bias_grad as always here);
+    `_flags=_lib.FLAG_GATHER` keeps such a layer on the generic kernel (tests, tools/depthwise_bench.py --wgrad)."""
     L = _lib.lib()
     if op.transposed:
         raise _lib.BtxError("wgrad_hip wants the plain-convolution geometry (exchange x and dy for transposed layers)")

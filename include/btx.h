@@ -431,7 +431,15 @@ int btx_contract_wgrad(int kind, const BtxGeom* g, const void* x, const void* dy
  * rho_w / drho (both or neither): the reduction launch also writes what btx_rho_grad would compute from the finished
  * gradient, drho[i] = dw[i] * eps(i) * sigmoid(rho_w[i]) with dw = dw_delta (Flipout) or dw_mu (Reparameterization), eps of
  * stream BTX_STREAM_EPS_W of rng; rho_w in the order of mu_w.  drho may alias dw_delta (which then holds drho only); for a
- * Reparameterization layer it must be a buffer of its own (dw_mu is dmu). */
+ * Reparameterization layer it must be a buffer of its own (dw_mu is dmu).
+ * Depthwise 2-D layers (groups == C == N, T <= 49, KW <= 7, Reparameterization / Flipout) take the stencil reduction of the
+ * depthwise family with a workspace (csrc/btx_contract_dw_wgrad.h): 64 channels x a slab of output tiles
+ * per workgroup, x read once per tile instead of once per (channel, tap), slabs added in slab order.  Conditions: C a whole number
+ * of 16-byte granules of the activation dtype, x and dy 16-byte aligned, hashed signs (no noise->sign_*), no BTX_FLAG_ROWFUSE,
+ * db_mu == NULL; anything else runs on the generic kernel as before (a valid tensor never ends in BTX_E_ALIGN).
+ * BTX_FLAG_GATHER, passed to btx_contract_wgrad[_ws] or btx_wgrad_workspace_bytes, declines that kernel as it declines the
+ * depthwise forward: the generic kernel on the same request (tests, A/B timing); it changes nothing else about a weight gradient.
+ * btx_wgrad_workspace_bytes covers whichever kernel the pointers select: for such a layer the larger of the two sizes. */
 size_t btx_wgrad_workspace_bytes(int kind, const BtxGeom* g, int act_dtype, uint32_t flags);
 int btx_contract_wgrad_ws(int kind, const BtxGeom* g, const void* x, const void* dy, float* dw_mu, float* dw_delta,
                           float* db_mu, float* db_delta, const BtxRng* rng, const BtxNoise* noise /* nullable */,
