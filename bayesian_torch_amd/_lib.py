@@ -181,6 +181,8 @@ EXPORTS = ("btx_abi_version", "btx_strerror", "btx_kl_workspace_bytes", "btx_kl_
            "btx_kl_logu_workspace_bytes", "btx_kl_logu_model", "btx_kl_logu_model_bwd", "btx_logalpha_stats", "btx_logalpha_prune")
 # include/btx_drop.h: entry points added to ABI 9 in a header of their own (EXPORTS stays what include/btx.h declares)
 EXPORTS_DROP = ("btx_dropout_fwd", "btx_dropout_bwd")
+# include/btx_gru.h: the fused Bayesian GRU sequence, likewise an addition to ABI 9 in a header of its own
+EXPORTS_GRU = ("btx_gru_workspace_bytes", "btx_gru_fwd")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -401,6 +403,11 @@ def lib():
     L.btx_dropout_fwd.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, u32, f32, i32, i64, ctypes.POINTER(Rng), vp]
     L.btx_dropout_bwd.restype = i32
     L.btx_dropout_bwd.argtypes = [vp, vp, i32, i64, i64, i64, i32, i32, u32, f32, ctypes.POINTER(Rng), vp]
+    L.btx_gru_workspace_bytes.restype = sz
+    L.btx_gru_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.btx_gru_fwd.restype = i32
+    L.btx_gru_fwd.argtypes = [i32, ctypes.POINTER(LstmLayer), ctypes.POINTER(LstmLayer), ctypes.c_uint64, vp, i32, vp, vp,
+                              vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

@@ -765,10 +765,10 @@ def max_pool_train(mp, x):
 
 
 def _refuse_lstm(model, what):
-    from .layers.base_variational_layer import _VariationalLSTM
+    from .layers.base_variational_layer import _VariationalGRU, _VariationalLSTM
     for name, m in model.named_modules():
-        if isinstance(m, _VariationalLSTM):
-            raise _lib.BtxError("%s: the model holds the Bayesian LSTM %r (%s); its time steps consume the sample indices s + t, "
+        if isinstance(m, (_VariationalLSTM, _VariationalGRU)):
+            raise _lib.BtxError("%s: the model holds the Bayesian LSTM / GRU %r (%s); its time steps consume the sample indices s + t, "
                                 "which collide with the indices of the Monte-Carlo passes: use num_mc=1" % (what, name, type(m).__name__))
 
 

@@ -1137,6 +1137,62 @@ def lstm_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, c0=
     return hs, cs, kl
 
 
+def gru_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, kl_terms=None, out=None):
+    """The whole sequence of a Bayesian GRU in one call (btx_gru_fwd: 1 + T launches enqueued on the current stream).
+    x [rows, T, I] (f32 / bf16); ih / hh = (mu_w [3H, K], rho_w, mu_b [3H] or None, rho_b, layer_id, sample_idx, sample_dev), gate
+    rows in torch's order (r, z, n): step t of a layer draws the noise of sample index sample_idx + lane + t, or
+    sample_dev[lane] + t when sample_dev (an int32 tensor with one word per lane) is given.  lanes > 1: rows == batch (one input,
+    shared by the lanes) or lanes * batch (lane l's rows at l * B); h0 holds lanes * B rows.  kl_terms = (kl_ih, kl_hh): f32
+    scalars whose per-step sum over the T steps is returned as the second value (else None).  out: a contiguous
+    [lanes * B, T, H] tensor of x's dtype to write hidden_seq into (any element-aligned address).  Returns (hidden_seq, kl),
+    hidden_seq [lanes * B, T, H]."""
+    L = _lib.lib()
+    if not x.is_cuda:
+        raise _lib.BtxError("gru_hip needs a CUDA (ROCm) tensor")
+    act = _lstm_act(x)
+    prec = prec or _PRECISION
+    if prec not in LSTM_PRECISIONS:
+        raise _lib.BtxError("the fused GRU sequence has no %s form" % prec)
+    lanes = int(lanes)
+    rows, T, I = x.shape
+    H = ih[0].shape[0] // 3
+    B, x_shared = rows, 0
+    if lanes > 1:
+        if batch is None:
+            raise _lib.BtxError("lanes > 1 needs batch (rows per lane)")
+        B = int(batch)
+        if rows == B:
+            x_shared = 1
+        elif rows != lanes * B:
+            raise _lib.BtxError("lanes=%d x batch=%d does not match the input rows %d" % (lanes, B, rows))
+    x = x.contiguous()
+    li, lh = _lstm_layer(ih, lanes), _lstm_layer(hh, lanes)
+    if ih[0].shape[0] != 3 * H or tuple(hh[0].shape) != (3 * H, H) or ih[0].shape[1] != I:
+        raise _lib.BtxError("GRU parameter shapes do not match the input (I=%d, H=%d)" % (I, H))
+    if h0 is not None:
+        if h0.shape != (lanes * B, H):
+            raise _lib.BtxError("h0 must be [lanes * B, H] = [%d, %d]" % (lanes * B, H))
+        h0 = h0.to(x.dtype).contiguous()
+    hs = out
+    if hs is None:
+        hs = torch.empty(lanes * B, T, H, dtype=x.dtype, device=x.device)
+    elif tuple(hs.shape) != (lanes * B, T, H) or hs.dtype != x.dtype or hs.device != x.device or not hs.is_contiguous():
+        raise _lib.BtxError("out must be a contiguous [%d, %d, %d] %s tensor on x's device" % (lanes * B, T, H, x.dtype))
+    need = L.btx_gru_workspace_bytes(lanes, B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    kl = ki = kh = None
+    if kl_terms is not None:
+        ki, kh = (k.detach().to(torch.float32).reshape(1).contiguous() for k in kl_terms)
+        kl = torch.empty((), dtype=torch.float32, device=x.device)
+    _lib.check(L.btx_gru_fwd(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                             ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(), x_shared,
+                             h0.data_ptr() if h0 is not None else None, hs.data_ptr(), ki.data_ptr() if ki is not None else None,
+                             kh.data_ptr() if kh is not None else None, kl.data_ptr() if kl is not None else None,
+                             lanes, B, I, H, T, act, _lib.PREC_CODE[prec], ws.data_ptr(), need,
+                             torch.cuda.current_stream(x.device).cuda_stream))
+    return hs, kl
+
+
 def fill_eps_hip(n, device, seed, sample_idx, layer_id, rng_stream, sample_dev=None):
     """BTX-RNG v1 eps for a flat index space of n elements, as a flat f32 CUDA tensor.  sample_dev: the sample index lives in
     that device word (captured steps) and sample_idx is ignored."""

@@ -1033,3 +1033,144 @@ class _VariationalLSTM(BaseVariationalLayer_):
         if return_kl:
             return hidden_seq, (hidden_seq, c_ts), kl
         return hidden_seq, (hidden_seq, c_ts)
+
+
+class _VariationalGRU(BaseVariationalLayer_):
+    """GRU cell unrolled over time on two Bayesian Linear layers (input-to-hidden `ih`: in -> 3*out, hidden-to-hidden `hh`:
+    out -> 3*out), the sibling of _VariationalLSTM (not in the reference).  Gate rows are in torch's order
+    (r, z, n), so weight_ih_l0 / weight_hh_l0 of an nn.GRU copy into ih.mu_weight / hh.mu_weight unchanged.  X is
+    [batch, seq, in_features]; every time step calls both Linear layers on consecutive BTX-RNG sample indices and computes
+
+        r = sigmoid(gi_r + gh_r)    z = sigmoid(gi_z + gh_z)    n = tanh(gi_n + r * gh_n)    h = (1 - z) * n + z * h
+
+    with each Linear's own bias inside gi / gh (b_hn sits inside the product with r, as in torch).  hidden_states is h0 [batch, out]
+    or None (zeros).  Returns (hidden_seq [batch, seq, out], h_T [batch, out][, kl]), kl = the per-step KL terms summed over the
+    steps (the LSTM's accounting).  The gate math runs in float32 for bfloat16 / float16 inputs and in the input's dtype otherwise.
+    `_linear_cls` is the Linear class of the family."""
+
+    _linear_cls = None
+
+    def __init__(self, in_features, out_features, prior_mean=0, prior_variance=1, posterior_mu_init=0,
+                 posterior_rho_init=-3.0, bias=True):
+        super().__init__()
+        self.in_features, self.out_features = in_features, out_features
+        self.prior_mean, self.prior_variance = prior_mean, prior_variance
+        self.posterior_mu_init = posterior_mu_init,   # 1-tuples, as the LSTM classes keep them
+        self.posterior_rho_init = posterior_rho_init,
+        self.bias = bias
+        kw = dict(prior_mean=prior_mean, prior_variance=prior_variance, posterior_mu_init=posterior_mu_init,
+                  posterior_rho_init=posterior_rho_init, bias=bias)
+        self.ih = self._linear_cls(in_features=in_features, out_features=out_features * 3, **kw)
+        self.hh = self._linear_cls(in_features=out_features, out_features=out_features * 3, **kw)
+        for lin in (self.ih, self.hh):
+            lin.__dict__["_btx_no_prior"] = self._NO_PRIOR
+
+    _NO_PRIOR = ("non-Gaussian priors are not supported on the Bayesian GRU classes: the fused sequence counts ONE KL term times the "
+                 "number of steps, while the eager loop would draw a new estimate per step")
+    # models.get_kl_loss: kl_loss() of this module is the sum over its children `ih` and `hh`, which the walk meets on their own
+    _btx_kl_composite = True
+
+    def set_prior(self, prior, kl_samples=1):
+        from .. import priors as _priors
+        if _priors.check_prior(prior) is not None:
+            raise _lib.BtxError(self._NO_PRIOR)
+        return self
+
+    def kl_loss(self):
+        return self.ih.kl_loss() + self.hh.kl_loss()
+
+    # fused_sequence (opt-in; models.fuse_model sets it): inference forwards on the GPU run the whole sequence as one
+    # btx_gru_fwd call — 1 + T launches, lanes and graph capture included — with the noise and recurrence of the eager loop.
+    # There is no fused training path: forwards that need gradients take the eager loop, differentiated through the Linear layers.
+    @property
+    def fused_sequence(self):
+        return bool(self.__dict__.get("_btx_fused_sequence", False))
+
+    @fused_sequence.setter
+    def fused_sequence(self, on):
+        on = bool(on)
+        self.__dict__["_btx_fused_sequence"] = on
+        for lin in (self.ih, self.hh):
+            lin.__dict__["_btx_fused_seq"] = on  # rng.presample(): no tiles for the inner layers
+
+    def _fused_ok(self, X, h0):
+        """the conditions of the fused sequence path; otherwise the eager loop runs (and raises where it raises)"""
+        ih, hh = self.ih, self.hh
+        if not self.fused_sequence or not X.is_cuda or not ih._use_hip(X) or X.dim() != 3:
+            return False
+        if X.dtype not in (torch.float32, torch.bfloat16) or ih._needs_grad(X) or hh._needs_grad(None):
+            return False
+        if h0 is not None:
+            if h0.dtype != X.dtype or h0.dim() != 2 or (torch.is_grad_enabled() and h0.requires_grad):
+                return False
+        if ih._forward_hooks or ih._forward_pre_hooks or hh._forward_hooks or hh._forward_pre_hooks:
+            return False
+        prec = ih.precision or BF.get_precision()
+        if prec not in BF.LSTM_PRECISIONS or (hh.precision or BF.get_precision()) != prec:
+            return False
+        return ih._lanes() == hh._lanes()
+
+    def _forward_fused(self, X, h0, return_kl):
+        ih, hh = self.ih, self.hh
+        nb, steps, _ = X.shape
+        lanes, lane_batch = ih._lanes()
+        B = nb
+        if lanes > 1:
+            B = lane_batch if nb == lane_batch else nb // lanes
+            if h0 is not None and h0.shape[0] == B:  # one initial state, shared by the lanes
+                h0 = h0.repeat(lanes, 1)
+
+        def params(lin):
+            mu, rho = lin._w()
+            s = lin._btx_sample
+            lin.__dict__["_btx_sample"] = s + steps * lanes  # the counter of `steps` eager forwards
+            return (mu.detach(), rho.detach(), lin.mu_bias.detach() if lin.mu_bias is not None else None,
+                    lin.rho_bias.detach() if lin.rho_bias is not None else None, lin._btx_layer_id, s,
+                    getattr(lin, "_btx_sample_dev", None))
+
+        kl_terms = (ih.kl_loss(), hh.kl_loss())
+        kind = _lib.KIND_FLIPOUT if self._family == "flipout" else _lib.KIND_REPARAM
+        hidden_seq, kl = BF.gru_hip(kind, X, params(ih), params(hh), _rng.seed(), prec=ih.precision or BF.get_precision(),
+                                    lanes=lanes, batch=B, h0=h0, kl_terms=kl_terms)
+        if return_kl:
+            return hidden_seq, hidden_seq[:, -1], kl
+        return hidden_seq, hidden_seq[:, -1]
+
+    def forward(self, X, hidden_states=None, return_kl=True):
+        if self.dnn_to_bnn_flag:
+            return_kl = False
+        if self.fused_sequence and self._fused_ok(X, hidden_states):
+            return self._forward_fused(X, hidden_states, return_kl)
+        nb, steps, _ = X.size()
+        hs = self.out_features
+        for lin in (self.ih, self.hh):
+            # every time step must draw fresh noise (see _VariationalLSTM.forward): a pinned index would reuse one draw for every step
+            if X.is_cuda and steps > 1 and (lin.__dict__.get("_btx_lanes", 1) > 1 or getattr(lin, "_btx_sample_dev", None) is not None):
+                raise _lib.BtxError("GRU layers need a fresh MC sample index per time step, but this layer's index is pinned "
+                                    "(MC sample lanes are set, or a live mc.GraphedMC / GraphedTrainStep keeps the index in a device "
+                                    "word): set fused_sequence (models.fuse_model) for inference, or close() the graph / "
+                                    "rng.set_sample_lanes(model, None) and run eager forwards (mc.mc_forward(lanes=1))")
+        h_t = torch.zeros(nb, hs, device=X.device, dtype=X.dtype) if hidden_states is None else hidden_states
+        cdt = torch.float32 if X.dtype in (torch.bfloat16, torch.float16) else X.dtype  # the dtype of the gate math
+        hidden, kl = [], 0
+        # GPU: one KL reduction per Linear layer per sequence, summed per step in the eager order; CPU: KL inside every Linear forward
+        once = X.is_cuda and self.ih._use_hip(X)
+        if once:
+            kl_i, kl_h = self.ih.kl_loss(), self.hh.kl_loss()
+        for t in range(steps):
+            if once:
+                gi, gh = self.ih(X[:, t, :], return_kl=False), self.hh(h_t, return_kl=False)
+            else:
+                gi, kl_i = self.ih(X[:, t, :])
+                gh, kl_h = self.hh(h_t)
+            kl = kl + kl_i + kl_h
+            gi, gh = gi.to(cdt), gh.to(cdt)
+            r_t = torch.sigmoid(gi[:, :hs] + gh[:, :hs])
+            z_t = torch.sigmoid(gi[:, hs:2 * hs] + gh[:, hs:2 * hs])
+            n_t = torch.tanh(gi[:, 2 * hs:] + r_t * gh[:, 2 * hs:])
+            h_t = ((1 - z_t) * n_t + z_t * h_t.to(cdt)).to(X.dtype)
+            hidden.append(h_t)
+        hidden_seq = torch.stack(hidden, dim=1).contiguous()  # [batch, seq, out]
+        if return_kl:
+            return hidden_seq, h_t, kl
+        return hidden_seq, h_t

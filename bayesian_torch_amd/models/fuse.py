@@ -36,7 +36,7 @@ def _is_q8(m):
 
 
 def _is_lstm(m):
-    """a Bayesian LSTM: a leaf of the trace (its forward loops over the time steps), never an epilogue site; fuse_model switches
+    """a Bayesian LSTM or GRU: a leaf of the trace (its forward loops over the time steps), never an epilogue site; fuse_model switches
     it to its fused sequence path (fused_sequence)"""
     return hasattr(m, "fused_sequence") and hasattr(m, "ih") and hasattr(m, "hh")
 
@@ -683,7 +683,7 @@ class _FusedForward:
 def _lstm_training(model, on):
     if on:
         for m in model.modules():
-            if _is_lstm(m):
+            if _is_lstm(m) and hasattr(type(m), "fused_training"):  # (a Bayesian GRU has no fused training path)
                 m.fused_training = True
 
 
@@ -714,8 +714,8 @@ def fuse_model(model, lstm_training=False, lrt_training=False):
     in-place edits).  The module tree, state_dict keys and parameters are unchanged; nothing is copied, moved or sampled.
     A model whose forward cannot be traced (control flow on tensor values), or whose inlined modules have forward hooks at
     fusing time, gets the folding inside its nn.Sequential containers only (consecutive children V, BN, activation), with one
-    warning.  Every Bayesian LSTM (LSTMReparameterization / LSTMFlipout) is a leaf of the trace and gets fused_sequence = True:
-    its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd call.  Returns the number of fused sites plus
+    warning.  Every Bayesian LSTM (LSTMReparameterization / LSTMFlipout) and GRU (GRUReparameterization / GRUFlipout) is a leaf of the
+    trace and gets fused_sequence = True: its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd / btx_gru_fwd call.  Returns the number of fused sites plus
     the number of LSTMs switched; a second call returns 0.  lstm_training=True also sets fused_training on every Bayesian LSTM:
     its training forwards on the GPU then run btx_lstm_fwd_train and their backward btx_lstm_bwd (also inside
     autograd.GraphedTrainStep); it changes neither the count nor what the default call does.  lrt_training=True does the same for
