@@ -631,7 +631,20 @@ class BatchNormTrainFn(torch.autograd.Function):
         dev = x.device
         # the kernels move 8 channels per 16-byte access: a tensor off that grid (a dense view into a flat buffer) enters as one
         # aligned copy with the same strides — the same launches, the same bits
-        x, residual = BF.on_grid(x), BF.on_grid(residual)
+        x = BF.on_grid(x)
+        if residual is not None:
+            # the kernel addresses the residual with x's strides: anything stored otherwise (NCHW-dense, a batch or channel slice,
+            # an expanded row) enters as one copy in x's layout (DESIGN.md "Stride contract")
+            if residual.shape != x.shape or residual.dtype != x.dtype:
+                raise _lib.BtxError("batch_norm_train: residual must have x's shape and dtype (got %s %s for %s %s)"
+                                    % (tuple(residual.shape), residual.dtype, tuple(x.shape), x.dtype))
+            if residual.stride() != x.stride():
+                residual = torch.empty_like(x).copy_(residual)
+            residual = BF.on_grid(residual)
+        # the running estimates are read and written as dense [C] vectors: a strided one goes through a dense copy and back
+        rm_in, rv_in = running_mean, running_var
+        running_mean = rm_in.contiguous() if rm_in is not None else None
+        running_var = rv_in.contiguous() if rv_in is not None else None
         y = torch.empty_like(x)  # preserves the channels-last strides
         save_mean = torch.empty(C, dtype=torch.float32, device=dev)
         save_invstd = torch.empty(C, dtype=torch.float32, device=dev)
@@ -650,6 +663,10 @@ class BatchNormTrainFn(torch.autograd.Function):
                                       ptr(running_var), pdt, float(momentum if momentum is not None else 0.0), float(eps),
                                       save_mean.data_ptr(), save_invstd.data_ptr(), ptr(batches_tracked),
                                       ctypes.byref(fuse) if fuse is not None else None, ws.data_ptr(), ws.numel(), stream))
+        if running_mean is not rm_in:
+            rm_in.copy_(running_mean)
+        if running_var is not rv_in:
+            rv_in.copy_(running_var)
         ctx.save_for_backward(x, w, save_mean, save_invstd, mask)
         ctx.has_bias = bias is not None
         ctx.has_res = residual is not None

@@ -482,8 +482,9 @@ def contract_hip(kind, x, mu_p, rho_p, mu_b, rho_b, op, seed, sample_idx, layer_
         for name in ("scale", "shift"):
             t = epilogue.get(name)
             if t is not None:
-                if t.dtype != torch.float32 or t.numel() != op.out_channels or not t.is_contiguous():
-                    raise ValueError("epilogue %s must be a contiguous float32 [out_channels] tensor" % name)
+                if t.dtype != torch.float32 or t.numel() != op.out_channels:
+                    raise ValueError("epilogue %s must be a float32 [out_channels] tensor" % name)
+                t = t.contiguous()  # a strided vector (a slice of a wider table) enters as one dense copy
                 keep.append(t)
                 setattr(ep, name, t.data_ptr())
         res = epilogue.get("residual")
@@ -1326,6 +1327,9 @@ def lrt_bwd_hip(x, dy, root, mu_p, rho_p, rho_b, op, seed, sample_idx, layer_id,
     dyp, _, _, _ = _to_channels_last(dy2 if dy2.dtype == x.dtype else dy2.to(x.dtype), yop)
     if dyp.numel() != root.numel():
         raise _lib.BtxError("lrt_bwd_hip: dy does not match the saved root (%d != %d elements)" % (dyp.numel(), root.numel()))
+    if root.dtype != torch.float32:
+        raise _lib.BtxError("lrt_bwd_hip: root must be the float32 tensor lrt_fwd_train_hip returned (got %s)" % root.dtype)
+    root = root.contiguous()  # read through its bare pointer in the element order of dyp
     dev = x.device
     g = _lrt_geom(op, nb, spatial)
     need = ctypes.c_size_t(0)
@@ -1441,7 +1445,7 @@ def maxpool2d_train_hip(x, kernel, stride, padding):
     its maximum (uint8 [N][Ho][Wo][C]) for maxpool2d_bwd_hip"""
     L = _lib.lib()
     n, c, h, w = x.shape
-    x = on_grid(x)
+    x = on_grid(x.contiguous(memory_format=torch.channels_last))
     ho, wo = (h + 2 * padding - kernel) // stride + 1, (w + 2 * padding - kernel) // stride + 1
     out = torch.empty((n, c, ho, wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
     idx = torch.empty(n * ho * wo * c, dtype=torch.uint8, device=x.device)
@@ -1454,7 +1458,12 @@ def maxpool2d_bwd_hip(dy, idx, x_shape, kernel, stride, padding):
     """btx_maxpool2d_cl_bwd: the gradient of maxpool2d_train_hip's input (channels-last), dy channels-last"""
     L = _lib.lib()
     n, c, h, w = x_shape
-    dy = on_grid(dy)
+    dy = on_grid(dy.contiguous(memory_format=torch.channels_last))
+    ho, wo = (h + 2 * padding - kernel) // stride + 1, (w + 2 * padding - kernel) // stride + 1
+    if tuple(dy.shape) != (n, c, ho, wo) or idx.dtype != torch.uint8 or idx.numel() != dy.numel():
+        raise _lib.BtxError("maxpool2d_bwd_hip: dy must be [%d, %d, %d, %d] and idx the uint8 window positions of maxpool2d_train_hip, "
+                            "one per element of dy" % (n, c, ho, wo))
+    idx = idx.contiguous()
     dx = torch.empty((n, c, h, w), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
     _lib.check(L.btx_maxpool2d_cl_bwd(dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), _lib.ACT_BF16 if dy.dtype == torch.bfloat16 else _lib.ACT_F32,
                                       n, h, w, c, kernel, stride, padding, torch.cuda.current_stream(dy.device).cuda_stream))
@@ -1624,6 +1633,7 @@ def dropout_hip(x, T, scale, mode, seed, sample_idx, layer_id, sample_dev=None, 
     if N * C * S > _lib.DROP_MAX_ELEMENTS:
         raise _lib.BtxError("dropout: a lane tensor of more than 2^35 elements")
     xr, layout = _drop_layout(x, N, C, S)
+    dst = None
     if shared and lanes > 1:
         oshape = (lanes * B,) + tuple(x.shape[1:])
         if layout == _lib.DROP_CL and x.dim() >= 3 and not (S == 1 or C == 1):
@@ -1634,8 +1644,15 @@ def dropout_hip(x, T, scale, mode, seed, sample_idx, layer_id, sample_dev=None, 
             out = torch.empty(oshape, dtype=x.dtype, device=x.device)
     elif out is None:
         out = torch.empty_like(xr)  # preserve_format: the memory order of xr (dense)
+    else:
+        if tuple(out.shape) != tuple(xr.shape) or out.dtype != x.dtype or out.device != x.device:
+            raise _lib.BtxError("dropout_hip: out must be a %s tensor of shape %s on x's device" % (x.dtype, tuple(xr.shape)))
+        if out.stride() != xr.stride():
+            # the kernel writes `out` in the memory order it reads xr in: a target stored otherwise (x itself when x is a strided
+            # view, as in an in-place call) is written through one dense buffer and a copy back
+            dst, out = out, torch.empty_like(xr)
     if x.numel() == 0:
-        return out
+        return out if dst is None else dst
     r = _lib.Rng(int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_idx) & 0xFFFFFFFF, int(layer_id) & 0xFFFFFFFF,
                  sample_dev.data_ptr() if sample_dev is not None else None)
     act = _lib.ACT_BF16 if x.dtype == torch.bfloat16 else _lib.ACT_F32
@@ -1645,7 +1662,7 @@ def dropout_hip(x, T, scale, mode, seed, sample_idx, layer_id, sample_dev=None, 
             raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
         _lib.check(L.btx_dropout_bwd(xr.data_ptr(), out.data_ptr(), act, N, C, S, DROP_MODES[mode], layout, int(T), float(scale),
                                      ctypes.byref(r), stream))
-        return out
+        return out if dst is None else dst.copy_(out)
     _lib.check(L.btx_dropout_fwd(xr.data_ptr(), out.data_ptr(), act, N, C, S, DROP_MODES[mode], layout, int(T), float(scale),
                                  lanes, B if (shared and lanes > 1) else lanes * B, ctypes.byref(r), stream))
-    return out
+    return out if dst is None else dst.copy_(out)

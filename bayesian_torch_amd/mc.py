@@ -51,10 +51,11 @@ def accumulate(packed, logits, kl=0.0):
             act = _lib.ACT_BF16
         else:
             lg, act = lg.float(), _lib.ACT_F32
-        rc = _lib.lib().btx_mc_accumulate(lg.data_ptr(), bs, C, act, float(kl), packed.data_ptr(),
+        pk = packed.contiguous()  # the kernel adds into a dense vector: a strided one goes through a dense copy and back
+        rc = _lib.lib().btx_mc_accumulate(lg.data_ptr(), bs, C, act, float(kl), pk.data_ptr(),
                                           torch.cuda.current_stream(lg.device).cuda_stream)
         _lib.check(rc)
-        return packed
+        return packed if pk is packed else packed.copy_(pk)
     return _accumulate_torch(packed, logits, kl)
 
 
@@ -71,9 +72,10 @@ def accumulate_lanes(packed, logits, lanes, kl=0.0):
         return packed
     lg = logits.contiguous()
     act = _lib.ACT_F32 if lg.dtype == torch.float32 else _lib.ACT_BF16
-    _lib.check(_lib.lib().btx_mc_accumulate_lanes(lg.data_ptr(), lanes, bs, lg.shape[1], act, float(kl), packed.data_ptr(),
+    pk = packed.contiguous()
+    _lib.check(_lib.lib().btx_mc_accumulate_lanes(lg.data_ptr(), lanes, bs, lg.shape[1], act, float(kl), pk.data_ptr(),
                                                   torch.cuda.current_stream(lg.device).cuda_stream))
-    return packed
+    return packed if pk is packed else packed.copy_(pk)
 
 
 def unpack(packed, bs, num_classes):
@@ -153,12 +155,13 @@ class GaussianStats:
         if packed.dtype != torch.float64 or packed.numel() != 3 * N + 2 or packed.device != out.device:
             raise ValueError("packed must be a float64 vector of %d words on %s" % (3 * N + 2, out.device))
         has_var = self.variance == "log"
-        if out.is_cuda and out.dtype in (torch.float32, torch.bfloat16) and packed.is_contiguous() and N <= 2 ** 31 - 3:
+        if out.is_cuda and out.dtype in (torch.float32, torch.bfloat16) and N <= 2 ** 31 - 3:
             o = out.contiguous()
+            pk = packed.contiguous()  # a strided packed vector: a dense copy for the kernel, and back
             act = _lib.ACT_F32 if o.dtype == torch.float32 else _lib.ACT_BF16
-            _lib.check(_lib.lib().btx_mc_moments_lanes(o.data_ptr(), lanes, bs, D, int(has_var), act, float(kl), packed.data_ptr(),
+            _lib.check(_lib.lib().btx_mc_moments_lanes(o.data_ptr(), lanes, bs, D, int(has_var), act, float(kl), pk.data_ptr(),
                                                        torch.cuda.current_stream(o.device).cuda_stream))
-            return packed
+            return packed if pk is packed else packed.copy_(pk)
         for k in range(lanes):
             o = out[k * bs:(k + 1) * bs]
             o = o if o.dtype == torch.float64 else o.float()  # what the kernel widens: the f32 value

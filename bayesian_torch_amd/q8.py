@@ -24,6 +24,8 @@ class QTensor:
             raise _lib.BtxError("QTensor holds uint8 values (got %s)" % q.dtype)
         if q.dim() == 4:
             q = q.contiguous(memory_format=torch.channels_last)
+        elif not q.is_contiguous():
+            q = q.contiguous()  # the kernels read the carrier through its bare pointer: a strided [B, K] view enters as one dense copy
         self.q, self.scale, self.zero_point = q, float(scale), int(zero_point)
 
     shape = property(lambda self: self.q.shape)
@@ -174,8 +176,7 @@ def contract(xq, z_x, W, S, b_i, n, kernel, stride, padding, dilation, multiplie
         if residual.dtype != torch.uint8 or residual.shape != out.shape or residual.device != out.device:
             raise _lib.BtxError("quantized conv: the residual must be uint8 of the output's shape %s on its device (got %s %s)"
                                 % (tuple(out.shape), residual.dtype, tuple(residual.shape)))
-        if residual.dim() == 4:
-            residual = residual.contiguous(memory_format=torch.channels_last)
+        residual = residual.contiguous(memory_format=torch.channels_last) if residual.dim() == 4 else residual.contiguous()
         _lib.check(_lib.lib().btx_q8_contract_res(ctypes.byref(g), xq.data_ptr(), int(z_x), W.data_ptr(), S.data_ptr(), b_i.data_ptr(),
                                                   float(multiplier), int(z_o), 1 if relu else 0, 1 if out_f32 else 0,
                                                   residual.data_ptr(), ctypes.byref(add), out.data_ptr(), _stream(xq.device)))
