@@ -1,4 +1,5 @@
-// btx_gru.hip — fused Bayesian GRU inference (GRUReparameterization / GRUFlipout) for gfx950.  DESIGN.md §28.
+// btx_gru.hip — fused Bayesian GRU forward (GRUReparameterization / GRUFlipout) for gfx950: inference (btx_gru_fwd)
+// and the training forward (btx_gru_fwd_train, §29: the same launches, the step's epilogue also saves what btx_gru_bwd needs).
 //
 // One sequence = 1 + T launches on the caller's stream, enqueued from C++ (btx_gru_fwd), so it can be captured whole:
 //
@@ -30,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/btx_gru.h"
+#include "../../include/btx_gru_train.h"
 #include "btx_rng.h"
 
 namespace {
@@ -60,6 +62,7 @@ struct GruKArgs {
   const float* kl_i;             // projection launch, block 0: kl_out = sum over T of (kl_i + kl_h), eager order
   const float* kl_h;
   float* kl_out;
+  float* sv;                     // training step (SAVE): [T][B][4H] f32 planes r_t, z_t, n_t, gh_n,t
 };
 
 template <typename T> __device__ __forceinline__ float ld_f(const T* p) { return (float)*p; }
@@ -73,7 +76,8 @@ __device__ __forceinline__ bool sign_neg(uint32_t idx, uint32_t ka, uint32_t kb)
 __device__ __forceinline__ float sigm(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 // STEP = 0: input projection (grid.x = hblocks * lanes * T, grid.y = batch blocks); 1: recurrent step t (grid.z = lanes)
-template <int FLIP, int BFP, typename XT, int STEP>
+// SAVE (step launches of btx_gru_fwd_train, one lane): the epilogue also keeps the gates and the n row's recurrent sum
+template <int FLIP, int BFP, typename XT, int STEP, int SAVE = 0>
 __global__ __launch_bounds__(256) void gru_kernel(GruKArgs a) {
   __shared__ __attribute__((aligned(16))) float xs[GB * GXS];
   __shared__ __attribute__((aligned(16))) float xd[FLIP ? GB * GXS : 4];
@@ -248,35 +252,32 @@ __global__ __launch_bounds__(256) void gru_kernel(GruKArgs a) {
   const float n_t = tanhf(gi[2] + r_t * gh[2]);
   const float h = (1.0f - z_t) * n_t + z_t * h_prev;
   st_f((XT*)a.hs + (((long long)lane * B + gb) * a.T + t) * H + j, h);
+  if (SAVE) {  // what btx_gru_bwd needs: with these it evaluates no transcendental and never re-reads Gi
+    float* sp = a.sv + ((long long)t * B + gb) * 4 * H + j;
+    sp[0] = r_t; sp[H] = z_t; sp[2 * H] = n_t; sp[3 * H] = gh[2];
+  }
 }
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-template <int FLIP, int BFP, typename XT>
+template <int FLIP, int BFP, typename XT, int SAVE = 0>
 hipError_t launch_all(GruKArgs pa, GruKArgs sa, int lanes, int bblocks, int T, hipStream_t st) {
   hipLaunchKernelGGL((gru_kernel<FLIP, BFP, XT, 0>), dim3(pa.hblocks * lanes * T, bblocks, 1), dim3(256), 0, st, pa);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   for (int t = 0; t < T; ++t) {
     sa.t = t;
-    hipLaunchKernelGGL((gru_kernel<FLIP, BFP, XT, 1>), dim3(sa.hblocks, bblocks, lanes), dim3(256), 0, st, sa);
+    hipLaunchKernelGGL((gru_kernel<FLIP, BFP, XT, 1, SAVE>), dim3(sa.hblocks, bblocks, lanes), dim3(256), 0, st, sa);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t btx_gru_workspace_bytes(int lanes, int B, int H, int T) {
-  if (lanes <= 0 || B <= 0 || H <= 0 || T <= 0) return 0;
-  return align256((size_t)lanes * T * B * 3 * H * sizeof(float));
-}
-
-int btx_gru_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
-                const void* h0, void* hidden_seq, const float* kl_ih, const float* kl_hh, float* kl_out, int lanes, int B,
-                int I, int H, int T, int act_dtype, int prec, void* workspace, size_t ws_bytes, void* stream) {
+// saved != null: the training forward (one lane), whose step launches are the SAVE form
+int gru_fwd_impl(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
+                 const void* h0, void* hidden_seq, const float* kl_ih, const float* kl_hh, float* kl_out, int lanes, int B,
+                 int I, int H, int T, int act_dtype, int prec, void* workspace, size_t ws_bytes, void* saved,
+                 size_t saved_bytes, void* stream) {
   if (!ih || !hh || !x || !hidden_seq || !workspace) return BTX_E_NULL;
   if (!ih->mu_w || !ih->rho_w || !hh->mu_w || !hh->rho_w) return BTX_E_NULL;
   if ((ih->mu_b == nullptr) != (ih->rho_b == nullptr) || (hh->mu_b == nullptr) != (hh->rho_b == nullptr)) return BTX_E_NULL;
@@ -293,7 +294,8 @@ int btx_gru_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64
     return BTX_E_UNSUPPORTED;
   const uint64_t hblocks = ((uint64_t)H + GJ - 1) / GJ, bblocks = ((uint64_t)B + GB - 1) / GB;
   if (hblocks * lanes * T > 0x7fffffffull || bblocks > 65535) return BTX_E_UNSUPPORTED;
-  if (ws_bytes < btx_gru_workspace_bytes(lanes, B, H, T)) return BTX_E_WORKSPACE;
+  if (ws_bytes < (saved ? btx_gru_train_workspace_bytes(B, H, T) : btx_gru_workspace_bytes(lanes, B, H, T))) return BTX_E_WORKSPACE;
+  if (saved && saved_bytes < btx_gru_train_saved_bytes(B, H, T)) return BTX_E_WORKSPACE;
 
   GruKArgs pa = {};
   pa.x = x;
@@ -309,13 +311,21 @@ int btx_gru_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64
   sa.mu_w = hh->mu_w; sa.rho_w = hh->rho_w; sa.mu_b = hh->mu_b; sa.rho_b = hh->rho_b;
   sa.sample_dev = (const uint32_t*)hh->sample_idx_dev; sa.sample = hh->sample_idx; sa.layer = hh->layer_id;
   sa.K = H; sa.Kr = Hr;
-  sa.h0 = h0; sa.hs = hidden_seq;
+  sa.h0 = h0; sa.hs = hidden_seq; sa.sv = (float*)saved;
 
   hipStream_t st = (hipStream_t)stream;
   const int bb = (int)bblocks;
   hipError_t e;
   const bool bf = prec == BTX_PREC_BF16, xb = act_dtype == BTX_ACT_BF16;
-  if (kind == BTX_KIND_FLIPOUT) {
+  if (saved) {
+    if (kind == BTX_KIND_FLIPOUT) {
+      if (bf) e = xb ? launch_all<1, 1, __bf16, 1>(pa, sa, 1, bb, T, st) : launch_all<1, 1, float, 1>(pa, sa, 1, bb, T, st);
+      else    e = xb ? launch_all<1, 0, __bf16, 1>(pa, sa, 1, bb, T, st) : launch_all<1, 0, float, 1>(pa, sa, 1, bb, T, st);
+    } else {
+      if (bf) e = xb ? launch_all<0, 1, __bf16, 1>(pa, sa, 1, bb, T, st) : launch_all<0, 1, float, 1>(pa, sa, 1, bb, T, st);
+      else    e = xb ? launch_all<0, 0, __bf16, 1>(pa, sa, 1, bb, T, st) : launch_all<0, 0, float, 1>(pa, sa, 1, bb, T, st);
+    }
+  } else if (kind == BTX_KIND_FLIPOUT) {
     if (bf) e = xb ? launch_all<1, 1, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<1, 1, float>(pa, sa, lanes, bb, T, st);
     else    e = xb ? launch_all<1, 0, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<1, 0, float>(pa, sa, lanes, bb, T, st);
   } else {
@@ -323,6 +333,41 @@ int btx_gru_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64
     else    e = xb ? launch_all<0, 0, __bf16>(pa, sa, lanes, bb, T, st) : launch_all<0, 0, float>(pa, sa, lanes, bb, T, st);
   }
   return (int)e;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t btx_gru_workspace_bytes(int lanes, int B, int H, int T) {
+  if (lanes <= 0 || B <= 0 || H <= 0 || T <= 0) return 0;
+  return align256((size_t)lanes * T * B * 3 * H * sizeof(float));
+}
+
+size_t btx_gru_train_saved_bytes(int B, int H, int T) {
+  if (B <= 0 || H <= 0 || T <= 0) return 0;
+  return align256((size_t)T * B * 4 * H * sizeof(float));
+}
+
+size_t btx_gru_train_workspace_bytes(int B, int H, int T) {
+  // the backward's dG [T][B][4H] + the f32 z-carry [B][H]; the forward's projection Gi [T][B][3H] fits in the first part
+  if (B <= 0 || H <= 0 || T <= 0) return 0;
+  return align256((size_t)T * B * 4 * H * sizeof(float)) + align256((size_t)B * H * sizeof(float));
+}
+
+int btx_gru_fwd(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, int x_shared,
+                const void* h0, void* hidden_seq, const float* kl_ih, const float* kl_hh, float* kl_out, int lanes, int B,
+                int I, int H, int T, int act_dtype, int prec, void* workspace, size_t ws_bytes, void* stream) {
+  return gru_fwd_impl(kind, ih, hh, seed, x, x_shared, h0, hidden_seq, kl_ih, kl_hh, kl_out, lanes, B, I, H, T, act_dtype, prec,
+                      workspace, ws_bytes, nullptr, 0, stream);
+}
+
+int btx_gru_fwd_train(int kind, const BtxLstmLayer* ih, const BtxLstmLayer* hh, uint64_t seed, const void* x, const void* h0,
+                      void* hidden_seq, const float* kl_ih, const float* kl_hh, float* kl_out, int B, int I, int H, int T,
+                      int act_dtype, int prec, void* workspace, size_t ws_bytes, void* saved, size_t saved_bytes, void* stream) {
+  if (!saved) return BTX_E_NULL;
+  return gru_fwd_impl(kind, ih, hh, seed, x, 0, h0, hidden_seq, kl_ih, kl_hh, kl_out, 1, B, I, H, T, act_dtype, prec, workspace,
+                      ws_bytes, saved, saved_bytes, stream);
 }
 
 }  // extern "C"

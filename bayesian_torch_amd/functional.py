@@ -1194,6 +1194,92 @@ def gru_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, kl_t
     return hs, kl
 
 
+def _gru_train_args(fn, x, ih, hh, prec, h0):
+    """the checks gru_train_fwd_hip and gru_bwd_hip share; returns (act, prec, B, T, I, H, dense x, dense h0)"""
+    if not x.is_cuda:
+        raise _lib.BtxError("%s needs a CUDA (ROCm) tensor" % fn)
+    act = _lstm_act(x)
+    prec = prec or _PRECISION
+    if prec not in LSTM_PRECISIONS:
+        raise _lib.BtxError("the fused GRU sequence has no %s form" % prec)
+    B, T, I = x.shape
+    H = ih[0].shape[0] // 3
+    if ih[0].shape[0] != 3 * H or tuple(hh[0].shape) != (3 * H, H) or ih[0].shape[1] != I:
+        raise _lib.BtxError("GRU parameter shapes do not match the input (I=%d, H=%d)" % (I, H))
+    if h0 is not None:
+        if h0.shape != (B, H):
+            raise _lib.BtxError("h0 must be [B, H] = [%d, %d]" % (B, H))
+        h0 = h0.to(x.dtype).contiguous()
+    return act, prec, B, T, I, H, x.contiguous(), h0
+
+
+def gru_train_fwd_hip(kind, x, ih, hh, seed, prec=None, h0=None, kl_terms=None):
+    """The forward of a fused GRU training step (btx_gru_fwd_train, one lane): gru_hip's (hidden_seq, kl), bit for bit, plus
+    `saved` — the f32 planes r_t, z_t, n_t, gh_n,t gru_bwd_hip needs.  ih / hh as in gru_hip (sample_dev: one word); h0 [B, H] or
+    None.  Returns (hidden_seq, kl, saved)."""
+    L = _lib.lib()
+    act, prec, B, T, I, H, x, h0 = _gru_train_args("gru_train_fwd_hip", x, ih, hh, prec, h0)
+    li, lh = _lstm_layer(ih), _lstm_layer(hh)
+    hs = torch.empty(B, T, H, dtype=x.dtype, device=x.device)
+    need = L.btx_gru_train_workspace_bytes(B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    nsv = L.btx_gru_train_saved_bytes(B, H, T)
+    saved = torch.empty(nsv, dtype=torch.uint8, device=x.device)
+    kl = ki = kh = None
+    if kl_terms is not None:
+        ki, kh = (k.detach().to(torch.float32).reshape(1).contiguous() for k in kl_terms)
+        kl = torch.empty((), dtype=torch.float32, device=x.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(L.btx_gru_fwd_train(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                                   ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(), ptr(h0), hs.data_ptr(),
+                                   ptr(ki), ptr(kh), ptr(kl), B, I, H, T, act, _lib.PREC_CODE[prec], ws.data_ptr(), need,
+                                   saved.data_ptr(), nsv, torch.cuda.current_stream(x.device).cuda_stream))
+    return hs, kl, saved
+
+
+def gru_bwd_hip(kind, x, ih, hh, seed, hidden_seq, saved, d_hidden_seq=None, prec=None, h0=None, want_dx=True, want_dh0=False,
+                want_ih=True, want_hh=True):
+    """The backward through time of one gru_train_fwd_hip call with the same arguments (btx_gru_bwd).  d_hidden_seq [B, T, H] or
+    None.  Returns (dx, dh0, grads_ih, grads_hh); grads_* = (dmu_w, drho_w, dmu_b, drho_b) f32 (bias entries None without bias),
+    None where not wanted."""
+    L = _lib.lib()
+    act, prec, B, T, I, H, x, h0 = _gru_train_args("gru_bwd_hip", x, ih, hh, prec, h0)
+    li, lh = _lstm_layer(ih), _lstm_layer(hh)
+    dev = x.device
+    if tuple(hidden_seq.shape) != (B, T, H) or hidden_seq.dtype != x.dtype:
+        raise _lib.BtxError("hidden_seq must be the forward's [%d, %d, %d] %s tensor" % (B, T, H, x.dtype))
+    if saved.dtype != torch.uint8 or saved.numel() < L.btx_gru_train_saved_bytes(B, H, T):
+        raise _lib.BtxError("saved must be the byte buffer gru_train_fwd_hip returned")
+    hidden_seq, saved = hidden_seq.contiguous(), saved.contiguous()
+    d_hs = None
+    if d_hidden_seq is not None:
+        if tuple(d_hidden_seq.shape) != (B, T, H):
+            raise _lib.BtxError("d_hidden_seq must be [B, T, H] = [%d, %d, %d]" % (B, T, H))
+        d_hs = d_hidden_seq.to(x.dtype).contiguous()
+    dx = torch.empty(B, T, I, dtype=x.dtype, device=dev) if want_dx else None
+    dh0 = torch.empty(B, H, dtype=x.dtype, device=dev) if want_dh0 else None
+
+    def grads(p, want):
+        if not want:
+            return None, None
+        mu_w, mu_b = p[0], p[2]
+        g = (torch.empty_like(mu_w), torch.empty_like(mu_w), torch.empty_like(mu_b) if mu_b is not None else None,
+             torch.empty_like(mu_b) if mu_b is not None else None)
+        return g, _lib.LstmGrads(*(t.data_ptr() if t is not None else None for t in g))
+
+    gi, si = grads(ih, want_ih)
+    gh, sh = grads(hh, want_hh)
+    need = L.btx_gru_train_workspace_bytes(B, H, T)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    _lib.check(L.btx_gru_bwd(_lib.KIND_FLIPOUT if kind == _lib.KIND_FLIPOUT else _lib.KIND_REPARAM, ctypes.byref(li),
+                             ctypes.byref(lh), int(seed) & 0xFFFFFFFFFFFFFFFF, x.data_ptr(), ptr(h0), hidden_seq.data_ptr(),
+                             saved.data_ptr(), ptr(d_hs), ptr(dx), ptr(dh0), ctypes.byref(si) if si is not None else None,
+                             ctypes.byref(sh) if sh is not None else None, B, I, H, T, act, _lib.PREC_CODE[prec],
+                             ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream))
+    return dx, dh0, gi, gh
+
+
 def fill_eps_hip(n, device, seed, sample_idx, layer_id, rng_stream, sample_dev=None):
     """BTX-RNG v1 eps for a flat index space of n elements, as a flat f32 CUDA tensor.  sample_dev: the sample index lives in
     that device word (captured steps) and sample_idx is ignored."""

@@ -1081,7 +1081,7 @@ class _VariationalGRU(BaseVariationalLayer_):
 
     # fused_sequence (opt-in; models.fuse_model sets it): inference forwards on the GPU run the whole sequence as one
     # btx_gru_fwd call — 1 + T launches, lanes and graph capture included — with the noise and recurrence of the eager loop.
-    # There is no fused training path: forwards that need gradients take the eager loop, differentiated through the Linear layers.
+    # Forwards that need gradients take the eager loop, differentiated through the Linear layers, unless fused_training is on.
     @property
     def fused_sequence(self):
         return bool(self.__dict__.get("_btx_fused_sequence", False))
@@ -1092,6 +1092,63 @@ class _VariationalGRU(BaseVariationalLayer_):
         self.__dict__["_btx_fused_sequence"] = on
         for lin in (self.ih, self.hh):
             lin.__dict__["_btx_fused_seq"] = on  # rng.presample(): no tiles for the inner layers
+
+    # fused_training (opt-in; models.fuse_model(model, gru_training=True) sets it, and it implies fused_sequence): forwards that
+    # need gradients run btx_gru_fwd_train and their backward btx_gru_bwd (autograd.GruTrainFn) — eagerly and inside
+    # autograd.GraphedTrainStep.  Without it, training forwards take the eager loop.
+    @property
+    def fused_training(self):
+        return bool(self.__dict__.get("_btx_fused_training", False))
+
+    @fused_training.setter
+    def fused_training(self, on):
+        on = bool(on)
+        self.__dict__["_btx_fused_training"] = on
+        if on:
+            self.fused_sequence = True
+
+    def _fused_train_ok(self, X, h0):
+        """the conditions of the fused training path: fused_training, a forward that needs gradients, and _fused_ok's other
+        conditions; otherwise the eager loop runs"""
+        ih, hh = self.ih, self.hh
+        if not self.fused_training or not X.is_cuda or not ih._use_hip(X) or X.dim() != 3:
+            return False
+        if X.dtype not in (torch.float32, torch.bfloat16):
+            return False
+        grad = ih._needs_grad(X) or hh._needs_grad(None)
+        if h0 is not None:
+            if h0.dtype != X.dtype or h0.dim() != 2:
+                return False
+            grad = grad or (torch.is_grad_enabled() and h0.requires_grad)
+        if not grad:
+            return False
+        if ih._forward_hooks or ih._forward_pre_hooks or hh._forward_hooks or hh._forward_pre_hooks:
+            return False
+        prec = ih.precision or BF.get_precision()
+        return prec in BF.LSTM_PRECISIONS and (hh.precision or BF.get_precision()) == prec
+
+    def _forward_fused_train(self, X, h0, return_kl):
+        ih, hh = self.ih, self.hh
+        if ih._lanes()[0] > 1 or hh._lanes()[0] > 1:
+            raise _lib.BtxError("MC sample lanes are an inference feature: clear them before a training step")
+        steps = X.shape[1]
+
+        def meta(lin):
+            s = lin._btx_sample
+            lin.__dict__["_btx_sample"] = s + steps  # the counter of `steps` eager forwards
+            return lin._btx_layer_id, s, getattr(lin, "_btx_sample_dev", None)
+
+        kl_i, kl_h = ih.kl_loss(), hh.kl_loss()
+        kind = _lib.KIND_FLIPOUT if self._family == "flipout" else _lib.KIND_REPARAM
+        from .. import autograd as _ag
+        mu_i, rho_i = ih._w()
+        mu_h, rho_h = hh._w()
+        m = (kind, _rng.seed(), ih.precision or BF.get_precision(), meta(ih), meta(hh))
+        hidden_seq, kl = _ag.GruTrainFn.apply(m, X, h0, mu_i, rho_i, ih.mu_bias, ih.rho_bias, mu_h, rho_h, hh.mu_bias,
+                                              hh.rho_bias, kl_i, kl_h)
+        if return_kl:
+            return hidden_seq, hidden_seq[:, -1], kl
+        return hidden_seq, hidden_seq[:, -1]
 
     def _fused_ok(self, X, h0):
         """the conditions of the fused sequence path; otherwise the eager loop runs (and raises where it raises)"""
@@ -1141,6 +1198,8 @@ class _VariationalGRU(BaseVariationalLayer_):
             return_kl = False
         if self.fused_sequence and self._fused_ok(X, hidden_states):
             return self._forward_fused(X, hidden_states, return_kl)
+        if self.fused_training and self._fused_train_ok(X, hidden_states):
+            return self._forward_fused_train(X, hidden_states, return_kl)
         nb, steps, _ = X.size()
         hs = self.out_features
         for lin in (self.ih, self.hh):
@@ -1149,7 +1208,8 @@ class _VariationalGRU(BaseVariationalLayer_):
                 raise _lib.BtxError("GRU layers need a fresh MC sample index per time step, but this layer's index is pinned "
                                     "(MC sample lanes are set, or a live mc.GraphedMC / GraphedTrainStep keeps the index in a device "
                                     "word): set fused_sequence (models.fuse_model) for inference, or close() the graph / "
-                                    "rng.set_sample_lanes(model, None) and run eager forwards (mc.mc_forward(lanes=1))")
+                                    "rng.set_sample_lanes(model, None) and run eager forwards (mc.mc_forward(lanes=1)); to "
+                                    "train under a pinned index set fused_training (models.fuse_model(model, gru_training=True))")
         h_t = torch.zeros(nb, hs, device=X.device, dtype=X.dtype) if hidden_states is None else hidden_states
         cdt = torch.float32 if X.dtype in (torch.bfloat16, torch.float16) else X.dtype  # the dtype of the gate math
         hidden, kl = [], 0

@@ -682,8 +682,17 @@ class _FusedForward:
 
 def _lstm_training(model, on):
     if on:
+        from ..layers.base_variational_layer import _VariationalLSTM
         for m in model.modules():
-            if _is_lstm(m) and hasattr(type(m), "fused_training"):  # (a Bayesian GRU has no fused training path)
+            if isinstance(m, _VariationalLSTM):  # (a Bayesian GRU has a switch of its own: gru_training)
+                m.fused_training = True
+
+
+def _gru_training(model, on):
+    if on:
+        from ..layers.base_variational_layer import _VariationalGRU
+        for m in model.modules():
+            if isinstance(m, _VariationalGRU):
                 m.fused_training = True
 
 
@@ -694,7 +703,7 @@ def _lrt_training(model, on):
                 m.fused_training = True
 
 
-def fuse_model(model, lstm_training=False, lrt_training=False):
+def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=False):
     """Fold eval-mode BatchNorm, residual adds and ReLU / ReLU6 into the store of the variational layers of ANY model converted
     by dnn_to_bnn (its variational layers return a tensor), in place.  The model's forward is traced with torch.fx (variational
     layers and torch.nn modules as leaves) and every chain
@@ -720,16 +729,20 @@ def fuse_model(model, lstm_training=False, lrt_training=False):
     its training forwards on the GPU then run btx_lstm_fwd_train and their backward btx_lstm_bwd (also inside
     autograd.GraphedTrainStep); it changes neither the count nor what the default call does.  lrt_training=True does the same for
     every ...LocalReparameterization layer (and for no other layer): GPU forwards that need gradients run btx_lrt_fwd_train /
-    btx_lrt_bwd where functional.lrt_train_ok holds, the ATen composite elsewhere."""
+    btx_lrt_bwd where functional.lrt_train_ok holds, the ATen composite elsewhere.  gru_training=True sets fused_training on every
+    Bayesian GRU (and on no LSTM, as lstm_training=True sets it on no GRU): its training forwards on the GPU run btx_gru_fwd_train
+    and their backward btx_gru_bwd (also inside autograd.GraphedTrainStep)."""
     _lrt_training(model, lrt_training)
     if model.__dict__.get("_btx_fuse_model"):
         _lstm_training(model, lstm_training)
+        _gru_training(model, gru_training)
         return 0
     object.__setattr__(model, "_btx_fuse_model", True)
     lstms = [m for m in model.modules() if _is_lstm(m) and not m.fused_sequence]
     for m in lstms:
         m.fused_sequence = True
     _lstm_training(model, lstm_training)
+    _gru_training(model, gru_training)
     inl = set(map(id, _inlined(model)))
     hooked = [k for k, m in model.named_modules() if k and id(m) in inl and _hooked(m)]
     if hooked:  # (tracing would run the hooks on fx proxies, and the rewritten forward would skip them)

@@ -7,7 +7,13 @@ captured: its figure includes the gaps between its launches, which is what a use
 
 Every figure is device time between two events around a region of back-to-back calls, divided by the MC samples in the region: the
 median over the settled (second) half of `--regions` regions, with that half's spread (max - min) / median.  f32 activations;
-`prec` is the contraction precision.  Prints one JSON line per row and writes the table to --out."""
+`prec` is the contraction precision.  Prints one JSON line per row and writes the table to --out.
+
+    python tools/gru_bench.py --train [--types ...] [--precs ...] [--shapes 256x512x64x64] [--out FILE]
+
+--train times one training step instead (forward + cross-entropy + KL + backward), ms per step: the eager per-step
+loop differentiated op by op, the fused training path (fuse_model(gru_training=True): btx_gru_fwd_train + btx_gru_bwd) issued from
+Python, and the same fused step replayed by autograd.GraphedTrainStep.  The three alternate inside every region."""
 import argparse
 import json
 import os
@@ -53,8 +59,83 @@ def _regions(fn, calls, regions, samples_per_call):
     return med, (max(half) - min(half)) / med
 
 
+def _train_rows(a, bt, dev):
+    """the --train table: ms per training step of the three routes, timed in alternation (one region of each per round)"""
+    import torch.nn.functional as F
+    from bayesian_torch_amd.autograd import GraphedTrainStep
+    from bayesian_torch_amd.models import fuse_model
+    from bayesian_torch_amd.models.dnn_to_bnn import get_kl_loss
+    lines = ["%-19s %-5s %-16s %13s %8s %13s %8s %13s %8s %9s %9s" % (
+        "type", "prec", "I x H x B x T", "eager ms", "spread", "fused ms", "spread", "graphed ms", "spread", "fused x", "graphed x")]
+    for shape in a.shapes.split(","):
+        I, H, B, T = (int(v) for v in shape.split("x"))
+        for typ in a.types.split(","):
+            for prec in a.precs.split(","):
+                bt.set_precision(prec)
+                x = torch.randn(B, T, I, device=dev)
+                y = torch.randint(0, 10, (B,), device=dev)
+                models = []
+                for fused in (False, True, True):
+                    torch.manual_seed(0)
+                    m = SeqNet(I, H)
+                    bt.dnn_to_bnn(m, dict(PRIOR, type=typ))
+                    m = m.to(dev).train()
+                    if fused:
+                        fuse_model(m, gru_training=True)
+                    models.append(m)
+
+                def step(m, count=[0]):
+                    count[0] += 1
+                    for p in m.parameters():
+                        p.grad = None
+                    bt.set_sample_index(m, count[0] * T)
+                    loss = F.cross_entropy(m(x).float(), y) + get_kl_loss(m) / B
+                    loss.backward()
+                g = GraphedTrainStep(models[2], x, y)
+                fns = dict(eager=lambda: step(models[0]), fused=lambda: step(models[1]), graphed=lambda: g.run(7))
+                ms = {k: [] for k in fns}
+                for k, fn in fns.items():  # warm-up of every route at this shape
+                    fn()
+                torch.cuda.synchronize()
+                for _ in range(a.regions):
+                    for k, fn in fns.items():
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        for _ in range(a.calls):
+                            fn()
+                        e1.record()
+                        e1.synchronize()
+                        ms[k].append(e0.elapsed_time(e1) / a.calls)
+                g.close()
+                res = dict(mode="train", type=typ, prec=prec, I=I, H=H, B=B, T=T)
+                for k, v in ms.items():
+                    half = v[len(v) // 2:]
+                    res[k + "_ms"] = statistics.median(half)
+                    res[k + "_spread"] = (max(half) - min(half)) / res[k + "_ms"]
+                res["speedup_fused"] = res["eager_ms"] / res["fused_ms"]
+                res["speedup_graphed"] = res["eager_ms"] / res["graphed_ms"]
+                print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+                lines.append("%-19s %-5s %-16s %13.4f %7.1f%% %13.4f %7.1f%% %13.4f %7.1f%% %8.2fx %8.2fx" % (
+                    typ, prec, "%d x %d x %d x %d" % (I, H, B, T), res["eager_ms"], 100 * res["eager_spread"], res["fused_ms"],
+                    100 * res["fused_spread"], res["graphed_ms"], 100 * res["graphed_spread"], res["speedup_fused"],
+                    res["speedup_graphed"]))
+    bt.set_precision("f32")
+    table = "\n".join(lines)
+    print(table)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("tools/gru_bench.py --train on an MI355X: device ms per training step (forward + loss + backward; events around regions\n"
+                    "of %d back-to-back steps, the three routes alternating; median of the settled half of %d regions, spread = (max - min) /\n"
+                    "median of that half).  eager = the per-step loop differentiated op by op; fused = fused_training issued from Python;\n"
+                    "graphed = the fused step replayed by autograd.GraphedTrainStep; x = eager / that route.\n\n" % (a.calls, a.regions))
+            f.write(table + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="time a training step (forward + backward) instead of MC inference")
+    ap.add_argument("--calls", type=int, default=8, help="--train: steps per timed region")
     ap.add_argument("--types", default="Flipout,Reparameterization")
     ap.add_argument("--precs", default="f32,bf16")
     ap.add_argument("--shapes", default="256x512x64x64,32x64x8x16", help="IxHxBxT, comma separated")
@@ -67,6 +148,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("gru_bench needs a GPU: nothing is measured without one")
     dev = torch.device("cuda:0")
+    if a.train:
+        return _train_rows(a, bt, dev)
     lines = ["%-19s %-5s %-16s %14s %8s %14s %8s %14s %8s %9s %9s" % (
         "type", "prec", "I x H x B x T", "eager ms/smp", "spread", "fused L1 ms", "spread", "fused L8 ms", "spread", "L1 x", "L8 x")]
     for shape in a.shapes.split(","):
