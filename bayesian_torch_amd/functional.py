@@ -1194,6 +1194,66 @@ def gru_hip(kind, x, ih, hh, seed, prec=None, lanes=1, batch=None, h0=None, kl_t
     return hs, kl
 
 
+ATTN_PRECISIONS = ("f32", "bf16")  # btx_attn_fwd's forms
+ATTN_HEAD_DIMS = (32, 64, 128)
+
+
+def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
+    """The attention core softmax(scale * q k^T + masks) v of every (row, head) in ONE launch (btx_attn_fwd), scale =
+    head_dim ** -0.5.  qkv: one packed tensor [rows, T, 3E] (q | k | v along the last axis, an in-projection's output) or a tuple
+    (q [rows, Tq, E], k [rows, Tk, E], v [rows, Tk, E]); f32 or bf16.  The kernel is told each tensor's (row, token) strides, so a
+    packed buffer, a `[T, rows, E].transpose(0, 1)` view and tensors off the 16-byte grid are read where they lie; only a tensor whose
+    last axis is not contiguous is copied first (one stream-ordered copy).  key_padding_mask: [B, Tk] bool / uint8 (non-zero = masked)
+    with B dividing rows: row r reads mask row r % B (MC lanes share the batch's mask).  causal: key j is masked for query i when
+    j > i.  A query whose keys are all masked gives zeros.  out: a [rows, Tq, E] tensor of the input's dtype to write into (any
+    row / token strides, last axis contiguous, no overlap); returned.  No workspace, no allocation beyond `out`: capturable."""
+    L = _lib.lib()
+    if isinstance(qkv, (tuple, list)):
+        q, k, v = qkv
+    else:
+        if qkv.dim() != 3 or qkv.shape[-1] % 3:
+            raise _lib.BtxError("attn_hip: a packed qkv must be [rows, T, 3E], got %s" % (tuple(qkv.shape),))
+        E = qkv.shape[-1] // 3
+        q, k, v = qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:]
+    if not q.is_cuda:
+        raise _lib.BtxError("attn_hip needs CUDA (ROCm) tensors")
+    act = _lstm_act(q)
+    prec = prec or _PRECISION
+    if prec not in ATTN_PRECISIONS:
+        raise _lib.BtxError("the fused attention core has no %s form" % prec)
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
+        raise _lib.BtxError("attn_hip: q [rows, Tq, E] and k, v [rows, Tk, E] expected, got %s, %s, %s"
+                            % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
+        raise _lib.BtxError("attn_hip: q, k and v must share dtype and device")
+    rows, Tq, E = q.shape
+    Tk, heads = k.shape[1], int(heads)
+    if heads < 1 or E % heads or E // heads not in ATTN_HEAD_DIMS:
+        raise _lib.BtxError("attn_hip: head_dim = E / heads must be one of %s, got E=%d, heads=%d" % (ATTN_HEAD_DIMS, E, heads))
+    if rows < 1 or Tq < 1 or Tk < 1:
+        raise _lib.BtxError("attn_hip: empty input %s" % (tuple(q.shape),))
+    # DESIGN.md §15.1: the (row, token) strides are passed; a view whose last axis is not contiguous is densified
+    q, k, v = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k, v))
+    if out is None:
+        out = torch.empty(rows, Tq, E, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (rows, Tq, E) or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1:
+        raise _lib.BtxError("out must be a [%d, %d, %d] %s tensor on the input's device with a contiguous last axis" % (rows, Tq, E, q.dtype))
+    kp, pad_rows = None, 1
+    if key_padding_mask is not None:
+        kp = key_padding_mask
+        if kp.dtype not in (torch.bool, torch.uint8) or kp.dim() != 2 or kp.shape[1] != Tk or kp.shape[0] < 1 or rows % kp.shape[0]:
+            raise _lib.BtxError("key_padding_mask must be a bool / uint8 [B, Tk = %d] tensor with B dividing rows = %d, got %s %s"
+                                % (Tk, rows, kp.dtype, tuple(kp.shape)))
+        kp = kp.to(device=q.device).contiguous()
+        kp = kp.view(torch.uint8) if kp.dtype == torch.bool else kp
+        pad_rows = kp.shape[0]
+    strides = (ctypes.c_int64 * 8)(*(int(t.stride(i)) for t in (q, k, v, out) for i in (0, 1)))
+    _lib.check(L.btx_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), rows, Tq, Tk, heads, E // heads, strides,
+                              kp.data_ptr() if kp is not None else None, pad_rows, 1 if causal else 0, float(E // heads) ** -0.5,
+                              act, _lib.PREC_CODE[prec], torch.cuda.current_stream(q.device).cuda_stream))
+    return out
+
+
 def _gru_train_args(fn, x, ih, hh, prec, h0):
     """the checks gru_train_fwd_hip and gru_bwd_hip share; returns (act, prec, B, T, I, H, dense x, dense h0)"""
     if not x.is_cuda:

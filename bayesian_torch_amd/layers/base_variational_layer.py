@@ -1234,3 +1234,154 @@ class _VariationalGRU(BaseVariationalLayer_):
         if return_kl:
             return hidden_seq, h_t, kl
         return hidden_seq, h_t
+
+
+class _VariationalMHA(BaseVariationalLayer_):
+    """Multi-head self-attention on two Bayesian Linear layers (not in the reference): `in_proj` (E -> 3E, rows in
+    torch's order q | k | v, so in_proj_weight / in_proj_bias of an nn.MultiheadAttention copy into it unchanged) and `out_proj`
+    (E -> E), with the attention core between them:
+
+        qkv = in_proj(x)    s = scale * q k^T (+ masks: -inf)    p = softmax(s)    out = out_proj(merge_heads(p v))
+
+    forward() has nn.MultiheadAttention's signature and returns (out, weights or None[, kl]), kl = in_proj.kl_loss() +
+    out_proj.kl_loss().  Self-attention only: query, key and value must be the same tensor.  The scores and the softmax run in float32
+    for bfloat16 / float16 inputs and in the input's dtype otherwise.  The one deviation from torch: a query whose keys are all
+    masked gives zeros where torch gives NaN.  key_padding_mask: [batch, T] bool (True = masked) or additive float; attn_mask:
+    [T, T] bool or additive float; is_causal=True without an attn_mask means the causal mask, with one it vouches (as in torch) that
+    the mask IS the causal one.  `_linear_cls` is the Linear class of the family.
+
+    The attributes embed_dim, num_heads, head_dim, batch_first, in_proj_bias (None) and _qkv_same_embed_dim (False) are what
+    nn.TransformerEncoderLayer / nn.TransformerEncoder probe before their fused "fast path": with these values they skip it and call
+    this module like any other."""
+
+    _linear_cls = None
+    _qkv_same_embed_dim = False
+    in_proj_bias = None
+    # models.get_kl_loss: kl_loss() of this module is the sum over its children, which the walk meets on their own
+    _btx_kl_composite = True
+
+    def __init__(self, embed_dim, num_heads, bias=True, batch_first=False, prior_mean=0, prior_variance=1, posterior_mu_init=0,
+                 posterior_rho_init=-3.0):
+        super().__init__()
+        if embed_dim <= 0 or num_heads <= 0 or embed_dim % num_heads:
+            raise ValueError("embed_dim (%r) must be a positive multiple of num_heads (%r)" % (embed_dim, num_heads))
+        self.embed_dim, self.num_heads, self.head_dim = embed_dim, num_heads, embed_dim // num_heads
+        self.batch_first, self.bias = batch_first, bias
+        self.prior_mean, self.prior_variance = prior_mean, prior_variance
+        kw = dict(prior_mean=prior_mean, prior_variance=prior_variance, posterior_mu_init=posterior_mu_init,
+                  posterior_rho_init=posterior_rho_init, bias=bias)
+        self.in_proj = self._linear_cls(in_features=embed_dim, out_features=3 * embed_dim, **kw)
+        self.out_proj = self._linear_cls(in_features=embed_dim, out_features=embed_dim, **kw)
+
+    def set_prior(self, prior, kl_samples=1):
+        # both children are ordinary layers evaluated once per forward: any prior of priors.py works (unlike on the LSTM / GRU)
+        self.in_proj.set_prior(prior, kl_samples)
+        self.out_proj.set_prior(prior, kl_samples)
+        return self
+
+    def kl_loss(self):
+        return self.in_proj.kl_loss() + self.out_proj.kl_loss()
+
+    # fused_attention (opt-in; models.fuse_model sets it): inference forwards on the GPU run the attention core as ONE btx_attn_fwd
+    # launch that reads q, k and v in place from in_proj's output and writes the layout out_proj consumes.  Both paths call in_proj
+    # and out_proj identically: noise, sample counters, pre-sampling, MC lanes and graph capture are those of two Linear layers.
+    @property
+    def fused_attention(self):
+        return bool(self.__dict__.get("_btx_fused_attention", False))
+
+    @fused_attention.setter
+    def fused_attention(self, on):
+        self.__dict__["_btx_fused_attention"] = bool(on)
+
+    def _fused_ok(self, x, key_padding_mask, need_weights, attn_mask, is_causal):
+        """the conditions of the fused core; anything else takes the composite"""
+        ip, op = self.in_proj, self.out_proj
+        if not self.fused_attention or not x.is_cuda or not ip._use_hip(x) or x.dim() != 3 or need_weights:
+            return False
+        if x.dtype not in (torch.float32, torch.bfloat16) or ip._needs_grad(x) or op._needs_grad(None):
+            return False
+        if self.head_dim not in BF.ATTN_HEAD_DIMS:
+            return False
+        if attn_mask is not None and not is_causal:
+            return False  # a general mask; with is_causal the caller vouches that it is the causal one (torch's contract)
+        if key_padding_mask is not None and key_padding_mask.dtype != torch.bool:
+            return False  # an additive float mask may hold finite values: only the composite can add them
+        if ip._forward_hooks or ip._forward_pre_hooks or op._forward_hooks or op._forward_pre_hooks:
+            return False
+        return (ip.precision or BF.get_precision()) in BF.ATTN_PRECISIONS
+
+    def _core(self, qkv, key_padding_mask, need_weights, attn_mask, average_attn_weights, is_causal):
+        """the eager composite between the projections: qkv [rows, T, 3E] (any strides) -> (merged heads [rows, T, E], weights)"""
+        R, T, _ = qkv.shape
+        H, D = self.num_heads, self.head_dim
+        cdt = torch.float32 if qkv.dtype in (torch.bfloat16, torch.float16) else qkv.dtype
+        q, k, v = qkv.reshape(R, T, 3, H, D).permute(2, 0, 3, 1, 4).to(cdt)  # [rows, heads, T, D] each
+        s = (q @ k.transpose(-1, -2)) * (D ** -0.5)
+
+        def apply(s, m):
+            return s.masked_fill(m, float("-inf")) if m.dtype == torch.bool else s + m.to(cdt)
+
+        if attn_mask is not None:
+            if tuple(attn_mask.shape) != (T, T):
+                raise _lib.BtxError("attn_mask must be [T, T] = [%d, %d], got %s" % (T, T, tuple(attn_mask.shape)))
+            s = apply(s, attn_mask)
+        elif is_causal:
+            s = apply(s, torch.ones(T, T, dtype=torch.bool, device=s.device).triu(1))
+        if key_padding_mask is not None:
+            m = key_padding_mask
+            if m.dim() != 2 or m.shape[1] != T or R % m.shape[0]:
+                raise _lib.BtxError("key_padding_mask must be [batch, T] with batch dividing the rows %d, got %s" % (R, tuple(m.shape)))
+            s = apply(s, m.repeat(R // m.shape[0], 1)[:, None, None, :])  # MC lanes share the batch's mask (lane l's rows at l * B)
+        dead = s.amax(-1, keepdim=True) == float("-inf")  # every key masked: zeros (torch: NaN)
+        p = torch.softmax(s.masked_fill(dead, 0.0), dim=-1).masked_fill(dead, 0.0)
+        o = (p @ v).to(qkv.dtype).transpose(1, 2).reshape(R, T, H * D)
+        w = None
+        if need_weights:
+            w = p.mean(1) if average_attn_weights else p
+        return o, w
+
+    def forward(self, query, key, value, key_padding_mask=None, need_weights=False, attn_mask=None, average_attn_weights=True,
+                is_causal=False, return_kl=True):
+        if self.dnn_to_bnn_flag:
+            return_kl = False
+        if key is not query or value is not query:
+            raise _lib.BtxError("%s: cross-attention is not supported (query, key and value must be the same tensor: self-attention)"
+                                % type(self).__name__)
+        if query.dim() != 3:
+            raise _lib.BtxError("%s: the input must be 3-D (%s), got %s" % (
+                type(self).__name__, "[batch, T, E]" if self.batch_first else "[T, batch, E]", tuple(query.shape)))
+        if not self.batch_first and query.is_cuda and self.in_proj._lanes()[0] > 1:
+            raise _lib.BtxError("%s: MC sample lanes need batch_first=True (the lanes are stacked on axis 0, which is the token axis "
+                                "of a [T, batch, E] input)" % type(self).__name__)
+        fused = self._fused_ok(query, key_padding_mask, need_weights, attn_mask, is_causal)
+        hip = query.is_cuda and self.in_proj._use_hip(query)
+        kl = None
+        if return_kl:
+            if hip:
+                qkv = self.in_proj(query, return_kl=False)
+                kl = self.in_proj.kl_loss()
+            else:
+                qkv, kl = self.in_proj(query)
+        else:
+            qkv = self.in_proj(query, return_kl=False)
+        rows_first = qkv if self.batch_first else qkv.transpose(0, 1)  # [rows, T, 3E] as a view
+        w = None
+        if fused:
+            R, T, _ = rows_first.shape
+            o = torch.empty((R, T, self.embed_dim) if self.batch_first else (T, R, self.embed_dim), dtype=qkv.dtype, device=qkv.device)
+            BF.attn_hip(rows_first, self.num_heads, key_padding_mask, causal=bool(is_causal or attn_mask is not None),
+                        prec=self.in_proj.precision or BF.get_precision(), out=o if self.batch_first else o.transpose(0, 1))
+        else:
+            o, w = self._core(rows_first, key_padding_mask, need_weights, attn_mask, average_attn_weights, is_causal)
+            if not self.batch_first:
+                o = o.transpose(0, 1)
+        if return_kl and not hip:
+            out, kl_o = self.out_proj(o)
+            kl = kl + kl_o
+        else:
+            out = self.out_proj(o, return_kl=False)
+            if return_kl:
+                kl = kl + self.out_proj.kl_loss()
+        if return_kl:
+            return out, w, kl
+        return out, w

@@ -119,6 +119,8 @@ def bnn_to_qbnn(m, fuse_conv_bn=False, flipout=False):
             setattr(m, name, qbnn_linear_layer(child) if child._nd == 0 else qbnn_conv_layer(child))
         elif hasattr(child, "ih") and hasattr(child, "hh") and hasattr(child, "fused_sequence"):
             continue  # a Bayesian LSTM stays whole: its inner Linear layers are part of its recurrence
+        elif hasattr(child, "fused_attention") and hasattr(child, "in_proj") and hasattr(child, "out_proj"):
+            continue  # a Bayesian multi-head attention stays whole: there is no INT8 attention core between quantized projections
         elif child._modules:
             bnn_to_qbnn(child, fuse_conv_bn=fuse_conv_bn, flipout=flipout)
     return

@@ -6,7 +6,9 @@ looked up as `<ClassName><params["type"]>` in `bayesian_torch_amd.layers`; the r
 prior_mu, prior_sigma, posterior_mu_init, posterior_rho_init, type, moped_enable (KeyError if absent), moped_delta;
 `output_padding` / `padding_mode` are NOT forwarded; converted layers get `dnn_to_bnn_flag = True` (forward returns
 only `out`).  nn.LSTM children become LSTM<type> (two Bayesian Linear layers per time step).  Beyond the reference: a one-layer,
-unidirectional, batch-first nn.GRU becomes GRU<type>; any other nn.GRU is refused by name.
+unidirectional, batch-first nn.GRU becomes GRU<type>; any other nn.GRU is refused by name.  An nn.MultiheadAttention
+(self-attention: one packed in-projection, no attention dropout, no bias_k / add_zero_attn) becomes MultiheadAttention<type>
+ as a whole, MOPED included; any other one is refused by name.
 Beyond the reference: the optional keys "prior" (a bayesian_torch_amd.priors prior) and "kl_samples" install a non-Gaussian weight
 prior on every converted layer (layer.set_prior); without them nothing changes.
 """
@@ -93,6 +95,33 @@ def bnn_gru_layer(params, d, name="GRU"):
     return bnn_layer
 
 
+def bnn_mha_layer(params, d, name="MultiheadAttention"):
+    """nn.MultiheadAttention(E, heads) -> MultiheadAttention<type>(E, heads): the packed in-projection becomes the Bayesian Linear
+    `in_proj` (E -> 3E, rows q | k | v), out_proj the Bayesian Linear `out_proj`.  The Bayesian layer is self-attention without
+    attention dropout: every other configuration is refused with the module and the option in the message.  MOPED is well defined
+    (both projections are Linear layers): in_proj_weight / in_proj_bias and out_proj.weight / out_proj.bias become mu, get_rho of
+    them rho."""
+    for opt, got, want in (("kdim", d.kdim, d.embed_dim), ("vdim", d.vdim, d.embed_dim), ("dropout", d.dropout, 0),
+                           ("add_bias_kv", d.bias_k is not None, False), ("add_zero_attn", d.add_zero_attn, False)):
+        if got != want:
+            raise ValueError("dnn_to_bnn: cannot convert the MultiheadAttention %r: %s=%r is not supported (the Bayesian attention "
+                             "needs %s=%r)" % (name, opt, got, opt, want))
+    layer_fn = _layer_class(params, d)
+    bnn_layer = layer_fn(embed_dim=d.embed_dim, num_heads=d.num_heads, bias=d.in_proj_bias is not None, batch_first=d.batch_first,
+                         prior_mean=params["prior_mu"], prior_variance=params["prior_sigma"],
+                         posterior_mu_init=params["posterior_mu_init"], posterior_rho_init=params["posterior_rho_init"])
+    if params["moped_enable"]:
+        delta = params["moped_delta"]
+        for lin, w, b in ((bnn_layer.in_proj, d.in_proj_weight, d.in_proj_bias), (bnn_layer.out_proj, d.out_proj.weight, d.out_proj.bias)):
+            lin.mu_weight.data.copy_(w.data)
+            lin.rho_weight.data.copy_(get_rho(w.data, delta))
+            if lin.mu_bias is not None:
+                lin.mu_bias.data.copy_(b.data)
+                lin.rho_bias.data.copy_(get_rho(b.data, delta))
+    bnn_layer.dnn_to_bnn_flag = True
+    return bnn_layer
+
+
 def _with_prior(bnn_layer, params):
     if "prior" in params:
         bnn_layer.set_prior(params["prior"], params.get("kl_samples", 1))
@@ -104,7 +133,10 @@ def dnn_to_bnn(m, bnn_prior_parameters):
         if child is None:
             continue
         cname = child.__class__.__name__
-        if child._modules:
+        if "MultiheadAttention" in cname:  # before the recursion: its out_proj is a child, its in-projection a bare parameter
+            setattr(m, name, _with_prior(bnn_mha_layer(bnn_prior_parameters, child, name), bnn_prior_parameters)
+                    .to(child.out_proj.weight.device))
+        elif child._modules:
             dnn_to_bnn(child, bnn_prior_parameters)
         elif "Conv" in cname:
             setattr(m, name, _with_prior(bnn_conv_layer(bnn_prior_parameters, child), bnn_prior_parameters).to(child.weight.device))

@@ -41,6 +41,12 @@ def _is_lstm(m):
     return hasattr(m, "fused_sequence") and hasattr(m, "ih") and hasattr(m, "hh")
 
 
+def _is_mha(m):
+    """a Bayesian multi-head attention: a leaf of the trace (its forward takes three tensors and masks), never an epilogue site;
+    fuse_model switches it to its fused attention core (fused_attention)"""
+    return hasattr(m, "fused_attention") and hasattr(m, "in_proj") and hasattr(m, "out_proj")
+
+
 # ---- "is this module's forward the dataflow the fused forms assume?" — decided by RUNNING it, not by its class name -------------
 # Attribute names prove nothing about a forward (a pre-activation block has conv1 / bn1 / conv2 / bn2 / downsample too), and a
 # class-name list stops at the classes it knows.  A deep copy of the module on the CPU, in eval mode, is run twice on a small random
@@ -540,7 +546,7 @@ class _Tracer(torch.fx.Tracer):
 
     def is_leaf_module(self, m, qualname):
         # (an MCDropout is a leaf and no epilogue site: it stays where it is and nothing is folded across it)
-        return _is_var(m) or _is_lstm(m) or _is_q8(m) or getattr(m, "_btx_dropout", False) or super().is_leaf_module(m, qualname)
+        return _is_var(m) or _is_lstm(m) or _is_mha(m) or _is_q8(m) or getattr(m, "_btx_dropout", False) or super().is_leaf_module(m, qualname)
 
 
 def _inlined(module):
@@ -724,7 +730,9 @@ def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=Fals
     A model whose forward cannot be traced (control flow on tensor values), or whose inlined modules have forward hooks at
     fusing time, gets the folding inside its nn.Sequential containers only (consecutive children V, BN, activation), with one
     warning.  Every Bayesian LSTM (LSTMReparameterization / LSTMFlipout) and GRU (GRUReparameterization / GRUFlipout) is a leaf of the
-    trace and gets fused_sequence = True: its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd / btx_gru_fwd call.  Returns the number of fused sites plus
+    trace and gets fused_sequence = True: its inference forwards on the GPU run the whole sequence in one btx_lstm_fwd / btx_gru_fwd call.  Every
+    Bayesian multi-head attention (MultiheadAttentionReparameterization / MultiheadAttentionFlipout) is a leaf as well and gets
+    fused_attention = True: the attention core of its inference forwards on the GPU is one btx_attn_fwd launch (it counts like an LSTM).  Returns the number of fused sites plus
     the number of LSTMs switched; a second call returns 0.  lstm_training=True also sets fused_training on every Bayesian LSTM:
     its training forwards on the GPU then run btx_lstm_fwd_train and their backward btx_lstm_bwd (also inside
     autograd.GraphedTrainStep); it changes neither the count nor what the default call does.  lrt_training=True does the same for
@@ -741,6 +749,10 @@ def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=Fals
     lstms = [m for m in model.modules() if _is_lstm(m) and not m.fused_sequence]
     for m in lstms:
         m.fused_sequence = True
+    mhas = [m for m in model.modules() if _is_mha(m) and not m.fused_attention]
+    for m in mhas:  # counted with the LSTMs: one switched module each
+        m.fused_attention = True
+    lstms = lstms + mhas
     _lstm_training(model, lstm_training)
     _gru_training(model, gru_training)
     inl = set(map(id, _inlined(model)))

@@ -1,0 +1,160 @@
+"""GPU time of the fused attention core (btx_attn_fwd) against the other routes of the same build, and of a whole
+converted nn.TransformerEncoderLayer forward with and without it.
+
+    python tools/attn_bench.py [--regions 10] [--calls 20] [--out profiles/attn_bench.txt]
+
+Core: every route is captured into a graph of its own and the routes ALTERNATE inside every round; a figure is device time between two
+events around `--calls` back-to-back replays, per replay: the median over the settled (second) half of `--regions` rounds, with that
+half's spread (max - min) / median.
+  fused      functional.attn_hip on the packed in-projection output [rows, T, 3E]: q, k, v read in place, [rows, T, E] written
+  composite  the layer's eager core on the same tensor: head split, QK^T, softmax, PV, merge (transposes included)
+  sdpa       F.scaled_dot_product_attention fed pre-transposed contiguous [rows, heads, T, D] heads (no transposes counted)
+TFLOP/s = 4 rows heads Tq Tk D (half of it under the causal mask) over the fused time; "of peak" is that rate over the 2500 TFLOP/s
+dense bf16 MFMA peak of an MI355X (printed for the bf16 rows only).
+Layer: mc.GraphedMC replays (one MC sample each) of embed -> converted TransformerEncoderLayer -> first token -> head, the model fused by
+fuse_model against the same model unfused, alternating."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PRIOR = dict(prior_mu=0.0, prior_sigma=1.0, posterior_mu_init=0.0, posterior_rho_init=-3.0, moped_enable=False, moped_delta=0.5)
+BF16_PEAK = 2500e12
+# (name, rows, T, heads, D, causal)
+SHAPES = [("vit-b", 64, 197, 12, 64, False), ("vit-b x8 lanes", 512, 197, 12, 64, False), ("T1024 D64", 8, 1024, 12, 64, False),
+          ("T1024 D128", 8, 1024, 8, 128, False), ("T1024 D64 causal", 8, 1024, 12, 64, True)]
+
+
+def _alternate(fns, calls, regions):
+    """{name: (median ms per call over the settled half, spread)} with the routes alternating inside every round"""
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(regions):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(calls):
+                fn()
+            b.record()
+            b.synchronize()
+            ms[k].append(a.elapsed_time(b) / calls)
+    out = {}
+    for k, v in ms.items():
+        half = v[len(v) // 2:]
+        med = statistics.median(half)
+        out[k] = (med, (max(half) - min(half)) / med)
+    return out
+
+
+def _graphed(fn):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s), torch.no_grad():
+        for _ in range(2):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g), torch.no_grad():
+        fn()
+    return g.replay
+
+
+class Net(nn.Module):
+    def __init__(self, e, heads, ff):
+        super().__init__()
+        self.embed = nn.Linear(e, e)
+        self.enc = nn.TransformerEncoderLayer(e, heads, ff, dropout=0.0, batch_first=True)
+        self.head = nn.Linear(e, 10)
+
+    def forward(self, x):
+        return self.head(self.enc(self.embed(x))[:, 0])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--regions", type=int, default=10)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import bayesian_torch_amd as bt
+    from bayesian_torch_amd import functional as BF, layers as L, mc
+    from bayesian_torch_amd.models import fuse_model
+    if not torch.cuda.is_available():
+        raise SystemExit("attn_bench needs a GPU: nothing is measured without one")
+    dev = torch.device("cuda:0")
+    lines = ["%-17s %-5s %11s %7s %13s %7s %10s %7s %9s %8s %8s %8s" % (
+        "core", "dtype", "fused ms", "spread", "composite ms", "spread", "sdpa ms", "spread", "comp / f", "sdpa / f", "TFLOP/s", "of peak")]
+    for name, R, T, H, D, causal in SHAPES:
+        for dt, prec in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
+            torch.manual_seed(0)
+            layer = L.MultiheadAttentionReparameterization(H * D, H, batch_first=True)
+            qkv = (0.5 * torch.randn(R, T, 3 * H * D, device=dev)).to(dt)
+            heads = [t.reshape(R, T, H, D).transpose(1, 2).contiguous() for t in qkv.chunk(3, dim=-1)]
+            fns = dict(fused=_graphed(lambda: BF.attn_hip(qkv, H, causal=causal, prec=prec)),
+                       composite=_graphed(lambda: layer._core(qkv, None, False, None, True, causal)),
+                       sdpa=_graphed(lambda: F.scaled_dot_product_attention(*heads, is_causal=causal)))
+            r = _alternate(fns, a.calls, a.regions)
+            flops = 4.0 * R * H * T * T * D * (0.5 if causal else 1.0)
+            tf = flops / (r["fused"][0] * 1e-3) / 1e12
+            res = dict(core=name, dtype=prec, rows=R, T=T, heads=H, D=D, causal=causal, tflops=tf)
+            for k, (med, spr) in r.items():
+                res[k + "_ms"], res[k + "_spread"] = med, spr
+            print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+            lines.append("%-17s %-5s %11.4f %6.1f%% %13.4f %6.1f%% %10.4f %6.1f%% %8.2fx %7.2fx %8.1f %8s" % (
+                name, prec, r["fused"][0], 100 * r["fused"][1], r["composite"][0], 100 * r["composite"][1], r["sdpa"][0],
+                100 * r["sdpa"][1], r["composite"][0] / r["fused"][0], r["sdpa"][0] / r["fused"][0], tf,
+                "%.1f%%" % (100 * tf * 1e12 / BF16_PEAK) if prec == "bf16" else "-"))
+            del fns
+    lines.append("")
+    lines.append("%-34s %-5s %11s %7s %13s %7s %9s" % ("layer (embed, encoder layer, head)", "prec", "fused ms", "spread", "unfused ms", "spread", "unf / f"))
+    for name, B, T, E, H, FF in (("vit-b 64 x 197 x 768", 64, 197, 768, 12, 3072),):
+        for kind in ("Reparameterization", "Flipout"):
+            for prec in ("bf16", "f32"):
+                bt.set_precision(prec)
+                x = torch.randn(B, T, E, device=dev)
+                graphs = {}
+                for route in ("fused", "unfused"):
+                    torch.manual_seed(0)
+                    m = Net(E, H, FF)
+                    bt.dnn_to_bnn(m, dict(PRIOR, type=kind))
+                    m = m.to(dev).eval()
+                    if route == "fused":
+                        fuse_model(m)
+                    graphs[route] = mc.GraphedMC(m, x.clone(), lanes=1)
+                r = _alternate({k: (lambda g=g: g.run(0)) for k, g in graphs.items()}, max(2, a.calls // 4), a.regions)
+                for g in graphs.values():
+                    g.close()
+                res = dict(layer=name, type=kind, prec=prec)
+                for k, (med, spr) in r.items():
+                    res[k + "_ms"], res[k + "_spread"] = med, spr
+                print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+                lines.append("%-34s %-5s %11.4f %6.1f%% %13.4f %6.1f%% %8.2fx" % (
+                    name + " " + kind[:7], prec, r["fused"][0], 100 * r["fused"][1], r["unfused"][0], 100 * r["unfused"][1],
+                    r["unfused"][0] / r["fused"][0]))
+    bt.set_precision("f32")
+    table = "\n".join(lines)
+    print(table)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("tools/attn_bench.py on an MI355X: device ms per captured replay (events around %d back-to-back replays, the routes\n"
+                    "alternating inside every round; median of the settled half of %d rounds, spread = (max - min) / median of that half).\n"
+                    "fused = btx_attn_fwd on the packed projection output; composite = the layer's eager core (transposes included); sdpa =\n"
+                    "F.scaled_dot_product_attention on pre-transposed contiguous heads; x = that route / fused.  TFLOP/s = 4 rows heads T^2 D\n"
+                    "(half under the causal mask) over the fused time; of peak = over the 2500 TFLOP/s dense bf16 MFMA peak.\n\n" % (a.calls, a.regions))
+            f.write(table + "\n")
+
+
+if __name__ == "__main__":
+    main()
