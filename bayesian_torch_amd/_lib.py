@@ -187,6 +187,8 @@ EXPORTS_GRU = ("btx_gru_workspace_bytes", "btx_gru_fwd")
 EXPORTS_GRU_TRAIN = ("btx_gru_train_saved_bytes", "btx_gru_train_workspace_bytes", "btx_gru_fwd_train", "btx_gru_bwd")
 # include/btx_attn.h: the fused multi-head attention forward, a fifth table
 EXPORTS_ATTN = ("btx_attn_fwd",)
+# include/btx_attn_train.h: the attention's training forward and its flash-attention backward, a sixth table
+EXPORTS_ATTN_TRAIN = ("btx_attn_fwd_train", "btx_attn_bwd")
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -424,6 +426,11 @@ def lib():
                               vp, ctypes.POINTER(LstmGrads), ctypes.POINTER(LstmGrads), i32, i32, i32, i32, i32, i32, vp, sz, vp]
     L.btx_attn_fwd.restype = i32
     L.btx_attn_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), vp, i32, i32, f32, i32, i32, vp]
+    L.btx_attn_fwd_train.restype = i32
+    L.btx_attn_fwd_train.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), vp, i32, i32, f32, i32,
+                                     i32, vp]
+    L.btx_attn_bwd.restype = i32
+    L.btx_attn_bwd.argtypes = [vp] * 10 + [i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), vp, i32, i32, f32, i32, i32, vp]
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

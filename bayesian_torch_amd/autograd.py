@@ -435,6 +435,40 @@ class GruTrainFn(torch.autograd.Function):
                 tuple(mask(7 + i, g) for i, g in enumerate(gh)) + (mask(11, gk), mask(12, gk)))
 
 
+class AttnFn(torch.autograd.Function):
+    """The attention core of a Bayesian multi-head attention layer on the HIP backend — btx_attn_fwd_train, then btx_attn_bwd
+     — with the gradient w.r.t. the packed in-projection output.  qkv: [rows, T, 3E], rows-first as a view (a
+    [T, rows, 3E] tensor arrives transposed: the output and the gradient then get that memory order too, and no copy is made).
+    meta = (heads, key_padding_mask | None, causal, prec).  Saved: qkv, out and one f32 scalar per (row, head, query)."""
+
+    @staticmethod
+    def forward(ctx, meta, qkv):
+        heads, pad, causal, prec = meta
+        R, T, E3 = qkv.shape
+        tmajor = qkv.stride(0) < qkv.stride(1)
+        out = torch.empty((T, R, E3 // 3) if tmajor else (R, T, E3 // 3), dtype=qkv.dtype, device=qkv.device)
+        out = out.transpose(0, 1) if tmajor else out
+        _, lse = BF.attn_train_fwd_hip(qkv.detach(), heads, pad, causal=causal, prec=prec, out=out)
+        ctx.meta, ctx.lse, ctx.tmajor = meta, lse, tmajor
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(qkv, out)
+        return out
+
+    @staticmethod
+    @_first_order
+    def backward(ctx, d_out):
+        if d_out is None or not ctx.needs_input_grad[1]:
+            return None, None
+        heads, pad, causal, prec = ctx.meta
+        qkv, out = ctx.saved_tensors
+        R, T, E3 = qkv.shape
+        with torch.no_grad():
+            d_qkv = torch.empty((T, R, E3) if ctx.tmajor else (R, T, E3), dtype=qkv.dtype, device=qkv.device)
+            d_qkv = d_qkv.transpose(0, 1) if ctx.tmajor else d_qkv
+            BF.attn_bwd_hip(qkv.detach(), out.detach(), d_out, ctx.lse, heads, pad, causal=causal, prec=prec, d_qkv=d_qkv)
+        return None, d_qkv
+
+
 def _entries(meta, params):
     out = []
     for i, (pm, ps, pmt, pst, op) in enumerate(meta):

@@ -23,15 +23,8 @@
 // Rows of masked keys are written as zeros (never multiplied, whatever bits they hold), keys and queries past the end are not read.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/btx_attn.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
-typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+#include "../../include/btx_attn_train.h"
+#include "btx_attn_tile.h"
 
 namespace {
 
@@ -46,58 +39,12 @@ struct AttnArgs {
   int Tq, Tk, heads, pad_rows, causal, nqt;
   float c;       // scale * log2(e): the softmax runs in base 2
   uint32_t vec;  // bit x: tensor x (q, k, v, out) sits on the 16-byte grid
+  float* lse;    // [rows][heads][Tq], the training forward only (btx_attn_fwd_train)
 };
 
-__device__ __forceinline__ uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
-__device__ __forceinline__ float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
-__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // v_cvt_pk_bf16_f32, round to nearest even
-  const f32x2 v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-
-// N (4 or 8) consecutive elements at element offset `off` of an ACT tensor, as f32 (exact)
-template <int ACT, int N>
-__device__ __forceinline__ void load_elems(const void* base, int64_t off, bool vec, float (&f)[N]) {
-  if constexpr (ACT == BTX_ACT_F32) {
-    const float* p = (const float*)base + off;
-    if (vec) {
-#pragma unroll
-      for (int i = 0; i < N / 4; ++i) {
-        const f32x4 t = *(const f32x4*)(p + 4 * i);
-        f[4 * i] = t[0]; f[4 * i + 1] = t[1]; f[4 * i + 2] = t[2]; f[4 * i + 3] = t[3];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < N; ++i) f[i] = p[i];
-    }
-  } else {
-    const uint16_t* p = (const uint16_t*)base + off;
-    if (vec) {
-      uint32_t w[N / 2];
-      if constexpr (N == 8) {
-        const u32x4 t = *(const u32x4*)p;
-        w[0] = t[0]; w[1] = t[1]; w[2] = t[2]; w[3] = t[3];
-      } else {
-        const u32x2 t = *(const u32x2*)p;
-        w[0] = t[0]; w[1] = t[1];
-      }
-#pragma unroll
-      for (int i = 0; i < N / 2; ++i) { f[2 * i] = u2f(w[i] << 16); f[2 * i + 1] = u2f(w[i] & 0xffff0000u); }
-    } else {
-#pragma unroll
-      for (int i = 0; i < N; ++i) f[i] = u2f((uint32_t)p[i] << 16);
-    }
-  }
-}
-
-// one 16-byte LDS unit of the operand type: 8 bf16 (PREC 1) or 4 f32 (PREC 0)
-template <int PREC, int N>
-__device__ __forceinline__ u32x4 pack_unit(const float (&f)[N]) {
-  if constexpr (PREC == BTX_PREC_BF16) return (u32x4){pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7])};
-  else return (u32x4){f2u(f[0]), f2u(f[1]), f2u(f[2]), f2u(f[3])};
-}
-
-template <int ACT, int PREC, int D>
+// LSE: the training forward — the same kernel, and each query also stores L = m + log2(l), the base-2 log-sum-exp of its scaled
+// scores (+inf for a query whose keys are all masked: every probability exp2(c s - L) the backward recomputes is then 0)
+template <int ACT, int PREC, int D, bool LSE>
 __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
   constexpr bool BF = PREC == BTX_PREC_BF16;
   constexpr int BK = BF ? 64 : 32, NKB = BK / 32;  // keys per tile, 32-key MFMA blocks per tile
@@ -311,6 +258,9 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
   // ---- out = O / l; a query with every key masked stores zeros -------------------------------------------------------------------
   const float l = l_run + __shfl_xor(l_run, 32);
   if (!qok) return;
+  if constexpr (LSE) {
+    if (h == 0) a.lse[((int64_t)row * a.heads + head) * Tq + qidx] = l > 0.f ? m_run + log2f(l) : __builtin_huge_valf();
+  }
   const float inv = 1.0f / l;
   const int64_t ooff = (int64_t)row * a.s[6] + (int64_t)qidx * a.s[7] + (int64_t)head * D;
 #pragma unroll
@@ -320,35 +270,25 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
       float r4[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) r4[e] = l > 0.f ? o[dc][4 * g + e] * inv : 0.f;
-      const int64_t off = ooff + dc * 32 + 8 * g + 4 * h;
-      if constexpr (ACT == BTX_ACT_F32) {
-        float* p = (float*)a.out + off;
-        if (vo) *(f32x4*)p = (f32x4){r4[0], r4[1], r4[2], r4[3]};
-        else { p[0] = r4[0]; p[1] = r4[1]; p[2] = r4[2]; p[3] = r4[3]; }
-      } else {
-        uint16_t* p = (uint16_t*)a.out + off;
-        const uint32_t w0 = pk_bf16(r4[0], r4[1]), w1 = pk_bf16(r4[2], r4[3]);
-        if (vo) *(u32x2*)p = (u32x2){w0, w1};
-        else { p[0] = (uint16_t)w0; p[1] = (uint16_t)(w0 >> 16); p[2] = (uint16_t)w1; p[3] = (uint16_t)(w1 >> 16); }
-      }
+      store4<ACT>(a.out, ooff + dc * 32 + 8 * g + 4 * h, vo, r4);
     }
 }
 
-template <int ACT, int PREC>
+template <int ACT, int PREC, bool LSE>
 hipError_t launch_d(const AttnArgs& a, int D, uint32_t grid, hipStream_t st) {
   switch (D) {
-    case 32: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 32>), dim3(grid), dim3(NT), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 64>), dim3(grid), dim3(NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 128>), dim3(grid), dim3(NT), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 32, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 64, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 128, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
   }
   return hipGetLastError();
 }
 
-}  // namespace
-
-extern "C" int btx_attn_fwd(const void* q, const void* k, const void* v, void* out, int rows, int Tq, int Tk, int heads, int D,
-                            const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype,
-                            int prec, void* stream) {
+// the argument checks and the launch of both entry points; lse == nullptr: the inference kernel
+template <bool LSE>
+int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int rows, int Tq, int Tk, int heads, int D,
+             const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype, int prec,
+             void* stream) {
   if (!q || !k || !v || !out || !strides) return BTX_E_NULL;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   if (prec == BTX_PREC_BF16X3) return BTX_E_UNSUPPORTED;  // f32 and bf16 forms only
@@ -358,7 +298,9 @@ extern "C" int btx_attn_fwd(const void* q, const void* k, const void* v, void* o
   if (D != 32 && D != 64 && D != 128) return BTX_E_UNSUPPORTED;
   const uint64_t nqt = ((uint64_t)Tq + BQ - 1) / BQ, grid = nqt * (uint64_t)heads * (uint64_t)rows;
   if (grid > 0x7fffffffull) return BTX_E_UNSUPPORTED;
+  if (LSE && (uintptr_t)lse % 4) return BTX_E_ALIGN;
   AttnArgs a = {};
+  a.lse = lse;
   a.q = q; a.k = k; a.v = v; a.out = out; a.pad = key_pad;
   const uintptr_t base[4] = {(uintptr_t)q, (uintptr_t)k, (uintptr_t)v, (uintptr_t)out};
   const int64_t esz = act_dtype == BTX_ACT_F32 ? 4 : 2;
@@ -372,9 +314,24 @@ extern "C" int btx_attn_fwd(const void* q, const void* k, const void* v, void* o
   a.c = scale * 1.44269504088896340736f;
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
-  if (act_dtype == BTX_ACT_F32) e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32>(a, D, (uint32_t)grid, st)
-                                                        : launch_d<BTX_ACT_F32, BTX_PREC_BF16>(a, D, (uint32_t)grid, st);
-  else e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32>(a, D, (uint32_t)grid, st)
-                                : launch_d<BTX_ACT_BF16, BTX_PREC_BF16>(a, D, (uint32_t)grid, st);
+  if (act_dtype == BTX_ACT_F32) e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32, LSE>(a, D, (uint32_t)grid, st)
+                                                        : launch_d<BTX_ACT_F32, BTX_PREC_BF16, LSE>(a, D, (uint32_t)grid, st);
+  else e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32, LSE>(a, D, (uint32_t)grid, st)
+                                : launch_d<BTX_ACT_BF16, BTX_PREC_BF16, LSE>(a, D, (uint32_t)grid, st);
   return (int)e;
+}
+
+}  // namespace
+
+extern "C" int btx_attn_fwd(const void* q, const void* k, const void* v, void* out, int rows, int Tq, int Tk, int heads, int D,
+                            const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype,
+                            int prec, void* stream) {
+  return attn_fwd<false>(q, k, v, out, nullptr, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale, act_dtype, prec, stream);
+}
+
+extern "C" int btx_attn_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int rows, int Tq, int Tk,
+                                  int heads, int D, const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal,
+                                  float scale, int act_dtype, int prec, void* stream) {
+  if (!lse) return BTX_E_NULL;
+  return attn_fwd<true>(q, k, v, out, lse, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale, act_dtype, prec, stream);
 }

@@ -1,0 +1,82 @@
+// btx_attn_tile.h — what the attention kernels share (btx_attn.hip, btx_attn_bwd.hip): the vector types of the MFMA operands, the
+// element loads of an activation tensor and the 16-byte LDS unit of the operand type.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/btx.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+
+namespace {
+
+__device__ __forceinline__ uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
+__device__ __forceinline__ float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
+__device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) {  // v_cvt_pk_bf16_f32, round to nearest even
+  const f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+
+// N (4 or 8) consecutive elements at element offset `off` of an ACT tensor, as f32 (exact)
+template <int ACT, int N>
+__device__ __forceinline__ void load_elems(const void* base, int64_t off, bool vec, float (&f)[N]) {
+  if constexpr (ACT == BTX_ACT_F32) {
+    const float* p = (const float*)base + off;
+    if (vec) {
+#pragma unroll
+      for (int i = 0; i < N / 4; ++i) {
+        const f32x4 t = *(const f32x4*)(p + 4 * i);
+        f[4 * i] = t[0]; f[4 * i + 1] = t[1]; f[4 * i + 2] = t[2]; f[4 * i + 3] = t[3];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) f[i] = p[i];
+    }
+  } else {
+    const uint16_t* p = (const uint16_t*)base + off;
+    if (vec) {
+      uint32_t w[N / 2];
+      if constexpr (N == 8) {
+        const u32x4 t = *(const u32x4*)p;
+        w[0] = t[0]; w[1] = t[1]; w[2] = t[2]; w[3] = t[3];
+      } else {
+        const u32x2 t = *(const u32x2*)p;
+        w[0] = t[0]; w[1] = t[1];
+      }
+#pragma unroll
+      for (int i = 0; i < N / 2; ++i) { f[2 * i] = u2f(w[i] << 16); f[2 * i + 1] = u2f(w[i] & 0xffff0000u); }
+    } else {
+#pragma unroll
+      for (int i = 0; i < N; ++i) f[i] = u2f((uint32_t)p[i] << 16);
+    }
+  }
+}
+
+// one 16-byte LDS unit of the operand type: 8 bf16 (PREC 1) or 4 f32 (PREC 0)
+template <int PREC, int N>
+__device__ __forceinline__ u32x4 pack_unit(const float (&f)[N]) {
+  if constexpr (PREC == BTX_PREC_BF16) return (u32x4){pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7])};
+  else return (u32x4){f2u(f[0]), f2u(f[1]), f2u(f[2]), f2u(f[3])};
+}
+
+// four consecutive f32 results stored as ACT elements at element offset `off` (16-byte / 8-byte store on the grid, else per element)
+template <int ACT>
+__device__ __forceinline__ void store4(void* base, int64_t off, bool vec, const float (&r4)[4]) {
+  if constexpr (ACT == BTX_ACT_F32) {
+    float* p = (float*)base + off;
+    if (vec) *(f32x4*)p = (f32x4){r4[0], r4[1], r4[2], r4[3]};
+    else { p[0] = r4[0]; p[1] = r4[1]; p[2] = r4[2]; p[3] = r4[3]; }
+  } else {
+    uint16_t* p = (uint16_t*)base + off;
+    const uint32_t w0 = pk_bf16(r4[0], r4[1]), w1 = pk_bf16(r4[2], r4[3]);
+    if (vec) *(u32x2*)p = (u32x2){w0, w1};
+    else { p[0] = (uint16_t)w0; p[1] = (uint16_t)(w0 >> 16); p[2] = (uint16_t)w1; p[3] = (uint16_t)(w1 >> 16); }
+  }
+}
+
+}  // namespace

@@ -1198,46 +1198,34 @@ ATTN_PRECISIONS = ("f32", "bf16")  # btx_attn_fwd's forms
 ATTN_HEAD_DIMS = (32, 64, 128)
 
 
-def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
-    """The attention core softmax(scale * q k^T + masks) v of every (row, head) in ONE launch (btx_attn_fwd, DESIGN.md §30), scale =
-    head_dim ** -0.5.  qkv: one packed tensor [rows, T, 3E] (q | k | v along the last axis, an in-projection's output) or a tuple
-    (q [rows, Tq, E], k [rows, Tk, E], v [rows, Tk, E]); f32 or bf16.  The kernel is told each tensor's (row, token) strides, so a
-    packed buffer, a `[T, rows, E].transpose(0, 1)` view and tensors off the 16-byte grid are read where they lie; only a tensor whose
-    last axis is not contiguous is copied first (one stream-ordered copy).  key_padding_mask: [B, Tk] bool / uint8 (non-zero = masked)
-    with B dividing rows: row r reads mask row r % B (MC lanes share the batch's mask).  causal: key j is masked for query i when
-    j > i.  A query whose keys are all masked gives zeros.  out: a [rows, Tq, E] tensor of the input's dtype to write into (any
-    row / token strides, last axis contiguous, no overlap); returned.  No workspace, no allocation beyond `out`: capturable."""
-    L = _lib.lib()
+def _attn_args(fn, qkv, heads, key_padding_mask, prec):
+    """the checks attn_hip, attn_train_fwd_hip and attn_bwd_hip share; returns (q, k, v, act, prec, heads, mask bytes | None, pad_rows)"""
     if isinstance(qkv, (tuple, list)):
         q, k, v = qkv
     else:
         if qkv.dim() != 3 or qkv.shape[-1] % 3:
-            raise _lib.BtxError("attn_hip: a packed qkv must be [rows, T, 3E], got %s" % (tuple(qkv.shape),))
+            raise _lib.BtxError("%s: a packed qkv must be [rows, T, 3E], got %s" % (fn, tuple(qkv.shape)))
         E = qkv.shape[-1] // 3
         q, k, v = qkv[..., :E], qkv[..., E:2 * E], qkv[..., 2 * E:]
     if not q.is_cuda:
-        raise _lib.BtxError("attn_hip needs CUDA (ROCm) tensors")
+        raise _lib.BtxError("%s needs CUDA (ROCm) tensors" % fn)
     act = _lstm_act(q)
     prec = prec or _PRECISION
     if prec not in ATTN_PRECISIONS:
         raise _lib.BtxError("the fused attention core has no %s form" % prec)
     if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != q.shape[2]:
-        raise _lib.BtxError("attn_hip: q [rows, Tq, E] and k, v [rows, Tk, E] expected, got %s, %s, %s"
-                            % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+        raise _lib.BtxError("%s: q [rows, Tq, E] and k, v [rows, Tk, E] expected, got %s, %s, %s"
+                            % (fn, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
     if k.dtype != q.dtype or v.dtype != q.dtype or k.device != q.device or v.device != q.device:
-        raise _lib.BtxError("attn_hip: q, k and v must share dtype and device")
+        raise _lib.BtxError("%s: q, k and v must share dtype and device" % fn)
     rows, Tq, E = q.shape
     Tk, heads = k.shape[1], int(heads)
     if heads < 1 or E % heads or E // heads not in ATTN_HEAD_DIMS:
-        raise _lib.BtxError("attn_hip: head_dim = E / heads must be one of %s, got E=%d, heads=%d" % (ATTN_HEAD_DIMS, E, heads))
+        raise _lib.BtxError("%s: head_dim = E / heads must be one of %s, got E=%d, heads=%d" % (fn, ATTN_HEAD_DIMS, E, heads))
     if rows < 1 or Tq < 1 or Tk < 1:
-        raise _lib.BtxError("attn_hip: empty input %s" % (tuple(q.shape),))
+        raise _lib.BtxError("%s: empty input %s" % (fn, tuple(q.shape)))
     # DESIGN.md §15.1: the (row, token) strides are passed; a view whose last axis is not contiguous is densified
     q, k, v = (t if t.stride(2) == 1 else t.contiguous() for t in (q, k, v))
-    if out is None:
-        out = torch.empty(rows, Tq, E, dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (rows, Tq, E) or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1:
-        raise _lib.BtxError("out must be a [%d, %d, %d] %s tensor on the input's device with a contiguous last axis" % (rows, Tq, E, q.dtype))
     kp, pad_rows = None, 1
     if key_padding_mask is not None:
         kp = key_padding_mask
@@ -1247,11 +1235,97 @@ def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=Non
         kp = kp.to(device=q.device).contiguous()
         kp = kp.view(torch.uint8) if kp.dtype == torch.bool else kp
         pad_rows = kp.shape[0]
-    strides = (ctypes.c_int64 * 8)(*(int(t.stride(i)) for t in (q, k, v, out) for i in (0, 1)))
-    _lib.check(L.btx_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), rows, Tq, Tk, heads, E // heads, strides,
-                              kp.data_ptr() if kp is not None else None, pad_rows, 1 if causal else 0, float(E // heads) ** -0.5,
-                              act, _lib.PREC_CODE[prec], torch.cuda.current_stream(q.device).cuda_stream))
-    return out
+    return q, k, v, act, prec, heads, kp, pad_rows
+
+
+def _attn_like(fn, name, t, ref, shape):
+    """a caller's [rows, T, E] tensor beside q: dtype, device, shape, contiguous last axis"""
+    if tuple(t.shape) != tuple(shape) or t.dtype != ref.dtype or t.device != ref.device or t.stride(2) != 1:
+        raise _lib.BtxError("%s: %s must be a [%d, %d, %d] %s tensor on the input's device with a contiguous last axis"
+                            % ((fn, name) + tuple(shape) + (ref.dtype,)))
+    return t
+
+
+def _attn_strides(*tensors):
+    return (ctypes.c_int64 * (2 * len(tensors)))(*(int(t.stride(i)) for t in tensors for i in (0, 1)))
+
+
+def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
+    """The attention core softmax(scale * q k^T + masks) v of every (row, head) in ONE launch (btx_attn_fwd, DESIGN.md §30), scale =
+    head_dim ** -0.5.  qkv: one packed tensor [rows, T, 3E] (q | k | v along the last axis, an in-projection's output) or a tuple
+    (q [rows, Tq, E], k [rows, Tk, E], v [rows, Tk, E]); f32 or bf16.  The kernel is told each tensor's (row, token) strides, so a
+    packed buffer, a `[T, rows, E].transpose(0, 1)` view and tensors off the 16-byte grid are read where they lie; only a tensor whose
+    last axis is not contiguous is copied first (one stream-ordered copy).  key_padding_mask: [B, Tk] bool / uint8 (non-zero = masked)
+    with B dividing rows: row r reads mask row r % B (MC lanes share the batch's mask).  causal: key j is masked for query i when
+    j > i.  A query whose keys are all masked gives zeros.  out: a [rows, Tq, E] tensor of the input's dtype to write into (any
+    row / token strides, last axis contiguous, no overlap); returned.  No workspace, no allocation beyond `out`: capturable."""
+    return _attn_fwd("attn_hip", qkv, heads, key_padding_mask, causal, prec, out, False)
+
+
+def _attn_fwd(fn, qkv, heads, key_padding_mask, causal, prec, out, train):
+    L = _lib.lib()
+    q, k, v, act, prec, heads, kp, pad_rows = _attn_args(fn, qkv, heads, key_padding_mask, prec)
+    (rows, Tq, E), Tk = q.shape, k.shape[1]
+    if out is None:
+        out = torch.empty(rows, Tq, E, dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (rows, Tq, E) or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1:
+        raise _lib.BtxError("out must be a [%d, %d, %d] %s tensor on the input's device with a contiguous last axis" % (rows, Tq, E, q.dtype))
+    tail = (rows, Tq, Tk, heads, E // heads, _attn_strides(q, k, v, out), kp.data_ptr() if kp is not None else None, pad_rows,
+            1 if causal else 0, float(E // heads) ** -0.5, act, _lib.PREC_CODE[prec], torch.cuda.current_stream(q.device).cuda_stream)
+    if not train:
+        _lib.check(L.btx_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), *tail))
+        return out
+    lse = torch.empty(rows, heads, Tq, dtype=torch.float32, device=q.device)
+    _lib.check(L.btx_attn_fwd_train(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), *tail))
+    return out, lse
+
+
+def attn_train_fwd_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
+    """attn_hip for a forward that will be differentiated (btx_attn_fwd_train): the same arguments and, bit for bit,
+    the same `out`; returns (out, lse) with lse [rows, heads, Tq] f32, the base-2 log-sum-exp of every query's scaled scores (+inf
+    for a query whose keys are all masked) — with `out`, all that attn_bwd_hip needs beside the inputs."""
+    return _attn_fwd("attn_train_fwd_hip", qkv, heads, key_padding_mask, causal, prec, out, True)
+
+
+def attn_bwd_hip(qkv, out, d_out, lse, heads, key_padding_mask=None, causal=False, prec=None, d_qkv=None):
+    """The backward of one attn_train_fwd_hip call with the same qkv, masks and prec (btx_attn_bwd): two launches, no
+    T x T tensor, no atomics (two calls give the same bits).  out, lse: what the forward returned; d_out [rows, Tq, E]: the gradient
+    at `out` (any row / token strides).  Returns the gradient in the input's form: for a packed qkv ONE [rows, T, 3E] tensor (dq |
+    dk | dv, the layout in_proj's backward consumes), for a tuple a tuple (dq, dk, dv).  d_qkv: the tensor(s) to write into, same
+    form (any row / token strides, last axis contiguous, no overlap with an input).  Every element is written, zeros for padded keys
+    and for queries whose keys are all masked: the buffers come from torch.empty.  One [rows, heads, Tq] f32 scratch plane (delta =
+    d_out . out) is allocated per call through the caching allocator: capturable."""
+    L = _lib.lib()
+    packed = not isinstance(qkv, (tuple, list))
+    q, k, v, act, prec, heads, kp, pad_rows = _attn_args("attn_bwd_hip", qkv, heads, key_padding_mask, prec)
+    (rows, Tq, E), Tk = q.shape, k.shape[1]
+    out = _attn_like("attn_bwd_hip", "out", out, q, q.shape)
+    if d_out.stride(2) != 1:
+        d_out = d_out.contiguous()
+    d_out = _attn_like("attn_bwd_hip", "d_out", d_out, q, q.shape)
+    if tuple(lse.shape) != (rows, heads, Tq) or lse.dtype != torch.float32 or lse.device != q.device or not lse.is_contiguous():
+        raise _lib.BtxError("attn_bwd_hip: lse must be the [%d, %d, %d] float32 tensor attn_train_fwd_hip returned" % (rows, heads, Tq))
+    if d_qkv is None:
+        if packed:
+            d_qkv = torch.empty(rows, Tq, 3 * E, dtype=q.dtype, device=q.device)
+        else:
+            d_qkv = (torch.empty(rows, Tq, E, dtype=q.dtype, device=q.device), torch.empty(rows, Tk, E, dtype=q.dtype, device=q.device),
+                     torch.empty(rows, Tk, E, dtype=q.dtype, device=q.device))
+    if isinstance(d_qkv, (tuple, list)):
+        dq, dk, dv = d_qkv
+    else:
+        if tuple(d_qkv.shape) != (rows, Tq, 3 * E) or Tq != Tk:
+            raise _lib.BtxError("attn_bwd_hip: a packed d_qkv must be [%d, %d, %d], got %s" % (rows, Tq, 3 * E, tuple(d_qkv.shape)))
+        dq, dk, dv = d_qkv[..., :E], d_qkv[..., E:2 * E], d_qkv[..., 2 * E:]
+    for name, t, ref in (("dq", dq, q), ("dk", dk, k), ("dv", dv, v)):
+        _attn_like("attn_bwd_hip", name, t, q, ref.shape)
+    delta = torch.empty(rows, heads, Tq, dtype=torch.float32, device=q.device)
+    _lib.check(L.btx_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(),
+                              delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rows, Tq, Tk, heads, E // heads,
+                              _attn_strides(q, k, v, out, d_out, dq, dk, dv), kp.data_ptr() if kp is not None else None, pad_rows,
+                              1 if causal else 0, float(E // heads) ** -0.5, act, _lib.PREC_CODE[prec],
+                              torch.cuda.current_stream(q.device).cuda_stream))
+    return d_qkv
 
 
 def _gru_train_args(fn, x, ih, hh, prec, h0):

@@ -1293,12 +1293,30 @@ class _VariationalMHA(BaseVariationalLayer_):
     def fused_attention(self, on):
         self.__dict__["_btx_fused_attention"] = bool(on)
 
-    def _fused_ok(self, x, key_padding_mask, need_weights, attn_mask, is_causal):
+    # fused_training (opt-in; models.fuse_model(model, attn_training=True) sets it, and it implies fused_attention): forwards that
+    # need gradients run the core as btx_attn_fwd_train and its backward as btx_attn_bwd (autograd.AttnFn) — eagerly,
+    # inside autograd.GraphedTrainStep and with MC lanes.  Without it, training forwards take the composite.
+    @property
+    def fused_training(self):
+        return bool(self.__dict__.get("_btx_fused_training", False))
+
+    @fused_training.setter
+    def fused_training(self, on):
+        on = bool(on)
+        self.__dict__["_btx_fused_training"] = on
+        if on:
+            self.fused_attention = True
+
+    def _fused_train_ok(self, x, key_padding_mask, need_weights, attn_mask, is_causal):
+        """the conditions of the fused training core: fused_training, a forward that needs gradients, and _fused_ok's other conditions"""
+        return self.fused_training and self._fused_ok(x, key_padding_mask, need_weights, attn_mask, is_causal, train=True)
+
+    def _fused_ok(self, x, key_padding_mask, need_weights, attn_mask, is_causal, train=False):
         """the conditions of the fused core; anything else takes the composite"""
         ip, op = self.in_proj, self.out_proj
         if not self.fused_attention or not x.is_cuda or not ip._use_hip(x) or x.dim() != 3 or need_weights:
             return False
-        if x.dtype not in (torch.float32, torch.bfloat16) or ip._needs_grad(x) or op._needs_grad(None):
+        if x.dtype not in (torch.float32, torch.bfloat16) or bool(ip._needs_grad(x) or op._needs_grad(None)) != train:
             return False
         if self.head_dim not in BF.ATTN_HEAD_DIMS:
             return False
@@ -1354,6 +1372,7 @@ class _VariationalMHA(BaseVariationalLayer_):
             raise _lib.BtxError("%s: MC sample lanes need batch_first=True (the lanes are stacked on axis 0, which is the token axis "
                                 "of a [T, batch, E] input)" % type(self).__name__)
         fused = self._fused_ok(query, key_padding_mask, need_weights, attn_mask, is_causal)
+        fused_train = self._fused_train_ok(query, key_padding_mask, need_weights, attn_mask, is_causal)
         hip = query.is_cuda and self.in_proj._use_hip(query)
         kl = None
         if return_kl:
@@ -1371,6 +1390,11 @@ class _VariationalMHA(BaseVariationalLayer_):
             o = torch.empty((R, T, self.embed_dim) if self.batch_first else (T, R, self.embed_dim), dtype=qkv.dtype, device=qkv.device)
             BF.attn_hip(rows_first, self.num_heads, key_padding_mask, causal=bool(is_causal or attn_mask is not None),
                         prec=self.in_proj.precision or BF.get_precision(), out=o if self.batch_first else o.transpose(0, 1))
+        elif fused_train:
+            from .. import autograd as _ag
+            o = _ag.AttnFn.apply((self.num_heads, key_padding_mask, bool(is_causal or attn_mask is not None),
+                                  self.in_proj.precision or BF.get_precision()), rows_first)
+            o = o if self.batch_first else o.transpose(0, 1)
         else:
             o, w = self._core(rows_first, key_padding_mask, need_weights, attn_mask, average_attn_weights, is_causal)
             if not self.batch_first:

@@ -702,6 +702,13 @@ def _gru_training(model, on):
                 m.fused_training = True
 
 
+def _attn_training(model, on):
+    if on:
+        for m in model.modules():
+            if _is_mha(m):
+                m.fused_training = True
+
+
 def _lrt_training(model, on):
     if on:
         for m in model.modules():
@@ -709,7 +716,7 @@ def _lrt_training(model, on):
                 m.fused_training = True
 
 
-def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=False):
+def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=False, attn_training=False):
     """Fold eval-mode BatchNorm, residual adds and ReLU / ReLU6 into the store of the variational layers of ANY model converted
     by dnn_to_bnn (its variational layers return a tensor), in place.  The model's forward is traced with torch.fx (variational
     layers and torch.nn modules as leaves) and every chain
@@ -739,11 +746,14 @@ def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=Fals
     every ...LocalReparameterization layer (and for no other layer): GPU forwards that need gradients run btx_lrt_fwd_train /
     btx_lrt_bwd where functional.lrt_train_ok holds, the ATen composite elsewhere.  gru_training=True sets fused_training on every
     Bayesian GRU (and on no LSTM, as lstm_training=True sets it on no GRU): its training forwards on the GPU run btx_gru_fwd_train
-    and their backward btx_gru_bwd (also inside autograd.GraphedTrainStep)."""
+    and their backward btx_gru_bwd (also inside autograd.GraphedTrainStep).  attn_training=True sets fused_training on every Bayesian
+    multi-head attention (and on nothing else): the attention core of its training forwards on the GPU runs btx_attn_fwd_train and
+    its backward btx_attn_bwd (autograd.AttnFn; also inside autograd.GraphedTrainStep and with MC lanes)."""
     _lrt_training(model, lrt_training)
     if model.__dict__.get("_btx_fuse_model"):
         _lstm_training(model, lstm_training)
         _gru_training(model, gru_training)
+        _attn_training(model, attn_training)
         return 0
     object.__setattr__(model, "_btx_fuse_model", True)
     lstms = [m for m in model.modules() if _is_lstm(m) and not m.fused_sequence]
@@ -755,6 +765,7 @@ def fuse_model(model, lstm_training=False, lrt_training=False, gru_training=Fals
     lstms = lstms + mhas
     _lstm_training(model, lstm_training)
     _gru_training(model, gru_training)
+    _attn_training(model, attn_training)
     inl = set(map(id, _inlined(model)))
     hooked = [k for k, m in model.named_modules() if k and id(m) in inl and _hooked(m)]
     if hooked:  # (tracing would run the hooks on fx proxies, and the rewritten forward would skip them)

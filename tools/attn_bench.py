@@ -12,7 +12,14 @@ half's spread (max - min) / median.
 TFLOP/s = 4 rows heads Tq Tk D (half of it under the causal mask) over the fused time; "of peak" is that rate over the 2500 TFLOP/s
 dense bf16 MFMA peak of an MI355X (printed for the bf16 rows only).
 Layer: mc.GraphedMC replays (one MC sample each) of embed -> converted TransformerEncoderLayer -> first token -> head, the model fused by
-fuse_model against the same model unfused, alternating."""
+fuse_model against the same model unfused, alternating.
+
+    python tools/attn_bench.py --train [--out profiles/attn_train_bench.txt]
+
+Training: forward plus backward of the core, each route captured with its backward (torch.autograd.grad at a fixed
+d_out) — fused = autograd.AttnFn (btx_attn_fwd_train + btx_attn_bwd), composite = the layer's eager core under autograd, sdpa =
+F.scaled_dot_product_attention — and one whole training step (autograd.GraphedTrainStep: forward, loss, backward) of the layer model,
+fuse_model(m, attn_training=True) against fuse_model(m).  The saved-activation bytes of the core are derived, not measured."""
 import argparse
 import json
 import os
@@ -57,15 +64,15 @@ def _alternate(fns, calls, regions):
     return out
 
 
-def _graphed(fn):
+def _graphed(fn, grad=False):
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s), torch.no_grad():
+    with torch.cuda.stream(s), torch.set_grad_enabled(grad):
         for _ in range(2):
             fn()
     torch.cuda.current_stream().wait_stream(s)
     g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g), torch.no_grad():
+    with torch.cuda.graph(g), torch.set_grad_enabled(grad):
         fn()
     return g.replay
 
@@ -81,12 +88,88 @@ class Net(nn.Module):
         return self.head(self.enc(self.embed(x))[:, 0])
 
 
+def train(a):
+    """the training mode: forward + backward of the core per route, then one captured training step of the layer model"""
+    import bayesian_torch_amd as bt
+    from bayesian_torch_amd import autograd as ag, layers as L
+    from bayesian_torch_amd.models import fuse_model
+    dev = torch.device("cuda:0")
+    lines = ["%-17s %-5s %11s %7s %13s %7s %10s %7s %9s %8s" % (
+        "core fwd + bwd", "dtype", "fused ms", "spread", "composite ms", "spread", "sdpa ms", "spread", "comp / f", "sdpa / f")]
+    for name, R, T, H, D, causal in SHAPES:
+        for dt, prec in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
+            torch.manual_seed(0)
+            layer = L.MultiheadAttentionReparameterization(H * D, H, batch_first=True)
+            qkv = (0.5 * torch.randn(R, T, 3 * H * D, device=dev)).to(dt).requires_grad_()
+            d_out = torch.randn(R, T, H * D, device=dev).to(dt)
+            heads = [t.detach().reshape(R, T, H, D).transpose(1, 2).contiguous().requires_grad_() for t in qkv.chunk(3, dim=-1)]
+            d_heads = d_out.reshape(R, T, H, D).transpose(1, 2).contiguous()
+            G = torch.autograd.grad
+            fns = dict(fused=_graphed(lambda: G(ag.AttnFn.apply((H, None, causal, prec), qkv), qkv, d_out), True),
+                       composite=_graphed(lambda: G(layer._core(qkv, None, False, None, True, causal)[0], qkv, d_out), True),
+                       sdpa=_graphed(lambda: G(F.scaled_dot_product_attention(*heads, is_causal=causal), heads, d_heads), True))
+            r = _alternate(fns, a.calls, a.regions)
+            res = dict(core=name, dtype=prec, rows=R, T=T, heads=H, D=D, causal=causal, mode="train")
+            for k, (med, spr) in r.items():
+                res[k + "_ms"], res[k + "_spread"] = med, spr
+            print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in res.items()}), flush=True)
+            lines.append("%-17s %-5s %11.4f %6.1f%% %13.4f %6.1f%% %10.4f %6.1f%% %8.2fx %7.2fx" % (
+                name, prec, r["fused"][0], 100 * r["fused"][1], r["composite"][0], 100 * r["composite"][1], r["sdpa"][0],
+                100 * r["sdpa"][1], r["composite"][0] / r["fused"][0], r["sdpa"][0] / r["fused"][0]))
+            del fns
+    lines.append("")
+    lines.append("%-34s %-5s %11s %7s %13s %7s %9s" % ("training step (embed, layer, head)", "prec", "fused ms", "spread", "unfused ms", "spread", "unf / f"))
+    B, T, E, H, FF = 64, 197, 768, 12, 3072
+    for kind in ("Reparameterization", "Flipout"):
+        for prec in ("bf16", "f32"):
+            bt.set_precision(prec)
+            x, y = torch.randn(B, T, E, device=dev), torch.randint(0, 10, (B,), device=dev)
+            steps = {}
+            for route in ("fused", "unfused"):
+                torch.manual_seed(0)
+                m = Net(E, H, FF)
+                bt.dnn_to_bnn(m, dict(PRIOR, type=kind))
+                m = m.to(dev).train()
+                fuse_model(m, attn_training=route == "fused")
+                steps[route] = ag.GraphedTrainStep(m, x.clone(), y)
+            r = _alternate({k: (lambda g=g: g.run(0)) for k, g in steps.items()}, max(2, a.calls // 4), a.regions)
+            for g in steps.values():
+                g.close()
+            print(json.dumps(dict(layer="vit-b", type=kind, prec=prec, mode="train", fused_ms=round(r["fused"][0], 5),
+                                  unfused_ms=round(r["unfused"][0], 5))), flush=True)
+            lines.append("%-34s %-5s %11.4f %6.1f%% %13.4f %6.1f%% %8.2fx" % (
+                "vit-b 64 x 197 x 768 " + kind[:7], prec, r["fused"][0], 100 * r["fused"][1], r["unfused"][0], 100 * r["unfused"][1],
+                r["unfused"][0] / r["fused"][0]))
+    bt.set_precision("f32")
+    # derived: what the core keeps for its backward beside qkv and out — fused: lse [rows, heads, T] f32 (the backward's delta plane of the
+    # same size is transient); composite under autograd: the f32 scores and probabilities [rows, heads, T, T] (softmax keeps its output,
+    # the two masked_fill nodes a bool mask each) and the head-major f32 copies of q, k, v
+    R, T, H, D = SHAPES[0][1:5]
+    lines += ["", "saved by the core for vit-b (derived): fused %d bytes (+ %d transient in the backward); composite >= %d bytes" % (
+        R * H * T * 4, R * H * T * 4, R * H * T * T * (4 + 4 + 1) + 3 * R * H * T * D * 4)]
+    table = "\n".join(lines)
+    print(table)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("tools/attn_bench.py --train on an MI355X: device ms per captured replay of forward + backward (events around %d back-to-back\n"
+                    "replays, the routes alternating inside every round; median of the settled half of %d rounds, spread = (max - min) /\n"
+                    "median of that half).  fused = autograd.AttnFn; composite = the layer's eager core under autograd; sdpa =\n"
+                    "F.scaled_dot_product_attention on pre-transposed contiguous heads; x = that route / fused.\n\n" % (a.calls, a.regions))
+            f.write(table + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=10)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train", action="store_true", help="time forward + backward (DESIGN.md section 31) instead of the inference forward")
     a = ap.parse_args()
+    if a.train:
+        if not torch.cuda.is_available():
+            raise SystemExit("attn_bench needs a GPU: nothing is measured without one")
+        return train(a)
     import bayesian_torch_amd as bt
     from bayesian_torch_amd import functional as BF, layers as L, mc
     from bayesian_torch_amd.models import fuse_model
