@@ -189,6 +189,9 @@ EXPORTS_GRU_TRAIN = ("btx_gru_train_saved_bytes", "btx_gru_train_workspace_bytes
 EXPORTS_ATTN = ("btx_attn_fwd",)
 # include/btx_attn_train.h: the attention's training forward and its flash-attention backward, a sixth table
 EXPORTS_ATTN_TRAIN = ("btx_attn_fwd_train", "btx_attn_bwd")
+# include/btx_attn_bias.h: the three attention entry points with an additive score bias / general mask, a seventh table
+EXPORTS_ATTN_BIAS = ("btx_attn_bias_fwd", "btx_attn_bias_fwd_train", "btx_attn_bias_bwd")
+BIAS_DTYPE_CODE = {"float32": 0, "bfloat16": 1, "uint8": 2, "bool": 2}  # BTX_BIAS_F32 / _BF16 / _U8
 MC_EVAL_MAX_CLASSES, MC_EVAL_MAX_BINS, MC_EVAL_MAX_THRESHOLDS = 24575, 64, 32
 MC_EVAL_HEADER, MC_EVAL_CURSOR, MC_EVAL_DROPPED = 16, 11, 12
 REG_EVAL_MAX_LEVELS, REG_EVAL_HEADER, REG_EVAL_CURSOR, REG_EVAL_DROPPED = 8, 16, 9, 10
@@ -431,6 +434,11 @@ def lib():
                                      i32, vp]
     L.btx_attn_bwd.restype = i32
     L.btx_attn_bwd.argtypes = [vp] * 10 + [i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64), vp, i32, i32, f32, i32, i32, vp]
+    bias_tail = [vp, i32, i32, ctypes.POINTER(ctypes.c_int64)]  # bias, bias_dtype, bias_rows, bias_strides[3]
+    for name, base in (("btx_attn_bias_fwd", L.btx_attn_fwd), ("btx_attn_bias_fwd_train", L.btx_attn_fwd_train),
+                       ("btx_attn_bias_bwd", L.btx_attn_bwd)):
+        getattr(L, name).restype = i32
+        getattr(L, name).argtypes = list(base.argtypes) + bias_tail
     if L.btx_abi_version() != ABI_VERSION:
         raise BtxError("libbtx.so ABI %d != expected %d" % (L.btx_abi_version(), ABI_VERSION))
     _LIB = L

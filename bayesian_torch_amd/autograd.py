@@ -439,16 +439,18 @@ class AttnFn(torch.autograd.Function):
     """The attention core of a Bayesian multi-head attention layer on the HIP backend — btx_attn_fwd_train, then btx_attn_bwd
      — with the gradient w.r.t. the packed in-projection output.  qkv: [rows, T, 3E], rows-first as a view (a
     [T, rows, 3E] tensor arrives transposed: the output and the gradient then get that memory order too, and no copy is made).
-    meta = (heads, key_padding_mask | None, causal, prec).  Saved: qkv, out and one f32 scalar per (row, head, query)."""
+    meta = (heads, key_padding_mask | None, causal, prec[, bias | None]): the additive score bias / general mask of DESIGN.md §32
+    rides in the non-tensor config like the key-padding mask (btx_attn_bias_fwd_train / btx_attn_bias_bwd; it has no gradient).
+    Saved: qkv, out and one f32 scalar per (row, head, query)."""
 
     @staticmethod
     def forward(ctx, meta, qkv):
-        heads, pad, causal, prec = meta
+        heads, pad, causal, prec, bias = (tuple(meta) + (None,))[:5]
         R, T, E3 = qkv.shape
         tmajor = qkv.stride(0) < qkv.stride(1)
         out = torch.empty((T, R, E3 // 3) if tmajor else (R, T, E3 // 3), dtype=qkv.dtype, device=qkv.device)
         out = out.transpose(0, 1) if tmajor else out
-        _, lse = BF.attn_train_fwd_hip(qkv.detach(), heads, pad, causal=causal, prec=prec, out=out)
+        _, lse = BF.attn_train_fwd_hip(qkv.detach(), heads, pad, causal=causal, prec=prec, out=out, bias=bias)
         ctx.meta, ctx.lse, ctx.tmajor = meta, lse, tmajor
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(qkv, out)
@@ -459,13 +461,13 @@ class AttnFn(torch.autograd.Function):
     def backward(ctx, d_out):
         if d_out is None or not ctx.needs_input_grad[1]:
             return None, None
-        heads, pad, causal, prec = ctx.meta
+        heads, pad, causal, prec, bias = (tuple(ctx.meta) + (None,))[:5]
         qkv, out = ctx.saved_tensors
         R, T, E3 = qkv.shape
         with torch.no_grad():
             d_qkv = torch.empty((T, R, E3) if ctx.tmajor else (R, T, E3), dtype=qkv.dtype, device=qkv.device)
             d_qkv = d_qkv.transpose(0, 1) if ctx.tmajor else d_qkv
-            BF.attn_bwd_hip(qkv.detach(), out.detach(), d_out, ctx.lse, heads, pad, causal=causal, prec=prec, d_qkv=d_qkv)
+            BF.attn_bwd_hip(qkv.detach(), out.detach(), d_out, ctx.lse, heads, pad, causal=causal, prec=prec, d_qkv=d_qkv, bias=bias)
         return None, d_qkv
 
 

@@ -23,7 +23,8 @@
 // Rows of masked keys are written as zeros (never multiplied, whatever bits they hold), keys and queries past the end are not read.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/btx_attn_train.h"
+#include <type_traits>
+#include "../../include/btx_attn_bias.h"
 #include "btx_attn_tile.h"
 
 namespace {
@@ -41,11 +42,20 @@ struct AttnArgs {
   uint32_t vec;  // bit x: tensor x (q, k, v, out) sits on the 16-byte grid
   float* lse;    // [rows][heads][Tq], the training forward only (btx_attn_fwd_train)
 };
+struct AttnBiasArgs : AttnArgs {
+  BiasOp b;  // the BIAS instantiations only: the kernel argument of the others is AttnArgs as it was
+};
 
 // LSE: the training forward — the same kernel, and each query also stores L = m + log2(l), the base-2 log-sum-exp of its scaled
 // scores (+inf for a query whose keys are all masked: every probability exp2(c s - L) the backward recomputes is then 0)
-template <int ACT, int PREC, int D, bool LSE>
-__global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
+//
+// BIAS (include/btx_attn_bias.h): the score becomes fma(s, c, b log2 e) with b = bias[row % rows][head][query][key].
+// Lane (l31, h) holds four consecutive keys of its own query per group g: one 16 / 8 / 4-byte load per group, every element used by
+// one lane once, so the bias goes from global memory to registers (no LDS).  Tile t+1's is requested as soon as the scores of tile t
+// have consumed tile t's (ONE register set): the loads fly under the P V MFMAs, the barrier and the next tile's S MFMAs.  A query
+// stride of 0 (key-only bias) makes the 32 lanes of a half-wave read the same address: one transaction.
+template <int ACT, int PREC, int D, bool LSE, bool BIAS>
+__global__ __launch_bounds__(NT) void attn_fwd_kernel(const typename std::conditional<BIAS, AttnBiasArgs, AttnArgs>::type a) {
   constexpr bool BF = PREC == BTX_PREC_BF16;
   constexpr int BK = BF ? 64 : 32, NKB = BK / 32;  // keys per tile, 32-key MFMA blocks per tile
   constexpr int ESZ = BF ? 2 : 4, EPU = 16 / ESZ;  // operand bytes, elements per 16-byte unit
@@ -150,6 +160,32 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
     if (tid < BK) Vs[V_BYTES + tid] = (unsigned char)flag;
   };
 
+  // ---- BIAS: the lane's bias of the next tile, [32-key block][group][key of the group]; elements past Tq / Tk are not read -------
+  constexpr int NBB = BIAS ? NKB * 16 : 1;
+  float bb[NBB];
+  if constexpr (BIAS) {  // a lane without a query never loads: its (unstored) column computes on zeros
+#pragma unroll
+    for (int i = 0; i < NBB; ++i) bb[i] = 0.f;
+  }
+  [[maybe_unused]] int64_t boff = 0;
+  if constexpr (BIAS) boff = (int64_t)(row % a.b.rows) * a.b.s[0] + (int64_t)head * a.b.s[1] + (int64_t)qidx * a.b.s[2];
+  auto fetch_bias = [&](int t) {
+    if constexpr (BIAS) {
+      const int k0 = t * BK;
+      if (!qok || (a.causal && k0 > wq0 + 31)) return;  // no query, or a tile the wave skips
+#pragma unroll
+      for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int key = k0 + kb * 32 + 8 * g + 4 * h;
+          float f[4] = {0.f, 0.f, 0.f, 0.f};
+          if (key < Tk) load_bias4(a.b, boff + key, min(4, Tk - key), f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bb[kb * 16 + 4 * g + e] = f[e];
+        }
+    }
+  };
+
   // ---- the key loop -------------------------------------------------------------------------------------------------------------
   f32x16 o[NDC];
 #pragma unroll
@@ -160,6 +196,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
 
   fetch(0);
   stash(0);
+  fetch_bias(0);
   __syncthreads();
   for (int t = 0; t < nkt; ++t) {
     const int k0 = t * BK;
@@ -197,12 +234,15 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
           if (need_mask) fw = *(const uint32_t*)(Vs + V_BYTES + kk);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float v = s[kb][4 * g + e] * a.c;
+            float v;
+            if constexpr (BIAS) v = __builtin_fmaf(s[kb][4 * g + e], a.c, bb[kb * 16 + 4 * g + e] * BIAS_LOG2E);
+            else v = s[kb][4 * g + e] * a.c;
             if (need_mask && (((fw >> (8 * e)) & 0xffu) || (a.causal && k0 + kk + e > qidx))) v = NEG_INF;
             s[kb][4 * g + e] = v;
             mx = fmaxf(mx, v);
           }
         }
+      if (t + 1 < nkt) fetch_bias(t + 1);  // bb is consumed: the next tile's loads fly under the P V MFMAs and the next K / V fetch
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       const float m_new = fmaxf(m_run, mx);
       const float m_use = m_new == NEG_INF ? 0.f : m_new;  // every key so far masked: p = exp2(-inf) = 0, alpha = 0
@@ -274,21 +314,30 @@ __global__ __launch_bounds__(NT) void attn_fwd_kernel(const AttnArgs a) {
     }
 }
 
-template <int ACT, int PREC, bool LSE>
-hipError_t launch_d(const AttnArgs& a, int D, uint32_t grid, hipStream_t st) {
+template <int ACT, int PREC, bool LSE, bool BIAS>
+hipError_t launch_d(const AttnBiasArgs& a, int D, uint32_t grid, hipStream_t st) {
   switch (D) {
-    case 32: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 32, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 64, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 128, LSE>), dim3(grid), dim3(NT), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 32, LSE, BIAS>), dim3(grid), dim3(NT), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 64, LSE, BIAS>), dim3(grid), dim3(NT), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_fwd_kernel<ACT, PREC, 128, LSE, BIAS>), dim3(grid), dim3(NT), 0, st, a); break;
   }
   return hipGetLastError();
 }
 
-// the argument checks and the launch of both entry points; lse == nullptr: the inference kernel
+template <bool LSE, bool BIAS>
+hipError_t launch_p(const AttnBiasArgs& a, int D, int act_dtype, int prec, uint32_t grid, hipStream_t st) {
+  if (act_dtype == BTX_ACT_F32) return prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32, LSE, BIAS>(a, D, grid, st)
+                                                            : launch_d<BTX_ACT_F32, BTX_PREC_BF16, LSE, BIAS>(a, D, grid, st);
+  return prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32, LSE, BIAS>(a, D, grid, st)
+                              : launch_d<BTX_ACT_BF16, BTX_PREC_BF16, LSE, BIAS>(a, D, grid, st);
+}
+
+// the argument checks and the launch of all four entry points; lse == nullptr: the inference kernel; bias == nullptr: no bias (the
+// kernel without the BIAS flag, whose argument is the AttnArgs part of `a`)
 template <bool LSE>
 int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse, int rows, int Tq, int Tk, int heads, int D,
              const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype, int prec,
-             void* stream) {
+             void* stream, const void* bias = nullptr, int bias_dtype = 0, int bias_rows = 1, const int64_t* bias_strides = nullptr) {
   if (!q || !k || !v || !out || !strides) return BTX_E_NULL;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   if (prec == BTX_PREC_BF16X3) return BTX_E_UNSUPPORTED;  // f32 and bf16 forms only
@@ -299,7 +348,11 @@ int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
   const uint64_t nqt = ((uint64_t)Tq + BQ - 1) / BQ, grid = nqt * (uint64_t)heads * (uint64_t)rows;
   if (grid > 0x7fffffffull) return BTX_E_UNSUPPORTED;
   if (LSE && (uintptr_t)lse % 4) return BTX_E_ALIGN;
-  AttnArgs a = {};
+  AttnBiasArgs a = {};
+  if (bias) {
+    const int rc = bias_operand(bias, bias_dtype, bias_rows, bias_strides, a.b);
+    if (rc) return rc;
+  }
   a.lse = lse;
   a.q = q; a.k = k; a.v = v; a.out = out; a.pad = key_pad;
   const uintptr_t base[4] = {(uintptr_t)q, (uintptr_t)k, (uintptr_t)v, (uintptr_t)out};
@@ -313,12 +366,8 @@ int attn_fwd(const void* q, const void* k, const void* v, void* out, float* lse,
   a.Tq = Tq; a.Tk = Tk; a.heads = heads; a.pad_rows = key_pad ? pad_rows : 1; a.causal = causal; a.nqt = (int)nqt;
   a.c = scale * 1.44269504088896340736f;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if (act_dtype == BTX_ACT_F32) e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32, LSE>(a, D, (uint32_t)grid, st)
-                                                        : launch_d<BTX_ACT_F32, BTX_PREC_BF16, LSE>(a, D, (uint32_t)grid, st);
-  else e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32, LSE>(a, D, (uint32_t)grid, st)
-                                : launch_d<BTX_ACT_BF16, BTX_PREC_BF16, LSE>(a, D, (uint32_t)grid, st);
-  return (int)e;
+  return (int)(bias ? launch_p<LSE, true>(a, D, act_dtype, prec, (uint32_t)grid, st)
+                    : launch_p<LSE, false>(a, D, act_dtype, prec, (uint32_t)grid, st));
 }
 
 }  // namespace
@@ -335,3 +384,21 @@ extern "C" int btx_attn_fwd_train(const void* q, const void* k, const void* v, v
   if (!lse) return BTX_E_NULL;
   return attn_fwd<true>(q, k, v, out, lse, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale, act_dtype, prec, stream);
 }
+
+extern "C" int btx_attn_bias_fwd(const void* q, const void* k, const void* v, void* out, int rows, int Tq, int Tk, int heads, int D,
+                                 const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal, float scale,
+                                 int act_dtype, int prec, void* stream, const void* bias, int bias_dtype, int bias_rows,
+                                 const int64_t bias_strides[3]) {
+  return attn_fwd<false>(q, k, v, out, nullptr, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale, act_dtype, prec, stream,
+                         bias, bias_dtype, bias_rows, bias_strides);
+}
+
+extern "C" int btx_attn_bias_fwd_train(const void* q, const void* k, const void* v, void* out, float* lse, int rows, int Tq, int Tk,
+                                       int heads, int D, const int64_t strides[8], const uint8_t* key_pad, int pad_rows, int causal,
+                                       float scale, int act_dtype, int prec, void* stream, const void* bias, int bias_dtype,
+                                       int bias_rows, const int64_t bias_strides[3]) {
+  if (!lse) return BTX_E_NULL;
+  return attn_fwd<true>(q, k, v, out, lse, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale, act_dtype, prec, stream,
+                        bias, bias_dtype, bias_rows, bias_strides);
+}
+

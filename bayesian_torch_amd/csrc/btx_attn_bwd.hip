@@ -29,7 +29,8 @@
 // Rows of masked keys and of tokens past the end are written as zeros and never read from memory; nothing is stored past the end.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/btx_attn_train.h"
+#include <type_traits>
+#include "../../include/btx_attn_bias.h"
 #include "btx_attn_tile.h"
 
 namespace {
@@ -50,8 +51,22 @@ struct BwdArgs {
   uint32_t vec;       // bit x: tensor x sits on the 16-byte grid
 };
 
-template <int ACT, int PREC, int D, bool KV>
-__global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
+struct BwdBiasArgs : BwdArgs {
+  BiasOp b;  // the BIAS instantiations only: the kernel argument of the others is BwdArgs as it was
+};
+
+// BIAS (include/btx_attn_bias.h): P = exp2(fma(S, c, b log2 e) - L), b = bias[row % rows][head][query][key].
+//   dQ pass     the lane's four consecutive streamed tokens are four consecutive KEYS of its own query: one 16 / 8 / 4-byte load per
+//               group straight into registers, as in the forward (requested when the previous tile's have been consumed)
+//   dK/dV pass  they are four consecutive QUERIES of its own key — four strided reads.  The [BS queries][128 own keys] tile goes through
+//               LDS instead: read from global memory along the key axis (thread u: query u / 32, keys 4 (u % 32) .. +3, coalesced) with
+//               the K / V fetch, stored as f32 rows of 128 + 8 words behind L and delta in `aux`, read per accumulator entry as one
+//               word at [query][own key].  A wave's 64 lanes read keys l31 of query rows kk + e and kk + e + 4 (h): 4 * 136 words = 32
+//               banks apart, so the 64 words fall on 64 different banks.
+constexpr int BROW = (BO + 8) * 4;
+
+template <int ACT, int PREC, int D, bool KV, bool BIAS>
+__global__ __launch_bounds__(NT) void attn_bwd_kernel(const typename std::conditional<BIAS, BwdBiasArgs, BwdArgs>::type a) {
   constexpr bool BF = PREC == BTX_PREC_BF16;
   constexpr int BS = (BF && D <= 64) ? 64 : 32, NSB = BS / 32;  // streamed tokens per tile, 32-token MFMA blocks per tile
   constexpr int ESZ = BF ? 2 : 4, EPU = 16 / ESZ;               // operand bytes, elements per 16-byte unit
@@ -59,7 +74,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
   constexpr int NDC = D / 32, NF = BF ? D / 16 : D / 8;         // 32-channel blocks; 16-byte units of an own fragment
   constexpr int RROW = D * ESZ + 16, R_BYTES = BS * RROW;
   constexpr int TROW = BS * 2 + 8, T_BYTES = BF ? D * TROW : 0, NTR = KV ? 2 : 1;
-  constexpr int AUX = KV ? BS * 8 : BS;
+  constexpr int B_BYTES = (KV && BIAS) ? BS * BROW : 0, NG = BS * 32 / NT;  // the bias tile; its four-key groups per thread
+  constexpr int AUX = KV ? BS * 8 + B_BYTES : BS;
+  // the f32 D = 128 dK/dV pass has no registers left to hold a next tile across the MFMAs once the bias is added (492 of 512
+  // without it; the compiler spills): it fetches tile t+1 after the MFMAs of tile t, right before it writes it, and pays that
+  // latency once per tile (section 32.3)
+  constexpr bool LATE = KV && BIAS && !BF && D == 128;
   constexpr int STAGE = 2 * R_BYTES + NTR * T_BYTES + AUX;
   constexpr int XO1 = KV ? X_K : X_Q, XO2 = KV ? X_V : X_DO, XS1 = KV ? X_Q : X_K, XS2 = KV ? X_DO : X_V;
   static_assert(BS * UPR == NU * NT && STAGE % 16 == 0, "tile plan");
@@ -129,6 +149,39 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
   u32x4 r1[NU], r2[NU];
   float auxL = 0.f, auxD = 0.f;
   uint32_t flag = 0;
+  f32x4 bst[(KV && BIAS) ? NG : 1];              // dK/dV pass: the thread's part of the next bias tile
+  float bb[(!KV && BIAS) ? NSB * 16 : 1];  // dQ pass: the lane's bias of the next tile, [32-key block][group][key of the group]
+  if constexpr (!KV && BIAS) {  // a lane without a query never loads: its (unstored) column computes on zeros
+#pragma unroll
+    for (int i = 0; i < NSB * 16; ++i) bb[i] = 0.f;
+  }
+  [[maybe_unused]] int64_t bbase = 0;
+  if constexpr (BIAS) bbase = (int64_t)(row % a.b.rows) * a.b.s[0] + (int64_t)head * a.b.s[1];
+  auto fetch_bias = [&](int t) {  // dQ pass; elements past Tq / Tk are not read
+    if constexpr (!KV && BIAS) {
+      const int s0 = t * BS;
+      if (!ook || (a.causal && s0 > w0 + 31)) return;  // no query, or a tile the wave skips
+#pragma unroll
+      for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int key = s0 + sb * 32 + 8 * g + 4 * h;
+          float f[4] = {0.f, 0.f, 0.f, 0.f};
+          if (key < Tk) load_bias4(a.b, bbase + (int64_t)oidx * a.b.s[2] + key, min(4, Tk - key), f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) bb[sb * 16 + 4 * g + e] = f[e];
+        }
+    }
+  };
+  // dK/dV pass: group u of the bias tile at s0 — query s0 + u / 32, own keys 4 (u % 32) .. +3; elements past Tq / Tk are not read
+  auto bias_group = [&](int s0, int u) -> f32x4 {
+    float f[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (KV && BIAS) {
+      const int tok = s0 + (u >> 5), key = ot * BO + (u & 31) * 4;
+      if (tok < Tq && key < Tk) load_bias4(a.b, bbase + (int64_t)tok * a.b.s[2] + key, min(4, Tk - key), f);
+    }
+    return (f32x4){f[0], f[1], f[2], f[3]};
+  };
   auto fetch = [&](int t) {
     const int s0 = t * BS;
 #pragma unroll
@@ -143,6 +196,10 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
       }
       r1[i] = pack_unit<PREC>(x1);
       r2[i] = pack_unit<PREC>(x2);
+    }
+    if constexpr (KV && BIAS) {
+#pragma unroll
+      for (int i = 0; i < NG; ++i) bst[i] = bias_group(s0, tid + i * NT);
     }
     if (tid < BS) {
       const int tok = s0 + tid;
@@ -173,6 +230,13 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
         }
       }
     }
+    if constexpr (KV && BIAS) {
+#pragma unroll
+      for (int i = 0; i < NG; ++i) {
+        const int u = tid + i * NT;
+        *(f32x4*)(A + BS * 8 + (u >> 5) * BROW + (u & 31) * 16) = bst[i];
+      }
+    }
     if (tid < BS) {
       if constexpr (KV) {
         *(float*)(A + tid * 4) = auxL;
@@ -195,10 +259,13 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
 
   fetch(t0);
   stash(t0 & 1);
+  if constexpr (BIAS) fetch_bias(t0);
   __syncthreads();
   for (int t = t0; t < t1; ++t) {
     const int s0 = t * BS;
-    if (t + 1 < t1) fetch(t + 1);
+    if constexpr (!LATE) {
+      if (t + 1 < t1) fetch(t + 1);
+    }
     const unsigned char* R1 = lds + (t & 1) * STAGE;
     const unsigned char* R2 = R1 + R_BYTES;
     const unsigned char* T1 = R2 + R_BYTES;
@@ -254,11 +321,21 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
             bool m;
             if constexpr (KV) m = !oload || (a.causal && oidx > tok);
             else m = need_mask && (((fw >> (8 * e)) & 0xffu) || (a.causal && tok > oidx));
-            const float p = m ? 0.f : __builtin_amdgcn_exp2f(s[sb][4 * g + e] * a.c - Lq[e]);
+            float p;
+            if constexpr (BIAS) {
+              float b;
+              if constexpr (KV) b = *(const float*)(A + BS * 8 + (kk + e) * BROW + (wave * 32 + l31) * 4);
+              else b = bb[sb * 16 + 4 * g + e];
+              p = m ? 0.f : __builtin_amdgcn_exp2f(__builtin_fmaf(s[sb][4 * g + e], a.c, b * BIAS_LOG2E) - Lq[e]);
+            } else {
+              p = m ? 0.f : __builtin_amdgcn_exp2f(s[sb][4 * g + e] * a.c - Lq[e]);
+            }
             s[sb][4 * g + e] = p;
             dp[sb][4 * g + e] = m ? 0.f : p * (dp[sb][4 * g + e] - dq[e]);
           }
         }
+      if constexpr (BIAS)
+        if (t + 1 < t1) fetch_bias(t + 1);  // bb is consumed: the next tile's loads fly under the MFMAs below and the next fetch
       // acc1 += T1^T dS;  dK/dV pass: acc2 += T2^T P
 #pragma unroll
       for (int sb = 0; sb < NSB; ++sb) {
@@ -299,6 +376,9 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
         }
       }
     }
+    if constexpr (LATE) {
+      if (t + 1 < t1) fetch(t + 1);
+    }
     if (t + 1 < t1) stash((t + 1) & 1);
     __syncthreads();
   }
@@ -323,32 +403,41 @@ __global__ __launch_bounds__(NT) void attn_bwd_kernel(const BwdArgs a) {
     }
 }
 
-template <int ACT, int PREC, int D>
-hipError_t launch_passes(BwdArgs a, uint32_t grid_q, uint32_t grid_k, int nqt, int nkt, hipStream_t st) {
+template <int ACT, int PREC, int D, bool BIAS>
+hipError_t launch_passes(BwdBiasArgs a, uint32_t grid_q, uint32_t grid_k, int nqt, int nkt, hipStream_t st) {
   a.not_ = nqt;
-  hipLaunchKernelGGL((attn_bwd_kernel<ACT, PREC, D, false>), dim3(grid_q), dim3(NT), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<ACT, PREC, D, false, BIAS>), dim3(grid_q), dim3(NT), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   a.not_ = nkt;
-  hipLaunchKernelGGL((attn_bwd_kernel<ACT, PREC, D, true>), dim3(grid_k), dim3(NT), 0, st, a);
+  hipLaunchKernelGGL((attn_bwd_kernel<ACT, PREC, D, true, BIAS>), dim3(grid_k), dim3(NT), 0, st, a);
   return hipGetLastError();
 }
 
-template <int ACT, int PREC>
-hipError_t launch_d(const BwdArgs& a, int D, uint32_t grid_q, uint32_t grid_k, int nqt, int nkt, hipStream_t st) {
+template <int ACT, int PREC, bool BIAS>
+hipError_t launch_d(const BwdBiasArgs& a, int D, uint32_t grid_q, uint32_t grid_k, int nqt, int nkt, hipStream_t st) {
   switch (D) {
-    case 32: return launch_passes<ACT, PREC, 32>(a, grid_q, grid_k, nqt, nkt, st);
-    case 64: return launch_passes<ACT, PREC, 64>(a, grid_q, grid_k, nqt, nkt, st);
-    default: return launch_passes<ACT, PREC, 128>(a, grid_q, grid_k, nqt, nkt, st);
+    case 32: return launch_passes<ACT, PREC, 32, BIAS>(a, grid_q, grid_k, nqt, nkt, st);
+    case 64: return launch_passes<ACT, PREC, 64, BIAS>(a, grid_q, grid_k, nqt, nkt, st);
+    default: return launch_passes<ACT, PREC, 128, BIAS>(a, grid_q, grid_k, nqt, nkt, st);
   }
 }
 
-}  // namespace
+template <bool BIAS>
+hipError_t launch_p(const BwdBiasArgs& a, int D, int act_dtype, int prec, uint32_t grid_q, uint32_t grid_k, int nqt, int nkt, hipStream_t st) {
+  if (act_dtype == BTX_ACT_F32)
+    return prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32, BIAS>(a, D, grid_q, grid_k, nqt, nkt, st)
+                                : launch_d<BTX_ACT_F32, BTX_PREC_BF16, BIAS>(a, D, grid_q, grid_k, nqt, nkt, st);
+  return prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32, BIAS>(a, D, grid_q, grid_k, nqt, nkt, st)
+                              : launch_d<BTX_ACT_BF16, BTX_PREC_BF16, BIAS>(a, D, grid_q, grid_k, nqt, nkt, st);
+}
 
-extern "C" int btx_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* d_out, const float* lse,
-                            float* delta, void* dq, void* dk, void* dv, int rows, int Tq, int Tk, int heads, int D,
-                            const int64_t strides[16], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype,
-                            int prec, void* stream) {
+// the argument checks and the launches of both entry points; bias == nullptr: no bias (the kernels without the BIAS flag, whose
+// argument is the BwdArgs part of `a`)
+int attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* d_out, const float* lse, float* delta, void* dq,
+             void* dk, void* dv, int rows, int Tq, int Tk, int heads, int D, const int64_t strides[16], const uint8_t* key_pad,
+             int pad_rows, int causal, float scale, int act_dtype, int prec, void* stream, const void* bias, int bias_dtype,
+             int bias_rows, const int64_t* bias_strides) {
   if (!q || !k || !v || !out || !d_out || !lse || !delta || !dq || !dk || !dv || !strides) return BTX_E_NULL;
   if (act_dtype != BTX_ACT_F32 && act_dtype != BTX_ACT_BF16) return BTX_E_DTYPE;
   if (prec == BTX_PREC_BF16X3) return BTX_E_UNSUPPORTED;  // f32 and bf16 forms only
@@ -360,7 +449,11 @@ extern "C" int btx_attn_bwd(const void* q, const void* k, const void* v, const v
   const uint64_t grid_q = nqt * (uint64_t)heads * (uint64_t)rows, grid_k = nkt * (uint64_t)heads * (uint64_t)rows;
   if (grid_q > 0x7fffffffull || grid_k > 0x7fffffffull) return BTX_E_UNSUPPORTED;
   if ((uintptr_t)lse % 4 || (uintptr_t)delta % 4) return BTX_E_ALIGN;
-  BwdArgs a = {};
+  BwdBiasArgs a = {};
+  if (bias) {
+    const int rc = bias_operand(bias, bias_dtype, bias_rows, bias_strides, a.b);
+    if (rc) return rc;
+  }
   a.in[X_Q] = q; a.in[X_K] = k; a.in[X_V] = v; a.in[X_O] = out; a.in[X_DO] = d_out;
   a.g[0] = dq; a.g[1] = dk; a.g[2] = dv;
   a.lse = lse; a.delta = delta; a.pad = key_pad;
@@ -376,12 +469,26 @@ extern "C" int btx_attn_bwd(const void* q, const void* k, const void* v, const v
   a.c = scale * 1.44269504088896340736f;
   a.scale = scale;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
-  if (act_dtype == BTX_ACT_F32)
-    e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_F32, BTX_PREC_F32>(a, D, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st)
-                             : launch_d<BTX_ACT_F32, BTX_PREC_BF16>(a, D, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st);
-  else
-    e = prec == BTX_PREC_F32 ? launch_d<BTX_ACT_BF16, BTX_PREC_F32>(a, D, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st)
-                             : launch_d<BTX_ACT_BF16, BTX_PREC_BF16>(a, D, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st);
-  return (int)e;
+  return (int)(bias ? launch_p<true>(a, D, act_dtype, prec, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st)
+                    : launch_p<false>(a, D, act_dtype, prec, (uint32_t)grid_q, (uint32_t)grid_k, (int)nqt, (int)nkt, st));
 }
+
+}  // namespace
+
+extern "C" int btx_attn_bwd(const void* q, const void* k, const void* v, const void* out, const void* d_out, const float* lse,
+                            float* delta, void* dq, void* dk, void* dv, int rows, int Tq, int Tk, int heads, int D,
+                            const int64_t strides[16], const uint8_t* key_pad, int pad_rows, int causal, float scale, int act_dtype,
+                            int prec, void* stream) {
+  return attn_bwd(q, k, v, out, d_out, lse, delta, dq, dk, dv, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale,
+                  act_dtype, prec, stream, nullptr, 0, 1, nullptr);
+}
+
+extern "C" int btx_attn_bias_bwd(const void* q, const void* k, const void* v, const void* out, const void* d_out, const float* lse,
+                                 float* delta, void* dq, void* dk, void* dv, int rows, int Tq, int Tk, int heads, int D,
+                                 const int64_t strides[16], const uint8_t* key_pad, int pad_rows, int causal, float scale,
+                                 int act_dtype, int prec, void* stream, const void* bias, int bias_dtype, int bias_rows,
+                                 const int64_t bias_strides[3]) {
+  return attn_bwd(q, k, v, out, d_out, lse, delta, dq, dk, dv, rows, Tq, Tk, heads, D, strides, key_pad, pad_rows, causal, scale,
+                  act_dtype, prec, stream, bias, bias_dtype, bias_rows, bias_strides);
+}
+

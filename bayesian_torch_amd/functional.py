@@ -1250,7 +1250,34 @@ def _attn_strides(*tensors):
     return (ctypes.c_int64 * (2 * len(tensors)))(*(int(t.stride(i)) for t in tensors for i in (0, 1)))
 
 
-def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
+def _attn_bias(fn, bias, rows, heads, Tq, Tk, device):
+    """the `bias` keyword of attn_hip, attn_train_fwd_hip and attn_bwd_hip -> the four trailing arguments of the btx_attn_bias_* entry
+    points, (tensor kept alive, (data_ptr, dtype code, bias_rows, strides[3]))"""
+    if not isinstance(bias, torch.Tensor) or str(bias.dtype).split(".")[-1] not in _lib.BIAS_DTYPE_CODE:
+        raise _lib.BtxError("%s: bias must be a bool, uint8, float32 or bfloat16 tensor, got %s"
+                            % (fn, bias.dtype if isinstance(bias, torch.Tensor) else type(bias).__name__))
+    if bias.requires_grad:
+        raise _lib.BtxError("%s: the bias has no gradient on the fused path (detach it, or take the composite)" % fn)
+    shp, B = tuple(bias.shape), 0
+    if bias.dim() == 2 and shp == (Tq, Tk):
+        B, bias = 1, bias[None, None]
+    elif bias.dim() == 3 and shp[1:] == (Tq, Tk) and shp[0] % heads == 0:
+        B, bias = shp[0] // heads, bias.unflatten(0, (shp[0] // heads, heads))
+    elif bias.dim() == 4 and shp[1] in (1, heads) and shp[2] in (1, Tq) and shp[3] == Tk:
+        B = shp[0]
+    if B < 1 or rows % B:
+        raise _lib.BtxError("%s: bias must be [Tq, Tk], [heads, Tq, Tk], [B * heads, Tq, Tk] or [B, heads | 1, Tq | 1, Tk] with B dividing "
+                            "rows (rows %d, heads %d, Tq %d, Tk %d), got %s" % (fn, rows, heads, Tq, Tk, shp))
+    bias = bias.to(device=device)
+    if bias.stride(3) != 1 and Tk > 1:
+        bias = bias.contiguous()  # the key axis is the kernel's vector axis; expanded (stride-0) axes are passed as they are otherwise
+    if bias.dtype == torch.bool:
+        bias = bias.view(torch.uint8)
+    strides = (ctypes.c_int64 * 3)(*(0 if bias.shape[i] == 1 else int(bias.stride(i)) for i in range(3)))
+    return bias, (bias.data_ptr(), _lib.BIAS_DTYPE_CODE[str(bias.dtype).split(".")[-1]], B, strides)
+
+
+def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None, bias=None):
     """The attention core softmax(scale * q k^T + masks) v of every (row, head) in ONE launch (btx_attn_fwd), scale =
     head_dim ** -0.5.  qkv: one packed tensor [rows, T, 3E] (q | k | v along the last axis, an in-projection's output) or a tuple
     (q [rows, Tq, E], k [rows, Tk, E], v [rows, Tk, E]); f32 or bf16.  The kernel is told each tensor's (row, token) strides, so a
@@ -1258,11 +1285,15 @@ def attn_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=Non
     last axis is not contiguous is copied first (one stream-ordered copy).  key_padding_mask: [B, Tk] bool / uint8 (non-zero = masked)
     with B dividing rows: row r reads mask row r % B (MC lanes share the batch's mask).  causal: key j is masked for query i when
     j > i.  A query whose keys are all masked gives zeros.  out: a [rows, Tq, E] tensor of the input's dtype to write into (any
-    row / token strides, last axis contiguous, no overlap); returned.  No workspace, no allocation beyond `out`: capturable."""
-    return _attn_fwd("attn_hip", qkv, heads, key_padding_mask, causal, prec, out, False)
+    row / token strides, last axis contiguous, no overlap); returned.  No workspace, no allocation beyond `out`: capturable.
+    bias (btx_attn_bias_fwd): a tensor added to the scaled scores before the softmax, broadcast to [rows, heads, Tq, Tk]
+    — [Tq, Tk], [heads, Tq, Tk], [B * heads, Tq, Tk] or [B, heads | 1, Tq | 1, Tk] with B dividing rows (row r reads bias row r % B);
+    float32 or bfloat16 (additive, -inf masks the pair), bool or uint8 (non-zero = masked).  Size-1 and expanded axes are passed as
+    stride 0 and never materialised; only a bias whose key axis is not contiguous is copied first.  It has no gradient."""
+    return _attn_fwd("attn_hip", qkv, heads, key_padding_mask, causal, prec, out, False, bias)
 
 
-def _attn_fwd(fn, qkv, heads, key_padding_mask, causal, prec, out, train):
+def _attn_fwd(fn, qkv, heads, key_padding_mask, causal, prec, out, train, bias=None):
     L = _lib.lib()
     q, k, v, act, prec, heads, kp, pad_rows = _attn_args(fn, qkv, heads, key_padding_mask, prec)
     (rows, Tq, E), Tk = q.shape, k.shape[1]
@@ -1272,29 +1303,33 @@ def _attn_fwd(fn, qkv, heads, key_padding_mask, causal, prec, out, train):
         raise _lib.BtxError("out must be a [%d, %d, %d] %s tensor on the input's device with a contiguous last axis" % (rows, Tq, E, q.dtype))
     tail = (rows, Tq, Tk, heads, E // heads, _attn_strides(q, k, v, out), kp.data_ptr() if kp is not None else None, pad_rows,
             1 if causal else 0, float(E // heads) ** -0.5, act, _lib.PREC_CODE[prec], torch.cuda.current_stream(q.device).cuda_stream)
+    fwd, fwd_train = L.btx_attn_fwd, L.btx_attn_fwd_train
+    if bias is not None:
+        bias, btail = _attn_bias(fn, bias, rows, heads, Tq, Tk, q.device)
+        tail, fwd, fwd_train = tail + btail, L.btx_attn_bias_fwd, L.btx_attn_bias_fwd_train
     if not train:
-        _lib.check(L.btx_attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), *tail))
+        _lib.check(fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), *tail))
         return out
     lse = torch.empty(rows, heads, Tq, dtype=torch.float32, device=q.device)
-    _lib.check(L.btx_attn_fwd_train(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), *tail))
+    _lib.check(fwd_train(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), lse.data_ptr(), *tail))
     return out, lse
 
 
-def attn_train_fwd_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None):
+def attn_train_fwd_hip(qkv, heads, key_padding_mask=None, causal=False, prec=None, out=None, bias=None):
     """attn_hip for a forward that will be differentiated (btx_attn_fwd_train): the same arguments and, bit for bit,
     the same `out`; returns (out, lse) with lse [rows, heads, Tq] f32, the base-2 log-sum-exp of every query's scaled scores (+inf
     for a query whose keys are all masked) — with `out`, all that attn_bwd_hip needs beside the inputs."""
-    return _attn_fwd("attn_train_fwd_hip", qkv, heads, key_padding_mask, causal, prec, out, True)
+    return _attn_fwd("attn_train_fwd_hip", qkv, heads, key_padding_mask, causal, prec, out, True, bias)
 
 
-def attn_bwd_hip(qkv, out, d_out, lse, heads, key_padding_mask=None, causal=False, prec=None, d_qkv=None):
+def attn_bwd_hip(qkv, out, d_out, lse, heads, key_padding_mask=None, causal=False, prec=None, d_qkv=None, bias=None):
     """The backward of one attn_train_fwd_hip call with the same qkv, masks and prec (btx_attn_bwd): two launches, no
     T x T tensor, no atomics (two calls give the same bits).  out, lse: what the forward returned; d_out [rows, Tq, E]: the gradient
     at `out` (any row / token strides).  Returns the gradient in the input's form: for a packed qkv ONE [rows, T, 3E] tensor (dq |
     dk | dv, the layout in_proj's backward consumes), for a tuple a tuple (dq, dk, dv).  d_qkv: the tensor(s) to write into, same
     form (any row / token strides, last axis contiguous, no overlap with an input).  Every element is written, zeros for padded keys
     and for queries whose keys are all masked: the buffers come from torch.empty.  One [rows, heads, Tq] f32 scratch plane (delta =
-    d_out . out) is allocated per call through the caching allocator: capturable."""
+    d_out . out) is allocated per call through the caching allocator: capturable.  bias: the forward's (btx_attn_bias_bwd)."""
     L = _lib.lib()
     packed = not isinstance(qkv, (tuple, list))
     q, k, v, act, prec, heads, kp, pad_rows = _attn_args("attn_bwd_hip", qkv, heads, key_padding_mask, prec)
@@ -1320,11 +1355,15 @@ def attn_bwd_hip(qkv, out, d_out, lse, heads, key_padding_mask=None, causal=Fals
     for name, t, ref in (("dq", dq, q), ("dk", dk, k), ("dv", dv, v)):
         _attn_like("attn_bwd_hip", name, t, q, ref.shape)
     delta = torch.empty(rows, heads, Tq, dtype=torch.float32, device=q.device)
-    _lib.check(L.btx_attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(),
-                              delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rows, Tq, Tk, heads, E // heads,
-                              _attn_strides(q, k, v, out, d_out, dq, dk, dv), kp.data_ptr() if kp is not None else None, pad_rows,
-                              1 if causal else 0, float(E // heads) ** -0.5, act, _lib.PREC_CODE[prec],
-                              torch.cuda.current_stream(q.device).cuda_stream))
+    bwd, btail = L.btx_attn_bwd, ()
+    if bias is not None:
+        bias, btail = _attn_bias("attn_bwd_hip", bias, rows, heads, Tq, Tk, q.device)
+        bwd = L.btx_attn_bias_bwd
+    _lib.check(bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), d_out.data_ptr(), lse.data_ptr(),
+                   delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), rows, Tq, Tk, heads, E // heads,
+                   _attn_strides(q, k, v, out, d_out, dq, dk, dv), kp.data_ptr() if kp is not None else None, pad_rows,
+                   1 if causal else 0, float(E // heads) ** -0.5, act, _lib.PREC_CODE[prec],
+                   torch.cuda.current_stream(q.device).cuda_stream, *btail))
     return d_qkv
 
 

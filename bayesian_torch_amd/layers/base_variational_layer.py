@@ -1247,8 +1247,11 @@ class _VariationalMHA(BaseVariationalLayer_):
     out_proj.kl_loss().  Self-attention only: query, key and value must be the same tensor.  The scores and the softmax run in float32
     for bfloat16 / float16 inputs and in the input's dtype otherwise.  The one deviation from torch: a query whose keys are all
     masked gives zeros where torch gives NaN.  key_padding_mask: [batch, T] bool (True = masked) or additive float; attn_mask:
-    [T, T] bool or additive float; is_causal=True without an attn_mask means the causal mask, with one it vouches (as in torch) that
-    the mask IS the causal one.  `_linear_cls` is the Linear class of the family.
+    [T, T] or [batch * heads, T, T], bool or additive float; is_causal=True without an attn_mask means the causal mask, with one it
+    vouches (as in torch) that the mask IS the causal one.  The fused core (fused_attention / fused_training) takes all of these as
+    bool, float32 or bfloat16 tensors (what nn.TransformerEncoder passes down is a float mask); a mask that requires
+    grad, a float16 / float64 mask and need_weights take the composite.  A float key_padding_mask together with an attn_mask costs
+    one eager broadcast add (see _fused_masks).  `_linear_cls` is the Linear class of the family.
 
     The attributes embed_dim, num_heads, head_dim, batch_first, in_proj_bias (None) and _qkv_same_embed_dim (False) are what
     nn.TransformerEncoderLayer / nn.TransformerEncoder probe before their fused "fast path": with these values they skip it and call
@@ -1320,13 +1323,54 @@ class _VariationalMHA(BaseVariationalLayer_):
             return False
         if self.head_dim not in BF.ATTN_HEAD_DIMS:
             return False
-        if attn_mask is not None and not is_causal:
-            return False  # a general mask; with is_causal the caller vouches that it is the causal one (torch's contract)
-        if key_padding_mask is not None and key_padding_mask.dtype != torch.bool:
-            return False  # an additive float mask may hold finite values: only the composite can add them
+        if not self._masks_fusable(x, key_padding_mask, attn_mask, is_causal):
+            return False
         if ip._forward_hooks or ip._forward_pre_hooks or op._forward_hooks or op._forward_pre_hooks:
             return False
         return (ip.precision or BF.get_precision()) in BF.ATTN_PRECISIONS
+
+    def _masks_fusable(self, x, key_padding_mask, attn_mask, is_causal):
+        """the masks the fused core takes: bool, float32 and bfloat16 tensors on the GPU that need no gradient — a
+        [B, T] key_padding_mask with B dividing the rows, an attn_mask [T, T] or [B * heads, T, T].  With is_causal the caller vouches
+        that attn_mask is the causal one (torch's contract): the kernel's causal flag is set and the mask is not read."""
+        R, T = (x.shape[0], x.shape[1]) if self.batch_first else (x.shape[1], x.shape[0])
+        ok = lambda m: not m.requires_grad and m.dtype in (torch.bool, torch.float32, torch.bfloat16)  # noqa: E731
+        am, kp, B = None if is_causal else attn_mask, key_padding_mask, 1
+        if am is not None:
+            if not ok(am) or am.dim() not in (2, 3) or tuple(am.shape[-2:]) != (T, T):
+                return False
+            if am.dim() == 3:
+                B = am.shape[0] // self.num_heads
+                if am.shape[0] % self.num_heads or B < 1 or R % B:
+                    return False
+        if kp is not None:
+            if not ok(kp) or kp.dim() != 2 or kp.shape[1] != T or kp.shape[0] < 1 or R % kp.shape[0]:
+                return False
+            if kp.dtype != torch.bool and am is not None and am.dim() == 3 and B not in (1, kp.shape[0]):
+                return False
+        return True
+
+    def _fused_masks(self, key_padding_mask, attn_mask, is_causal):
+        """(bool key-padding mask | None, causal flag, score bias | None) of the fused core, for masks _masks_fusable accepted.  A bool
+        key_padding_mask stays the kernel's key_pad; a float one becomes the [B, 1, 1, T] bias as a view (no copy); an attn_mask
+        becomes the bias as it lies ([T, T], or [B, heads, T, T] as a view of [B * heads, T, T]: under MC lanes row r reads mask row
+        r % B, as for padding).  A float key_padding_mask TOGETHER with an attn_mask is combined into one [B, 1 | heads, T, T] bias by
+        one eager broadcast add (torch.where for a bool attn_mask): an ordinary stream-ordered op, capturable, and the only T x T
+        tensor this path creates."""
+        if is_causal:
+            attn_mask = None
+        kp, bias = key_padding_mask, None
+        if attn_mask is not None:
+            bias = attn_mask if attn_mask.dim() == 2 else attn_mask.unflatten(0, (-1, self.num_heads))
+        if kp is not None and kp.dtype != torch.bool:
+            kb, kp = kp[:, None, None, :], None
+            if bias is None:
+                bias = kb
+            elif bias.dtype == torch.bool:
+                bias = torch.where(bias, float("-inf"), kb)
+            else:
+                bias = bias + kb
+        return kp, bool(is_causal), bias
 
     def _core(self, qkv, key_padding_mask, need_weights, attn_mask, average_attn_weights, is_causal):
         """the eager composite between the projections: qkv [rows, T, 3E] (any strides) -> (merged heads [rows, T, E], weights)"""
@@ -1340,9 +1384,15 @@ class _VariationalMHA(BaseVariationalLayer_):
             return s.masked_fill(m, float("-inf")) if m.dtype == torch.bool else s + m.to(cdt)
 
         if attn_mask is not None:
-            if tuple(attn_mask.shape) != (T, T):
-                raise _lib.BtxError("attn_mask must be [T, T] = [%d, %d], got %s" % (T, T, tuple(attn_mask.shape)))
-            s = apply(s, attn_mask)
+            B = attn_mask.shape[0] // H if attn_mask.dim() == 3 else 0
+            if attn_mask.dim() == 3 and tuple(attn_mask.shape[1:]) == (T, T) and B * H == attn_mask.shape[0] and B >= 1 and R % B == 0:
+                # MC lanes share the batch's mask (lane l's rows at l * B): broadcast over a leading lane axis, no copy of the mask
+                s = apply(s.reshape(R // B, B, H, T, T), attn_mask.unflatten(0, (B, H))).reshape(R, H, T, T)
+            elif tuple(attn_mask.shape) != (T, T):
+                raise _lib.BtxError("attn_mask must be [T, T] = [%d, %d] or [batch * heads, T, T] with batch dividing the rows %d, got %s"
+                                    % (T, T, R, tuple(attn_mask.shape)))
+            else:
+                s = apply(s, attn_mask)
         elif is_causal:
             s = apply(s, torch.ones(T, T, dtype=torch.bool, device=s.device).triu(1))
         if key_padding_mask is not None:
@@ -1388,12 +1438,13 @@ class _VariationalMHA(BaseVariationalLayer_):
         if fused:
             R, T, _ = rows_first.shape
             o = torch.empty((R, T, self.embed_dim) if self.batch_first else (T, R, self.embed_dim), dtype=qkv.dtype, device=qkv.device)
-            BF.attn_hip(rows_first, self.num_heads, key_padding_mask, causal=bool(is_causal or attn_mask is not None),
-                        prec=self.in_proj.precision or BF.get_precision(), out=o if self.batch_first else o.transpose(0, 1))
+            kp, causal, bias = self._fused_masks(key_padding_mask, attn_mask, is_causal)
+            BF.attn_hip(rows_first, self.num_heads, kp, causal=causal, prec=self.in_proj.precision or BF.get_precision(),
+                        out=o if self.batch_first else o.transpose(0, 1), bias=bias)
         elif fused_train:
             from .. import autograd as _ag
-            o = _ag.AttnFn.apply((self.num_heads, key_padding_mask, bool(is_causal or attn_mask is not None),
-                                  self.in_proj.precision or BF.get_precision()), rows_first)
+            kp, causal, bias = self._fused_masks(key_padding_mask, attn_mask, is_causal)
+            o = _ag.AttnFn.apply((self.num_heads, kp, causal, self.in_proj.precision or BF.get_precision(), bias), rows_first)
             o = o if self.batch_first else o.transpose(0, 1)
         else:
             o, w = self._core(rows_first, key_padding_mask, need_weights, attn_mask, average_attn_weights, is_causal)

@@ -159,13 +159,70 @@ def train(a):
             f.write(table + "\n")
 
 
+def bias(a):
+    """--bias: the core under an additive mask — fused with the bias, the composite on the same mask (what these inputs
+    took before the bias variant existed), and the fused core without a bias at the same shape (the variant's overhead); forward
+    (eval) and forward + backward (train) per shape class.  pad_float: a [rows, T] float key-padding mask, a quarter of every row's
+    keys padded; tt: a float [T, T] window of +-T/4; htt: a float bias DISTINCT per (row, head), given as [rows * heads, T, T] — the
+    variant's worst case, every element streamed once (a shared relative-position bias [heads, T, T] would be read with row stride 0)."""
+    from bayesian_torch_amd import autograd as ag, functional as BF, layers as L
+    dev = torch.device("cuda:0")
+    lines = ["--bias %s" % a.bias, "%-17s %-5s %-5s %11s %7s %13s %7s %11s %7s %9s %9s" % (
+        "core", "dtype", "mode", "bias ms", "spread", "composite ms", "spread", "no-bias ms", "spread", "comp / b", "b / no-b")]
+    for name, R, T, H, D, causal in SHAPES:
+        if causal:
+            continue  # the causal flag needs no bias
+        for dt, prec in ((torch.bfloat16, "bf16"), (torch.float32, "f32")):
+            torch.manual_seed(0)
+            layer = L.MultiheadAttentionReparameterization(H * D, H, batch_first=True)
+            qkv = (0.5 * torch.randn(R, T, 3 * H * D, device=dev)).to(dt).requires_grad_()
+            d_out = torch.randn(R, T, H * D, device=dev).to(dt)
+            kp = am = None
+            if a.bias == "pad_float":
+                kp = torch.zeros(R, T, device=dev, dtype=dt).masked_fill(torch.arange(T, device=dev)[None, :] >= T - T // 4, float("-inf"))
+            elif a.bias == "tt":
+                idx = torch.arange(T, device=dev)
+                am = torch.zeros(T, T, device=dev, dtype=dt).masked_fill((idx[:, None] - idx[None, :]).abs() > T // 4, float("-inf"))
+            else:
+                am = torch.randn(R * H, T, T, device=dev).to(dt)   # [rows * heads, T, T], as nn.MultiheadAttention takes it
+            kpb, _, b = layer._fused_masks(kp, am, False)
+            G = torch.autograd.grad
+            for mode in ("eval", "train"):
+                if mode == "eval":
+                    fns = dict(bias=_graphed(lambda: BF.attn_hip(qkv.detach(), H, kpb, prec=prec, bias=b)),
+                               composite=_graphed(lambda: layer._core(qkv.detach(), kp, False, am, True, False)),
+                               nobias=_graphed(lambda: BF.attn_hip(qkv.detach(), H, prec=prec)))
+                else:
+                    fns = dict(bias=_graphed(lambda: G(ag.AttnFn.apply((H, kpb, False, prec, b), qkv), qkv, d_out), True),
+                               composite=_graphed(lambda: G(layer._core(qkv, kp, False, am, True, False)[0], qkv, d_out), True),
+                               nobias=_graphed(lambda: G(ag.AttnFn.apply((H, None, False, prec), qkv), qkv, d_out), True))
+                r = _alternate(fns, a.calls, a.regions)
+                print(json.dumps(dict(core=name, dtype=prec, mode=mode, bias=a.bias, **{k + "_ms": round(v[0], 5) for k, v in r.items()})), flush=True)
+                lines.append("%-17s %-5s %-5s %11.4f %6.1f%% %13.4f %6.1f%% %11.4f %6.1f%% %8.2fx %8.2fx" % (
+                    name, prec, mode, r["bias"][0], 100 * r["bias"][1], r["composite"][0], 100 * r["composite"][1], r["nobias"][0],
+                    100 * r["nobias"][1], r["composite"][0] / r["bias"][0], r["bias"][0] / r["nobias"][0]))
+                del fns
+    table = "\n".join(lines)
+    print(table)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            f.write(table + "\n\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=10)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--train", action="store_true", help="time forward + backward (DESIGN.md section 31) instead of the inference forward")
+    ap.add_argument("--bias", choices=("none", "pad_float", "tt", "htt"), default="none",
+                    help="time the core under an additive mask (DESIGN.md section 32): appended to --out")
     a = ap.parse_args()
+    if a.bias != "none":
+        if not torch.cuda.is_available():
+            raise SystemExit("attn_bench needs a GPU: nothing is measured without one")
+        return bias(a)
     if a.train:
         if not torch.cuda.is_available():
             raise SystemExit("attn_bench needs a GPU: nothing is measured without one")
